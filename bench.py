@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the per-block IQ receive chain on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One process per GPU (launched by torch.distributed.run for N > 1).  Channels are
 sharded by rank with no data-path collective (RCCL unused; the only
@@ -11,11 +11,17 @@ every channel of the rank, already resident in HBM.  Rank 0 prints ONE JSON
 line.  Default workload = BASELINE.json configs[2] (K3, "full SSB+NR chain":
 4096 channels, USB + 512-pt spectral NR + LMS auto-notch + AGC), the
 configuration the metric is quoted on; --config K2|K4|K5 selects the others.
-The default run (no --config) times the K3 headline leg and then, each the same
-way, K2, the K5 per-GPU shape and K4 (`configs` in the line; N > 1: K5 only).
+A plain run sets up, warms up, times the --steps steps of that one leg and prints
+the line.  With --full the run goes on to everything else it measures: the
+isolated per-kernel durations (`kernels_ms_isolated`), then, each timed the same
+way, K2, the K5 per-GPU shape, K4 and the other legs of `configs` (N > 1: the K5
+leg only), the host-memory leg (`host_io`) and the CPU baseline.
 Stage A3 runs in the throughput form (rdsp_chain_set_fir_variant 2, named in
 `config.decimator`); every leg is preceded by un-timed settle steps
 (`setup_steps`) so that the timed steps are a stream in flight.
+--dump-outputs DIR writes the int16 audio of the headline leg's last timed step
+(a fixed, seeded sample of its channels, as float32) to DIR/audio.npy, so that two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -60,7 +66,7 @@ def parse():
     ap.add_argument("--no-host-io", action="store_true",
                     help="skip the extra PCIe-inclusive leg (host memory -> chain -> host memory)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the K2 / K4 / K5 legs that follow the headline leg of the default run")
+                    help="--full: skip the K2 / K4 / K5 legs that follow the headline leg of the default run")
     ap.add_argument("--spectral-as-written", action="store_true",
                     help="spectral stage re-synthesis as SPEC:229-232 writes it (atan2 + CMSIS table sine / cosine) instead of "
                          "the exact-arithmetic equivalent X mag'/mag (rdsp_set_spectral_resynthesis)")
@@ -69,6 +75,11 @@ def parse():
                     help="A/B runs: another build of librdsp_hip.so (default: the in-tree one); named in the JSON line")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction / JSON plumbing only, no device work (CPU-side test of --gpus N)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, everything else: isolated per-kernel durations, the other configurations, "
+                         "the host-memory leg and the CPU baseline (the --no-* switches still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the audio of the headline leg's last timed step (seeded channel sample, float32) to DIR/audio.npy")
     return ap.parse_args()
 
 
@@ -151,7 +162,7 @@ def f1_cpu_baseline(args):
     import oracle_lib
     from radiodsp_sdr_rx_amd.chain import synth_iq
     cores = host_cores(1)
-    lib = C.CDLL(oracle_lib.build(native=True, out_dir="/tmp"))
+    lib = C.CDLL(oracle_lib.build(native=True))
     lib.orc_fft256iq_multi.restype = C.c_uint64
     lib.orc_fft256iq_multi.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_int, C.c_int]
     nblk, nch = 512, cores * 16
@@ -208,7 +219,7 @@ def f1_main(args):
                         "valu": valu, "counters_note": ctr_note,
                         "note": "algorithmic bytes = 4 B per input sample (the spectra written are < 0.1 %); "
                                 "integer VALU issue binds"}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-worker", "--config", "F1"],
                                capture_output=True, text=True, timeout=600)
@@ -233,7 +244,7 @@ def k1_main(args):
     from radiodsp_sdr_rx_amd.graph import Graph
 
     cfg = dict(R.K_CONFIGS["K1"]["cfg"])
-    lib = oracle_lib.load(oracle_lib.build(native=True, out_dir="/tmp"))
+    lib = oracle_lib.load(oracle_lib.build(native=True))
     nblk = max(64, (min(args.blocks, 512) // 4) * 4)
     iq = synth_iq(1, nblk * 128)[0]                      # [n, 2] int16
     chain = oracle_lib.OracleChain(lib=lib, **cfg)
@@ -317,7 +328,7 @@ def cpu_baseline_worker(args):
     kc = R.K_CONFIGS[args.config]
     cfg = dict(kc["cfg"])
     cores = host_cores(1)
-    so = oracle_lib.build(native=True, out_dir="/tmp")
+    so = oracle_lib.build(native=True)
     lib = oracle_lib.load(so)
     # calibrate on a small sample, then size the timed sample to ~cpu-seconds
     nblk = min(args.blocks, 512)
@@ -386,7 +397,7 @@ def dry_run(args, rank, world, dist):
                 "ms_per_step": elapsed / args.steps * 1e3, "per_rank_ms": per_rank, "data": "dry-run",
                 "config": {"workload": f"{args.config}: {kc_channels} channels/GPU (not run)",
                            "sharding": f"channels x{world}, no collectives"}}
-        if world > 1 and args.config == "K3":   # the shape of the second leg of a real N > 1 run
+        if world > 1 and args.config == "K3" and args.full:   # the shape of the second leg of a real N > 1 --full run
             line["k5"] = {"config": "K5", "channels_per_gpu": 8192, "channels_total": 8192 * world, "steps": 0,
                           "ms_per_step": None, "value": None, "unit": "IQ Msamples/s", "note": "dry run"}
         print(json.dumps(line))
@@ -400,6 +411,30 @@ WORKLOAD_TEXT = {"K2": "NCO mix + 256-tap polyphase /4 + 256-pt overlap-save USB
                  "K3": "NCO mix + 256-tap polyphase /4 + 512-pt overlap-save USB filter + spectral NR + LMS auto-notch + AGC",
                  "K4": "NCO mix + 256-tap polyphase /4 + 4096-pt overlap-save CW filter (2049 taps) + AGC",
                  "K5": "K3 chain, 8192 channels/GPU"}
+
+
+DUMP_CHANNELS = 256            # channels --dump-outputs keeps at most (4096 x 16 384 x 2 samples would be 512 MB as float32)
+DUMP_BUDGET_BYTES = 48 << 20   # and bytes in all
+
+
+def dump_outputs(torch, out, directory, rank):
+    """--dump-outputs: the int16 audio [channels, samples, 2] the last timed step wrote, as float32 (exact) in
+    DIR/audio.npy (rank r > 0: DIR/audio_rank<r>.npy).  Every channel up to DUMP_CHANNELS, above that a fixed sample
+    (numpy default_rng(0), sorted), each channel's whole step unless that breaks the budget (then its first samples).
+    Returns what the JSON line says about it."""
+    import numpy as np
+    nch, nout = out.shape[0], out.shape[1]
+    k = max(1, min(nch, DUMP_CHANNELS, DUMP_BUDGET_BYTES // (nout * 2 * 4)))
+    idx = np.arange(nch) if k == nch else np.sort(np.random.default_rng(0).choice(nch, size=k, replace=False))
+    n = min(nout, DUMP_BUDGET_BYTES // (k * 2 * 4))
+    sel = out.index_select(0, torch.from_numpy(idx).to(out.device))[:, :n].cpu().numpy().astype(np.float32)
+    os.makedirs(directory, exist_ok=True)
+    name = "audio.npy" if rank == 0 else f"audio_rank{rank}.npy"
+    np.save(os.path.join(directory, name), sel)
+    return {"dir": os.path.abspath(directory), "files": [name], "shape": list(sel.shape), "dtype": "float32",
+            "sample": f"int16 audio [channel, sample, L/R] of the last timed step; {k} of {nch} channels"
+                      + ("" if k == nch else " (numpy default_rng(0), sorted)")
+                      + ("" if n == nout else f", first {n} of {nout} samples")}
 
 
 def dominant_kernel(fname, front_avg, tail_avg, decim):
@@ -541,6 +576,9 @@ def main():
         _lib.use_library(args.lib)
     if args.cpu_baseline_worker:
         return f1_cpu_baseline(args) if args.config == "F1" else cpu_baseline_worker(args)
+    if args.dump_outputs and (args.config in ("K1", "F1", "ENGINE") or args.dry_run):
+        sys.exit("--dump-outputs writes the audio of the chain configurations (K2 ... K5), not of --config "
+                 f"{args.config}{' --dry-run' if args.dry_run else ''}")
     if args.config == "F1":
         return f1_main(args)
     if args.config == "K1":
@@ -645,9 +683,13 @@ def main():
     if os.environ.get("RDSP_FRONT_VARIANT"):  # A/B runs: force the full (0) or lean (1) front kernel
         chain.set_front_variant(int(os.environ["RDSP_FRONT_VARIANT"]))
     # set-up, un-timed: the same kernels back to back without overlap (reference durations for the
-    # JSON line).  It runs before the warm-up so that the GPU has left its idle clocks by then.
-    iso = None
+    # JSON line).  It runs before the warm-up so that the GPU has left its idle clocks by then.  A plain
+    # run makes the same steps, HIP events included (the timed steps record into the same pool), and
+    # leaves their durations, --full's `kernels_ms_isolated`, unread: the clocks the timed steps start
+    # from and the stream they continue do not depend on --full.
+    iso, iso_steps = None, 0
     if not args.no_kernel_timing and not args.no_pipeline and not args.no_iso:
+        iso_steps = 30
         chain.set_pipelined(False)
         for _ in range(20):      # the clocks of an idle GPU ramp over ~15 steps
             chain.process(iq, out=out)
@@ -655,9 +697,10 @@ def main():
         for _ in range(10):
             chain.process(iq, out=out)
         torch.cuda.synchronize()
-        f2, t2, n2 = chain.get_timing()
+        if args.full:
+            f2, t2, n2 = chain.get_timing()
+            iso = {chain.front_kernel_name(): f2 / max(n2, 1), "rdsp_tail_kernel": t2 / max(n2, 1)}
         chain.set_timing(False)
-        iso = {chain.front_kernel_name(): f2 / max(n2, 1), "rdsp_tail_kernel": t2 / max(n2, 1)}
         chain.set_pipelined(True)
     # set-up, un-timed: the package's power management needs ~15 steps of the PIPELINED load to settle (the two
     # kernels together sit at the 1400 W cap; behind the lighter set-up above the first pipelined steps run
@@ -684,14 +727,15 @@ def main():
     span_ms, _ = chain.get_timing_span()
     chain.set_timing(False)
     elapsed, per_rank = gather_per_rank(torch, dist, world, elapsed, args.steps, span_ms / (calls - 1) if calls > 1 else None)
+    dumped = dump_outputs(torch, out, args.dump_outputs, rank) if args.dump_outputs else None
 
-    # After the headline leg, the other GPU configurations of BASELINE.json, each timed the same way (extra_leg):
+    # --full: after the headline leg, the other GPU configurations of BASELINE.json, each timed the same way (extra_leg):
     # N = 1: K2, K4 and the K5 per-GPU shape; N > 1: the K5 shape (8192 channels per GPU, 65 536 at N = 8).  The
     # headline `value` / `config` stay the K3 per-GPU workload for every N.
     fname = chain.front_kernel_name()   # rdsp_front_fd_kernel (stage A3 in the frequency domain) or rdsp_front_kernel
     legs = {}
     default_shape = args.config == "K3" and not args.channels_per_gpu and args.groups == 1
-    if default_shape and not args.no_extra_legs and not os.environ.get("RDSP_BENCH_NO_K5_LEG"):
+    if args.full and default_shape and not args.no_extra_legs and not os.environ.get("RDSP_BENCH_NO_K5_LEG"):
         # K3_default: the headline workload with the library's DEFAULT decimator (one granule per frame), i.e. what a
         # caller who selects nothing gets; then the other configurations in the headline's form
         which = ["K5"] if world > 1 else ["K3_default", "K3_as_written", "K2", "K2_default", "K5", "K4", "engine_literal"]
@@ -805,7 +849,7 @@ def main():
                                   "busy_frac_pmc": {k: v.get("valu_busy_frac") for k, v in ctr.items()
                                                     if k in (fname, "rdsp_tail_kernel")} or None}},
             "input_gen_s": gen_s,
-            "setup_steps": {"unpipelined_kernel_reference": 30 if iso is not None else 0, "settle_before_warmup": settle,
+            "setup_steps": {"unpipelined_kernel_reference": iso_steps, "settle_before_warmup": settle,
                             "note": "un-timed, before the --warmup steps: clock / power settling of the GPU under this load"},
             # what "matches the reference's CPU path" means here (tests/parity_util.py; a deviation from the
             # north-star's blanket 1e-5 for the bare-recursion chains, stated where the number is read)
@@ -836,7 +880,9 @@ def main():
             res["configs"] = legs      # K2 / K4 / K5-per-GPU legs of the same run (N > 1: K5 only)
         if k5_leg is not None:
             res["k5"] = k5_leg
-        if world == 1 and not args.no_host_io:
+        if dumped is not None:
+            res["outputs"] = dumped
+        if args.full and world == 1 and not args.no_host_io:
             # extra, un-timed for `value`: the same chain fed from and drained to host memory through
             # rdsp_stream_run_memory (pinned double buffers, upload / kernels / download overlapped)
             try:
@@ -871,7 +917,7 @@ def main():
                 del h_np
             except Exception as e:
                 res["host_io"] = {"value": None, "sample": f"failed: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-worker",
                                     "--config", args.config, "--blocks", str(nblk),

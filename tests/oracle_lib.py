@@ -69,7 +69,8 @@ def fill_config(struct_cls, **kw):
 
 def build(native=False, out_dir=None):
     """Compile the oracle.  native=True builds the -O3 -march=native variant used
-    only for the cpu_baseline timing leg (built on the box it runs on)."""
+    only for the cpu_baseline timing leg (built on the box it runs on, beside the
+    portable build unless out_dir says otherwise)."""
     if not native:
         so = os.path.join(ORACLE_DIR, "liboracle.so")
         srcs = [os.path.join(ORACLE_DIR, f) for f in ("rdsp_oracle.c", "rdsp_oracle.h", "Makefile")]
@@ -79,11 +80,13 @@ def build(native=False, out_dir=None):
             return so
         subprocess.check_call(["make", "-s", "-C", ORACLE_DIR])
         return so
-    out_dir = out_dir or "/tmp"
+    out_dir = out_dir or ORACLE_DIR
     so = os.path.join(out_dir, "liboracle_native.so")
+    tmp = f"{so}.{os.getpid()}"   # written aside, then renamed: a concurrent build never sees half a library
     subprocess.check_call(
         ["gcc", "-O3", "-march=native", "-ffp-contract=off", "-fPIC", "-fopenmp", "-shared",
-         "-o", so, os.path.join(ORACLE_DIR, "rdsp_oracle.c"), "-lm"])
+         "-o", tmp, os.path.join(ORACLE_DIR, "rdsp_oracle.c"), "-lm"])
+    os.replace(tmp, so)
     return so
 
 

@@ -74,3 +74,43 @@ def test_bench_step_shape_matches_the_oracle(rdsp, oracle, name):
         assert bool(torch.isfinite(pw).all()) and float(pw.min()) > 1e-7
     sc = ch.scalars()
     assert np.isfinite(sc).all()
+
+
+def test_plain_bench_run_times_the_steps_asked_and_dumps_its_last_step(rdsp, tmp_path):
+    """`bench.py --steps N --warmup W --dump-outputs DIR` at a small K3 shape, in a child process: the line counts the N
+    steps it timed, carries none of --full's legs, and DIR/audio.npy is bit for bit the audio of the last of them -- the
+    same chain fed the same input in the same sequence of calls here (bench.py's un-timed set-up included)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    from radiodsp_sdr_rx_amd.chain import Chain, synth_iq
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nch, nblk, steps, warmup = 64, 32, 3, 2
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RDSP_")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--channels-per-gpu", str(nch), "--blocks", str(nblk),
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0
+    assert not {"configs", "host_io", "cpu_baseline", "k5"} & set(d) and d["kernels_ms_isolated"] is None
+    assert d["outputs"]["files"] == ["audio.npy"] and d["outputs"]["shape"] == [nch, nblk * 32, 2]
+    got = np.load(tmp_path / "audio.npy")
+    assert got.dtype == np.float32 and got.shape == (nch, nblk * 32, 2)
+
+    import radiodsp_sdr_rx_amd as R
+    iq = torch.from_numpy(synth_iq(nch, nblk * 128)).cuda()
+    ch = Chain(nch, max_blocks_per_call=nblk, fir_variant=2, **dict(R.K_CONFIGS["K3"]["cfg"]))
+    out = torch.empty((nch, nblk * 32, 2), dtype=torch.int16, device="cuda")
+    ch.set_pipelined(False)
+    for _ in range(30):                                   # bench.py's un-timed set-up without overlap
+        ch.process(iq, out=out)
+    ch.set_pipelined(True)
+    for _ in range(max(0, 40 - warmup) + warmup + steps):  # settle, warm-up, timed steps
+        ch.process(iq, out=out)
+    ch.flush()
+    torch.cuda.synchronize()
+    want = out.cpu().numpy()
+    assert np.abs(want).max() > 0 and np.array_equal(got, want.astype(np.float32))

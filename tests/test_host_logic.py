@@ -349,14 +349,14 @@ def test_channel_sharding_world_size_2_gloo(tmp_path):
 
 
 def test_bench_gpus_2_launches_two_ranks(tmp_path):
-    """`python bench.py --gpus 2` (the driver's command form, no WORLD_SIZE in the environment)
+    """`python bench.py --gpus 2 --full` (the driver's command form, no WORLD_SIZE in the environment)
     starts two ranks as a child process and relays rank 0's single JSON line with n_gpus = 2.
     --dry-run replaces the device work by a sleep: launcher, rendezvous (gloo, 127.0.0.1), the
     barrier + max-over-ranks reduction and the one-line protocol are the real ones."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0",
-                        "--dry-run"], capture_output=True, text=True, env=env, timeout=300)
+                        "--full", "--dry-run"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                      # ONE JSON line on stdout
@@ -373,6 +373,23 @@ def test_bench_gpus_2_launches_two_ranks(tmp_path):
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True,
                          text=True, env=dict(env, WORLD_SIZE="1", RANK="0"), timeout=120)
     assert bad.returncode != 0 and "WORLD_SIZE=1" in bad.stderr
+
+
+def test_plain_bench_dry_run_carries_the_headline_leg_only():
+    """Without --full, `bench.py --gpus 2` times the headline leg and nothing after it: no K5 leg in the line."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0",
+                        "--dry-run"], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and "k5" not in d
+    # --dump-outputs has nothing to write in a dry run, and says so
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--dump-outputs", "unused"],
+                         capture_output=True, text=True, env=env, timeout=120)
+    assert bad.returncode != 0 and "--dump-outputs" in bad.stderr
 
 
 def test_bench_quotes_pmc_constants_only_for_the_sources_they_were_taken_on(tmp_path, monkeypatch):
