@@ -136,6 +136,45 @@ int rdsp_Init_LMS_NR(rdsp_chain_t *c, int LMS_nr_strength, void *stream);
 int rdsp_LMS_NoiseReduction(rdsp_chain_t *c, int n_samples, float *d_nrbuffer, size_t stride,
                             void *stream);
 
+/* ---- the law of the chain's tail: A8 ALS notch / peak and A9 AGC ---------------------------------------------
+ * RDSP_TAIL_BUILD (the default): this build's stand-ins -- A8 a 96-tap NLMS instance on the DSP-NR core, A9 a per-block
+ * RMS gain -- in the order ALS, AGC.  RDSP_TAIL_ENGINE: the reference engine's own laws (AudioSDR, restated from the
+ * firmware image; rdsp_engine_t runs them too), bit for bit with the image's stage taps:
+ *   Order.  [A7 DSP-NR NLMS if lms_nr > 0, unchanged, x 1.1 as CONV:334] -> engine AGC -> engine ALS -> output gain ->
+ *     the chain's pack (arm_float_to_q15 rounding, L = R; not the engine's truncating wrap).  d_out_f32 is the parity
+ *     surface.  Spectral stage, IIR bank and SAM in front are unchanged.
+ *   AGC (0xdb58).  Peak envelope with attack, hang counter and decay; the gain is looked up from the generated 130-entry
+ *     curve (0xdd40: trunc((double)env x 32767), fmaf interpolation), then (g x 10) x, clamped to +-1.  The chain's
+ *     agc_mode 1 .. 3 at creation, and rdsp_sdr_setAGCmode(c, k), select the image's set k (0xdfe0: fast / medium / slow);
+ *     mode 0 switches the AGC off and keeps the set; enableAGC / disableAGC switch it on / off as the engine's do.
+ *     Before any set is selected the constructor's applies (0xdf14: medium attack, slow decay, hang 4410).
+ *   ALS (0xda24).  55 taps, delay 3, mu 0.5, always adaptive (the image has no setter for it): the taps move on the
+ *     first and every fourth sample of each block, in the image's serial fmaf order.  als_mode RDSP_ALS_NOTCH outputs
+ *     the error, RDSP_ALS_PEAK the prediction; als_strength is ignored.  rdsp_sdr_enableALSfilter clears the line and
+ *     the taps at the next launch (0xdb2c).
+ *   Rate.  Both laws are defined per sample, as the image stores them, and are not rescaled: at the chain's 24 kHz
+ *     audio (96 kHz / 4) the hang times of the fast / medium / slow sets are 0.18 / 0.92 / 3.7 s, not the 0.1 / 0.5 /
+ *     2.0 s they are at the engine's 44.1 kHz, and the attack / decay time constants stretch by the same 1.84.
+ *   Where it runs.  With the engine law and the AGC or the ALS filter on, a tail stage follows the front kernel (the
+ *     front kernel's own AGC stays off); the default decimator picks its tail-side form accordingly.
+ *   State.  Per channel: envelope, gain, hang counter, active flag, the ALS line's newest 64 samples and the 55 taps;
+ *     allocated by the first switch to RDSP_TAIL_ENGINE, at the engine constructor's values (gain 0, active 1, the rest
+ *     0).  Switching law resets the tail state of the law switched to (RDSP_TAIL_BUILD: ALS instance cleared, AGC gain
+ *     1); setting the current law again changes nothing.  rdsp_chain_reset returns it to those values;
+ *     rdsp_chain_get_scalars slot 1 reports the engine AGC's gain; rdsp_chain_get_status reports no ALS bits under this
+ *     law; rdsp_chain_save_state / load_state carry it as an optional part once it is allocated (a blob that carries it
+ *     loads only into a chain switched to RDSP_TAIL_ENGINE first).  Chains that never switch keep their blobs.
+ *   Channel groups share the chain-wide AGC / ALS settings.  A set-up call: not while calls are in flight. */
+typedef enum { RDSP_TAIL_BUILD = 0, RDSP_TAIL_ENGINE = 1 } rdsp_tail_law_t;
+/* RDSP_ERR_INVALID for a law outside {0, 1}; RDSP_ERR_UNSUPPORTED for RDSP_TAIL_ENGINE on an engine-literal chain
+ * (rdsp_sdr_set_engine_literal: there the setters reach the engine object itself) */
+int rdsp_chain_set_tail_law(rdsp_chain_t *c, int law);
+int rdsp_chain_get_tail_law(const rdsp_chain_t *c);
+/* the engine-law AGC then ALS filter (as the chain's settings select them), in place on float audio
+ * d_audio[n_channels][stride], n_samples a positive multiple of 128; carries the chain's own tail state.  No NR, no
+ * output gain, no pack.  RDSP_ERR_UNSUPPORTED under RDSP_TAIL_BUILD. */
+int rdsp_chain_run_tail_f32(rdsp_chain_t *c, float *d_audio, size_t stride, int n_samples, void *stream);
+
 /* The hot path.  doConvolutionalProcessing (CONV:228 / SPEC:112) with the
  * engine stages in front and behind it, for every channel, over n_blocks
  * input blocks of 128 IQ samples per channel.

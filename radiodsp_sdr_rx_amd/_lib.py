@@ -96,6 +96,9 @@ SYMBOLS = [
     ("rdsp_reInitializeFilter", _i, [_vp, _d, _d, _vp]),
     ("rdsp_Init_LMS_NR", _i, [_vp, _i, _vp]),
     ("rdsp_LMS_NoiseReduction", _i, [_vp, _i, _vp, _sz, _vp]),
+    ("rdsp_chain_set_tail_law", _i, [_vp, _i]),
+    ("rdsp_chain_get_tail_law", _i, [_vp]),
+    ("rdsp_chain_run_tail_f32", _i, [_vp, _vp, _sz, _i, _vp]),
     ("rdsp_chain_process", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp, _vp]),
     ("rdsp_doConvolutionalProcessing", _i, [_vp, _f, _i, _d, _d, _vp, _sz, _i, _vp, _sz, _vp]),
     ("rdsp_q15_to_float", _i, [_vp, _vp, _sz, _vp]),

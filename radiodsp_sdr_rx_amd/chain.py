@@ -104,6 +104,28 @@ class Chain:
                                                    nrbuffer.stride(0), _stream_ptr(stream)))
         return nrbuffer
 
+    # ---- the law of the tail stage (A8 ALS, A9 AGC): include/rdsp.h rdsp_chain_set_tail_law ----------------------
+    TAIL_LAWS = {"build": 0, "engine": 1}
+
+    def set_tail_law(self, law):
+        """"build" (0, the default: this build's NLMS notch and RMS AGC) or "engine" (1: the reference engine's hang AGC
+        then its 55-tap ALS filter, bit for bit with the image's stage taps)"""
+        _lib.check(self.lib.rdsp_chain_set_tail_law(self.h, self.TAIL_LAWS[law] if isinstance(law, str) else int(law)))
+
+    @property
+    def tail_law(self):
+        """the tail law in force: 0 (build) or 1 (engine)"""
+        return self.lib.rdsp_chain_get_tail_law(self.h)
+
+    def run_tail_f32(self, audio, stream=None):
+        """the engine-law AGC then ALS filter alone, in place on float32 cuda tensor [n_channels, n] (rows may be slices
+        of a wider buffer: unit sample stride)"""
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2 and audio.stride(1) == 1
+        assert audio.shape[0] == self.n_channels
+        _lib.check(self.lib.rdsp_chain_run_tail_f32(self.h, C.c_void_p(audio.data_ptr()), audio.stride(0), audio.shape[1],
+                                                   _stream_ptr(stream)))
+        return audio
+
     def doConvolutionalProcessing(self, iNRLevel, bFilterEnabled, dFLoCut, dFHiCut, iq, out=None,
                                   stream=None):
         n = iq.shape[1]

@@ -180,11 +180,20 @@ struct rdsp_chain {
   float hist_scale_i = 0.f, hist_scale_q = 0.f;
   int nb_on = 0;              /* SDR.enableNoiseBlanker, BK_INO:1259 */
   float nb_threshold_db = 10.0f;
+  /* rdsp_chain_set_tail_law: A8 / A9 as this build's stand-ins (RDSP_TAIL_BUILD) or as the engine's own laws
+   * (RDSP_TAIL_ENGINE: rdsp_tail_engine.hip).  The engine law's state ([ch][4] AGC words, [ch][128] ALS line and
+   * taps) is allocated by the first switch to it */
+  int tail_law = RDSP_TAIL_BUILD;
+  int eng_agc_set = 0;        /* the engine AGC's constants: 0 the constructor's (0xdf14), 1 .. 3 setAGCmode's */
+  bool eng_als_clear = false; /* enableALSfilter clears the engine ALS line and taps at the next launch (0xdb2c) */
+  float *d_eng_st = nullptr, *d_eng_als = nullptr;
 };
 
 static int drain_tail_fwd(rdsp_chain_t *c);
 static int ensure_sam(rdsp_chain_t *c);
 static int ensure_sub_batch_events(rdsp_chain_t *c);
+static int eng_tail_boot(rdsp_chain_t *c, int first, int n);
+static void eng_tail_params(const rdsp_chain_t *c, RdspTailEngineParams *ep, float *rows, size_t stride, int n_blocks);
 static void passband(int filter, int demod, double *lo, double *hi);
 static int chain_build(rdsp_chain_t *c, const rdsp_chain_config_t *cfg, int n_channels, int device,
                        int max_blocks_per_call, int decim);
@@ -424,6 +433,7 @@ static int chain_build(rdsp_chain_t *c, const rdsp_chain_config_t *cfg, int n_ch
   c->nr_mu = rdsp_lms_mu(15);      /* Init_LMS_NR(15), INO:172 */
   c->als_mu = rdsp_lms_mu(cfg->als_strength > 0 ? cfg->als_strength : 15);
   c->nr_calls = c->als_calls = 0;
+  c->eng_agc_set = (cfg->agc_mode >= RDSP_AGC_FAST && cfg->agc_mode <= RDSP_AGC_SLOW) ? cfg->agc_mode : 0;
   c->fir_nat.assign(256, 0.0f);
   if (check_device(c) != RDSP_OK) return RDSP_ERR_HIP;
   {
@@ -496,7 +506,8 @@ extern "C" void rdsp_chain_destroy(rdsp_chain_t *c) {
   if (c->d_engine_io) (void)hipFree(c->d_engine_io);
   void *ptrs[] = {c->d_iir_coef, c->d_iir_state, c->d_fd_mask, c->d_rd_mask, c->d_sin_table, c->d_mid_q[0], c->d_mid_q[1], c->d_mid_q[2], c->d_sam, c->d_groups, c->d_group_of, c->d_mask_pool, c->d_fir_hc, c->d_hist, c->d_prev, c->d_scal,
                   c->d_nr_w, c->d_nr_prev, c->d_nr_energy, c->d_als_w, c->d_als_prev,
-                  c->d_als_energy, c->d_status, c->d_mid, c->d_slip_buf, c->d_slip_carry[0], c->d_slip_carry[1]};
+                  c->d_als_energy, c->d_status, c->d_mid, c->d_slip_buf, c->d_slip_carry[0], c->d_slip_carry[1],
+                  c->d_eng_st, c->d_eng_als};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -590,6 +601,10 @@ extern "C" int rdsp_chain_reset(rdsp_chain_t *c, void *stream_) {
   for (auto &g : c->groups) { g.has_dev_dphi = false; g.dirty = true; }
   if (c->d_sam) HIP_TRY(hipMemset(c->d_sam, 0, sizeof(float) * 4 * nch));
   if (c->d_iir_state) HIP_TRY(hipMemset(c->d_iir_state, 0, sizeof(float) * 16 * nch));
+  if (c->d_eng_st) {
+    int rc = eng_tail_boot(c, 0, c->n_channels);
+    if (rc != RDSP_OK) return rc;
+  }
   return RDSP_OK;
 }
 
@@ -710,7 +725,11 @@ extern "C" int rdsp_chain_process(rdsp_chain_t *c, const int16_t *d_iq, size_t i
     rdsp_set_error("IIR audio filter without its buffers (internal)");
     return RDSP_ERR_INVALID;
   }
-  const bool tail = sam || iir || (cf.lms_nr > 0) || (cf.als_mode != RDSP_ALS_OFF);
+  /* RDSP_TAIL_ENGINE: the engine's AGC and ALS filter run in a tail stage whenever either is on; the front kernel's own
+   * AGC stays off */
+  const bool eng = c->tail_law == RDSP_TAIL_ENGINE;
+  const bool eng_stage = eng && (cf.agc_mode != RDSP_AGC_OFF || cf.als_mode != RDSP_ALS_OFF);
+  const bool tail = sam || iir || (cf.lms_nr > 0) || (!eng && cf.als_mode != RDSP_ALS_OFF) || eng_stage;
   float attack, decay;
   agc_params(cf.agc_mode, &attack, &decay);
   const float og = cf.mute ? 0.0f : cf.output_gain;
@@ -762,7 +781,7 @@ extern "C" int rdsp_chain_process(rdsp_chain_t *c, const int16_t *d_iq, size_t i
   fp.spectral_literal = (c->spectral_literal && cf.spectral_nr == 1) ? c->spectral_literal : 0; /* SPEC only: the older variant scales the bin (BK_INO:1614-1628) */
   fp.sin_table = c->d_sin_table;
   fp.to_mid = tail ? 1 : 0;
-  fp.agc_on = cf.agc_mode != RDSP_AGC_OFF;
+  fp.agc_on = !eng && cf.agc_mode != RDSP_AGC_OFF;
   fp.agc_attack = attack;
   fp.agc_decay = decay;
   fp.out_gain = og;
@@ -915,7 +934,7 @@ extern "C" int rdsp_chain_process(rdsp_chain_t *c, const int16_t *d_iq, size_t i
     tp.n_channels = c->n_channels;
     tp.n_blocks = (int)(n_out / RDSP_BLOCK);
     tp.nr_on = cf.lms_nr > 0;
-    tp.als_mode = cf.als_mode;
+    tp.als_mode = eng ? RDSP_ALS_OFF : cf.als_mode;
     tp.nr_mu = c->nr_mu;
     tp.als_mu = c->als_mu;
     tp.nr_first = (c->nr_calls == 0);
@@ -934,13 +953,29 @@ extern "C" int rdsp_chain_process(rdsp_chain_t *c, const int16_t *d_iq, size_t i
     tp.out_i16 = reinterpret_cast<uint32_t *>(d_out);
     tp.out_stride = out_stride;
     tp.out_f32 = reinterpret_cast<float2 *>(d_out_f32);
+    RdspTailEngineParams ep;
+    if (eng) {
+      /* [A7 DSP-NR as rdsp_LMS_NoiseReduction runs it, x 1.1 (CONV:334), floats in place] -> engine AGC -> engine ALS
+       * -> output gain -> pack */
+      eng_tail_params(c, &ep, fp.mid, c->mid_stride, (int)(n_out / RDSP_BLOCK));
+      ep.out_i16 = tp.out_i16; ep.out_f32 = tp.out_f32; ep.out_stride = out_stride; ep.out_gain = og;
+      ep.prio = tp.prio;
+      tp.raw_out = fp.mid;
+      tp.nr_mode = 0;
+    }
     if (timed) HIP_TRY(hipEventRecord(ev2, tstream));
     for (int k = 0; k < nsb && e == 0; k++) {
       tp.ch_base = k * sbn;
       tp.n_channels = (c->n_channels - tp.ch_base < sbn) ? c->n_channels : tp.ch_base + sbn;
       if (nsb > 1) HIP_TRY(hipStreamWaitEvent(c->s_tail, c->ev_front_sb[slot][k], 0));
-      e = rdsp_launch_tail(&tp, c->tail_lpc, tstream);
+      if (!eng || tp.nr_on) e = rdsp_launch_tail(&tp, c->tail_lpc, tstream);
+      if (eng && e == 0) {
+        ep.ch_base = tp.ch_base;
+        ep.n_channels = tp.n_channels;
+        e = rdsp_launch_tail_engine(&ep, tstream);
+      }
     }
+    if (eng && ep.als_on) c->eng_als_clear = false;
     if (e != 0) {
       rdsp_set_error("tail kernel launch failed: %s", hipGetErrorString((hipError_t)e));
       return RDSP_ERR_HIP;
@@ -1002,6 +1037,103 @@ extern "C" int rdsp_LMS_NoiseReduction(rdsp_chain_t *c, int n_samples, float *d_
   return RDSP_OK;
 }
 
+/* ---- the engine law of the chain's tail (RDSP_TAIL_ENGINE) --------------------------------------------------- */
+/* boot values of the engine-law state of channels [first, first + n): envelope, gain and hang counter 0, the active flag 1
+ * (the constructor's values, until the AGC first runs), ALS line and taps 0.  Stream-ordered behind everything queued. */
+static int eng_tail_boot(rdsp_chain_t *c, int first, int n) {
+  if (c->s_tail) HIP_TRY(hipStreamSynchronize(c->s_tail));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<float> st((size_t)RDSP_ENG_ST_WORDS * (size_t)n, 0.0f);
+  for (int i = 0; i < n; i++) {
+    const int one = 1;
+    memcpy(&st[(size_t)RDSP_ENG_ST_WORDS * i + 3], &one, 4);
+  }
+  HIP_TRY(hipMemcpy(c->d_eng_st + (size_t)RDSP_ENG_ST_WORDS * first, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(c->d_eng_als + (size_t)RDSP_ENG_ALS_WORDS * first, 0, sizeof(float) * RDSP_ENG_ALS_WORDS * (size_t)n));
+  return RDSP_OK;
+}
+/* what a launch of the engine-law stage takes from the chain's settings */
+static void eng_tail_params(const rdsp_chain_t *c, RdspTailEngineParams *ep, float *rows, size_t stride, int n_blocks) {
+  memset(ep, 0, sizeof(*ep));
+  rdsp_tail_engine_constants(ep, c->eng_agc_set);
+  ep->in = rows;
+  ep->in_stride = stride;
+  ep->n_channels = c->n_channels;
+  ep->n_blocks = n_blocks;
+  ep->st = c->d_eng_st;
+  ep->als = c->d_eng_als;
+  ep->agc_on = c->cfg.agc_mode != RDSP_AGC_OFF;
+  ep->als_on = c->cfg.als_mode != RDSP_ALS_OFF;
+  ep->als_notch = c->cfg.als_mode == RDSP_ALS_NOTCH;
+  ep->als_clear = c->eng_als_clear ? 1 : 0;
+}
+
+extern "C" int rdsp_chain_set_tail_law(rdsp_chain_t *c, int law) {
+  if (!c) return RDSP_ERR_INVALID;
+  if (law != RDSP_TAIL_BUILD && law != RDSP_TAIL_ENGINE) {
+    rdsp_set_error("rdsp_chain_set_tail_law: law %d is not RDSP_TAIL_BUILD (0) or RDSP_TAIL_ENGINE (1)", law);
+    return RDSP_ERR_INVALID;
+  }
+  if (law == RDSP_TAIL_ENGINE && c->engine) {
+    rdsp_set_error("rdsp_chain_set_tail_law: the engine-literal chain runs the reference's engine itself; its setters reach that object");
+    return RDSP_ERR_UNSUPPORTED;
+  }
+  if (law == c->tail_law) return RDSP_OK;
+  if (check_device(c) != RDSP_OK) return RDSP_ERR_HIP;
+  if (c->s_tail) HIP_TRY(hipStreamSynchronize(c->s_tail));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nch = (size_t)c->n_channels;
+  if (law == RDSP_TAIL_ENGINE) {
+    if (!c->d_eng_st) {
+      HIP_TRY(hipMalloc((void **)&c->d_eng_st, sizeof(float) * RDSP_ENG_ST_WORDS * nch));
+      HIP_TRY(hipMalloc((void **)&c->d_eng_als, sizeof(float) * RDSP_ENG_ALS_WORDS * nch));
+    }
+    int rc = eng_tail_boot(c, 0, c->n_channels);
+    if (rc != RDSP_OK) return rc;
+    c->eng_als_clear = false;
+  } else { /* the build law's tail state as a fresh chain has it: ALS instance cleared, AGC gain 1 */
+    HIP_TRY(hipMemset(c->d_als_w, 0, sizeof(float) * RDSP_LMS_TAPS * nch));
+    HIP_TRY(hipMemset(c->d_als_prev, 0, sizeof(float) * RDSP_BLOCK * nch));
+    HIP_TRY(hipMemset(c->d_als_energy, 0, sizeof(float) * nch));
+    HIP_TRY(hipMemset(c->d_status + nch, 0, sizeof(uint32_t) * nch));
+    std::vector<float> sc(4 * nch);
+    HIP_TRY(hipMemcpy(sc.data(), c->d_scal, sc.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nch; i++) sc[4 * i + 1] = 1.0f;
+    HIP_TRY(hipMemcpy(c->d_scal, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->als_calls = 0;
+  }
+  c->tail_law = law;
+  return RDSP_OK;
+}
+extern "C" int rdsp_chain_get_tail_law(const rdsp_chain_t *c) { return c ? c->tail_law : RDSP_ERR_INVALID; }
+
+/* the engine-law AGC then ALS filter alone, in place on float audio [n_channels][stride] (what rdsp_LMS_NoiseReduction
+ * is to the DSP-NR instance) */
+extern "C" int rdsp_chain_run_tail_f32(rdsp_chain_t *c, float *d_audio, size_t stride, int n_samples, void *stream) {
+  if (!c) return RDSP_ERR_INVALID;
+  if (c->tail_law != RDSP_TAIL_ENGINE) {
+    rdsp_set_error("rdsp_chain_run_tail_f32: the chain's tail law is not RDSP_TAIL_ENGINE");
+    return RDSP_ERR_UNSUPPORTED;
+  }
+  if (!d_audio || n_samples <= 0 || n_samples % RDSP_BLOCK != 0 || stride < (size_t)n_samples) {
+    rdsp_set_error("rdsp_chain_run_tail_f32: bad argument (n_samples %d: a positive multiple of %d, stride %zu)", n_samples,
+                   RDSP_BLOCK, stride);
+    return RDSP_ERR_INVALID;
+  }
+  if (check_device(c) != RDSP_OK) return RDSP_ERR_HIP;
+  if (c->s_tail) HIP_TRY(hipStreamSynchronize(c->s_tail));
+  RdspTailEngineParams ep;
+  eng_tail_params(c, &ep, d_audio, stride, n_samples / RDSP_BLOCK);
+  ep.raw_out = d_audio;
+  int e = rdsp_launch_tail_engine(&ep, (hipStream_t)stream);
+  if (e != 0) {
+    rdsp_set_error("engine-law tail kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    return RDSP_ERR_HIP;
+  }
+  if (ep.als_on) c->eng_als_clear = false;
+  return RDSP_OK;
+}
+
 extern "C" int rdsp_doConvolutionalProcessing(rdsp_chain_t *c, float iNRLevel, int bFilterEnabled,
                                               double dFLoCut, double dFHiCut, const int16_t *d_iq,
                                               size_t in_stride, int n_blocks, int16_t *d_out,
@@ -1057,9 +1189,10 @@ extern "C" int rdsp_sdr_setAGCmode(rdsp_chain_t *c, int mode) {
   TO_ENGINE(c, rdsp_engine_setAGCmode(c->engine, mode));
   if (mode < RDSP_AGC_OFF || mode > RDSP_AGC_SLOW) return RDSP_ERR_INVALID;
   c->cfg.agc_mode = mode;
+  if (mode != RDSP_AGC_OFF) c->eng_agc_set = mode; /* 0xdfe0: mode 0 only switches the engine AGC off */
   return RDSP_OK;
 }
-extern "C" int rdsp_sdr_enableALSfilter(rdsp_chain_t *c) { NEED(c); TO_ENGINE(c, rdsp_engine_enableALSfilter(c->engine)); if (c->cfg.als_mode == RDSP_ALS_OFF) c->cfg.als_mode = c->saved_als_mode; return RDSP_OK; }
+extern "C" int rdsp_sdr_enableALSfilter(rdsp_chain_t *c) { NEED(c); TO_ENGINE(c, rdsp_engine_enableALSfilter(c->engine)); if (c->cfg.als_mode == RDSP_ALS_OFF) c->cfg.als_mode = c->saved_als_mode; c->eng_als_clear = true; return RDSP_OK; }
 extern "C" int rdsp_sdr_disableALSfilter(rdsp_chain_t *c) { NEED(c); TO_ENGINE(c, rdsp_engine_disableALSfilter(c->engine)); if (c->cfg.als_mode != RDSP_ALS_OFF) c->saved_als_mode = c->cfg.als_mode; c->cfg.als_mode = RDSP_ALS_OFF; return RDSP_OK; }
 extern "C" int rdsp_sdr_setALSfilterNotch(rdsp_chain_t *c) { NEED(c); TO_ENGINE(c, rdsp_engine_setALSfilterNotch(c->engine)); c->saved_als_mode = RDSP_ALS_NOTCH; if (c->cfg.als_mode != RDSP_ALS_OFF) c->cfg.als_mode = RDSP_ALS_NOTCH; return RDSP_OK; }
 extern "C" int rdsp_sdr_setALSfilterPeak(rdsp_chain_t *c) { NEED(c); TO_ENGINE(c, rdsp_engine_setALSfilterPeak(c->engine)); c->saved_als_mode = RDSP_ALS_PEAK; if (c->cfg.als_mode != RDSP_ALS_OFF) c->cfg.als_mode = RDSP_ALS_PEAK; return RDSP_OK; }
@@ -1629,12 +1762,15 @@ struct StateHeader {
   int32_t fir_fd;        /* stage A3 of the saving chain: 0 direct, 1 frequency domain with 448-sample frames, 2 with
                             granule frames (informative: all keep the same 256 raw samples, so a stream may be
                             continued in any of them) */
+  int32_t has_eng_tail;  /* the engine-law tail state travels (allocated by a switch to RDSP_TAIL_ENGINE); this word
+                            sits in what was the header's tail padding, zero in every blob of a chain without it */
 };
+static_assert(sizeof(StateHeader) == 96, "the blob header of chains without the engine-law state keeps its size");
 constexpr uint32_t kStateVersion = 4;
 constexpr uint32_t kStateMagic = 0x50534452u; /* 'R' 'D' 'S' 'P' */
 struct StatePart { void *dev; size_t per_channel; };
 /* the per-channel arrays in blob order; optional ones (SAM, IIR, slip carry) only when present */
-std::vector<StatePart> state_parts(const rdsp_chain_t *c, bool sam, bool iir, bool slip = false) {
+std::vector<StatePart> state_parts(const rdsp_chain_t *c, bool sam, bool iir, bool slip = false, bool eng = false) {
   std::vector<StatePart> v = {
       {c->d_hist, sizeof(uint32_t) * 256},
       {c->d_prev, sizeof(float2) * (size_t)(c->N / 2)},
@@ -1646,11 +1782,15 @@ std::vector<StatePart> state_parts(const rdsp_chain_t *c, bool sam, bool iir, bo
   if (sam) v.push_back({c->d_sam, sizeof(float) * 4});
   if (iir) v.push_back({c->d_iir_state, sizeof(float) * 16});
   if (slip) v.push_back({c->d_slip_carry[c->slip_phase], sizeof(uint32_t)});
+  if (eng) {
+    v.push_back({c->d_eng_st, sizeof(float) * RDSP_ENG_ST_WORDS});
+    v.push_back({c->d_eng_als, sizeof(float) * RDSP_ENG_ALS_WORDS});
+  }
   return v;
 }
-size_t state_bytes(const rdsp_chain_t *c, int n, bool sam, bool iir, bool slip, size_t n_groups) {
+size_t state_bytes(const rdsp_chain_t *c, int n, bool sam, bool iir, bool slip, size_t n_groups, bool eng) {
   size_t b = sizeof(StateHeader) + 2 * sizeof(uint32_t) * n_groups;
-  for (const auto &p : state_parts(c, sam, iir, slip)) b += p.per_channel * (size_t)n;
+  for (const auto &p : state_parts(c, sam, iir, slip, eng)) b += p.per_channel * (size_t)n;
   return b;
 }
 }  // namespace
@@ -1660,7 +1800,8 @@ extern "C" size_t rdsp_chain_state_bytes(const rdsp_chain_t *c, int n_channels) 
   /* an upper bound that only set-up calls change: optional parts count once their buffers exist (the slip
    * carry travels only when the last call ran corrected, but its place is reserved as soon as
    * rdsp_pre_setIQslip has allocated it), so a buffer sized after set-up fits every later save */
-  return state_bytes(c, n_channels, c->d_sam != nullptr, c->d_iir_state != nullptr, c->d_slip_buf != nullptr, c->groups.size());
+  return state_bytes(c, n_channels, c->d_sam != nullptr, c->d_iir_state != nullptr, c->d_slip_buf != nullptr, c->groups.size(),
+                     c->d_eng_st != nullptr);
 }
 
 /* everything queued so far has finished when the copy is taken (a control-path call) */
@@ -1683,6 +1824,7 @@ extern "C" int rdsp_chain_save_state(rdsp_chain_t *c, int first_channel, int n_c
   h.fir_fd = fir_fd_of(c); /* decim 1: no decimator */
   h.n_channels = n_channels; h.fft_l = c->N; h.decim = c->decim;
   h.has_sam = c->d_sam != nullptr; h.has_iir = c->d_iir_state != nullptr;
+  h.has_eng_tail = c->d_eng_st != nullptr;
   h.old_nr_level = c->old_nr_level; h.n_in = c->n_in;
   h.nr_calls = c->nr_calls; h.als_calls = c->als_calls;
   h.nr_mu = c->nr_mu; h.als_mu = c->als_mu;
@@ -1697,7 +1839,7 @@ extern "C" int rdsp_chain_save_state(rdsp_chain_t *c, int first_channel, int n_c
     memcpy(dst, w, sizeof(w));
     dst += sizeof(w);
   }
-  for (const auto &p : state_parts(c, h.has_sam, h.has_iir, h.has_slip)) {
+  for (const auto &p : state_parts(c, h.has_sam, h.has_iir, h.has_slip, h.has_eng_tail)) {
     const size_t n = p.per_channel * (size_t)n_channels;
     HIP_TRY(hipMemcpy(dst, (const unsigned char *)p.dev + p.per_channel * (size_t)first_channel, n, hipMemcpyDeviceToHost));
     dst += n;
@@ -1735,8 +1877,13 @@ extern "C" int rdsp_chain_load_state(rdsp_chain_t *c, int first_channel, const v
     rdsp_set_error("rdsp_chain_load_state: the blob was taken with the I2S slip correction on; call rdsp_pre_setIQslip first");
     return RDSP_ERR_INVALID;
   }
+  if (h.has_eng_tail && !c->d_eng_st) {
+    rdsp_set_error("rdsp_chain_load_state: the blob carries the engine-law tail state; select the law first "
+                   "(rdsp_chain_set_tail_law(chain, RDSP_TAIL_ENGINE))");
+    return RDSP_ERR_INVALID;
+  }
   if (h.has_sam && ensure_sam(c) != RDSP_OK) return RDSP_ERR_HIP;
-  if (bytes < state_bytes(c, h.n_channels, h.has_sam != 0, h.has_iir != 0, h.has_slip != 0, (size_t)h.n_groups)) {
+  if (bytes < state_bytes(c, h.n_channels, h.has_sam != 0, h.has_iir != 0, h.has_slip != 0, (size_t)h.n_groups, h.has_eng_tail != 0)) {
     rdsp_set_error("rdsp_chain_load_state: blob truncated");
     return RDSP_ERR_INVALID;
   }
@@ -1766,7 +1913,7 @@ extern "C" int rdsp_chain_load_state(rdsp_chain_t *c, int first_channel, const v
   if (c->s_tail) HIP_TRY(hipStreamSynchronize(c->s_tail));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   const unsigned char *src = gsrc + 2 * sizeof(uint32_t) * (size_t)h.n_groups;
-  for (const auto &p : state_parts(c, h.has_sam != 0, h.has_iir != 0, h.has_slip != 0)) {
+  for (const auto &p : state_parts(c, h.has_sam != 0, h.has_iir != 0, h.has_slip != 0, h.has_eng_tail != 0)) {
     const size_t n = p.per_channel * (size_t)h.n_channels;
     HIP_TRY(hipMemcpy((unsigned char *)p.dev + p.per_channel * (size_t)first_channel, src, n, hipMemcpyHostToDevice));
     src += n;
@@ -1775,6 +1922,10 @@ extern "C" int rdsp_chain_load_state(rdsp_chain_t *c, int first_channel, const v
   if (!h.has_sam && c->d_sam) HIP_TRY(hipMemset(c->d_sam + 4 * (size_t)first_channel, 0, sizeof(float) * 4 * (size_t)h.n_channels));
   if (!h.has_iir && c->d_iir_state)
     HIP_TRY(hipMemset(c->d_iir_state + 16 * (size_t)first_channel, 0, sizeof(float) * 16 * (size_t)h.n_channels));
+  if (!h.has_eng_tail && c->d_eng_st) {
+    int rc = eng_tail_boot(c, first_channel, h.n_channels);
+    if (rc != RDSP_OK) return rc;
+  }
   if (fresh) {
     c->n_in = h.n_in;
     c->old_nr_level = h.old_nr_level;
@@ -1803,6 +1954,11 @@ extern "C" int rdsp_chain_get_scalars(rdsp_chain_t *c, float *host_out, void *st
   if (c->s_tail) HIP_TRY(hipStreamSynchronize(c->s_tail));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   HIP_TRY(hipMemcpy(host_out, c->d_scal, sizeof(float) * 4 * (size_t)c->n_channels, hipMemcpyDeviceToHost));
+  if (c->tail_law == RDSP_TAIL_ENGINE) { /* slot 1: the engine AGC's gain */
+    std::vector<float> st((size_t)RDSP_ENG_ST_WORDS * (size_t)c->n_channels);
+    HIP_TRY(hipMemcpy(st.data(), c->d_eng_st, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int i = 0; i < c->n_channels; i++) host_out[4 * (size_t)i + 1] = st[(size_t)RDSP_ENG_ST_WORDS * i + 1];
+  }
   return RDSP_OK;
 }
 /* A channel whose NLMS instance has run away (rdsp_chain_get_status) stays dead: arm_lms_norm_init_f32
@@ -1841,7 +1997,8 @@ extern "C" int rdsp_chain_get_status(rdsp_chain_t *c, uint32_t *host_out, void *
   const size_t nch = (size_t)c->n_channels;
   std::vector<uint32_t> w(2 * nch);
   HIP_TRY(hipMemcpy(w.data(), c->d_status, sizeof(uint32_t) * 2 * nch, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < nch; i++) host_out[i] = (w[i] & 3u) | ((w[nch + i] & 3u) << 4);
+  const uint32_t als_bits = c->tail_law == RDSP_TAIL_ENGINE ? 0u : 3u; /* the engine's ALS filter has no health words */
+  for (size_t i = 0; i < nch; i++) host_out[i] = (w[i] & 3u) | ((w[nch + i] & als_bits) << 4);
   return RDSP_OK;
 }
 extern "C" int rdsp_chain_get_lms_coeffs(rdsp_chain_t *c, int which, float *host_out, void *stream) {
@@ -1878,6 +2035,10 @@ extern "C" int rdsp_sdr_set_engine_literal(rdsp_chain_t *c, int on) {
     return RDSP_OK;
   }
   if (c->engine) return RDSP_OK;
+  if (c->tail_law == RDSP_TAIL_ENGINE) {
+    rdsp_set_error("rdsp_sdr_set_engine_literal: the chain runs the engine-law tail (rdsp_chain_set_tail_law); switch it back first");
+    return RDSP_ERR_UNSUPPORTED;
+  }
   const rdsp_chain_config_t &cf = c->cfg;
   if (c->decim != 1 || cf.fs_in != 44100.0 || cf.demod != RDSP_DEMOD_IQ || cf.nco_hz != 0.0 || cf.agc_mode != RDSP_AGC_OFF ||
       cf.als_mode != RDSP_ALS_OFF || cf.spectral_nr != 0 || cf.input_gain != 1.0f || cf.output_gain != 1.0f || cf.iq_balance != 1.0f ||

@@ -47,6 +47,7 @@
 
 #include <vector>
 
+#include "rdsp_engine_agc.h"
 #include "rdsp_host.h"
 #include "rdsp_sync.h"
 
@@ -82,11 +83,6 @@ struct EngParams {
   float sam_keep, sam_new, sam_hz_per_rad, sam_lock_lo, sam_lock_hi, sam_ga, sam_gb;
 };
 
-__device__ __forceinline__ int trunc_s32(double x) { /* VCVT.S32.F64: toward zero, saturating, NaN -> 0 -- which is what v_cvt_i32_f64 does too */
-  int r;
-  asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
 
 /* the oscillator: sin of a phase in [0, 2 pi) by linear interpolation in the 256-step table, through double as the image does */
 /* trunc(RN(a / d)) for a >= 0 and d = the double of the image's 2 pi, without the division: k d is exact for k < 2^16 (a
@@ -545,14 +541,6 @@ __global__ __launch_bounds__(256) void rdsp_engine_hilbert_kernel(const EngParam
 }
 
 /* ---- tail: audio band-pass (0xd944), AGC (0xdb58), ALS (0xda24), output (0xebfa) ------------------------------------- */
-__device__ __forceinline__ float agc_lookup(const float *curve, float env) {
-  const int idx = trunc_s32((double)env * 32767.0);
-  int hi = (idx >> 8) & 0xff, hi1;
-  if (hi > 127) { hi = 127; hi1 = 128; } else hi1 = hi + 1;
-  const float frac = (float)(unsigned)(idx & 0xff) * 0.00390625f;
-  const float t0 = curve[hi];
-  return fmaf(frac, curve[hi1] - t0, t0);
-}
 
 /* 8 channels (16 with the ALS filter) per workgroup of four waves.  Per block: the audio cascade with a quad per channel (wave 0); the AGC's
  * envelope -- the only true recursion in it -- on one lane per channel (wave 1), which leaves for every sample the
@@ -778,36 +766,9 @@ __global__ __launch_bounds__(PW, 2) void rdsp_engine_tail_pipe_kernel(const EngP
   }
 }
 
-/* ---- host side ---------------------------------------------------------------------------------------------------- */
-float bits_f(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
-uint32_t f_bits(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
-
-/* expf of the C library the engine was linked against (newlib's e_expf.c, Sun's algorithm): the gain curve below is built
- * with it, and a different last bit in one of its 129 entries would be a different gain on every sample that uses it */
-float engine_expf(float x) {
-  const float ln2_hi = 6.9313812256e-01f, ln2_lo = 9.0580006145e-06f, inv_ln2 = 1.4426950216e+00f;
-  const float P[5] = {1.6666667163e-01f, -2.7777778450e-03f, 6.6137559770e-05f, -1.6533901999e-06f, 4.1381369442e-08f};
-  const uint32_t hx = f_bits(x) & 0x7fffffffu;
-  const int neg = (int)(f_bits(x) >> 31);
-  if (hx > 0x7f800000u) return x + x;
-  if (hx == 0x7f800000u) return neg ? 0.0f : x;
-  if (x > 8.8721679688e+01f) return INFINITY;
-  if (x < -1.0397208405e+02f) return 0.0f;
-  float hi = 0.0f, lo = 0.0f;
-  int k = 0;
-  if (hx > 0x3eb17218u) {
-    if (hx < 0x3F851592u) { hi = neg ? x + ln2_hi : x - ln2_hi; lo = neg ? -ln2_lo : ln2_lo; k = neg ? -1 : 1; }
-    else { k = (int)(inv_ln2 * x + (neg ? -0.5f : 0.5f)); const float t = (float)k; hi = x - t * ln2_hi; lo = t * ln2_lo; }
-    x = hi - lo;
-  } else if (hx < 0x31800000u) return 1.0f + x;
-  const float t = x * x;
-  const float c = x - t * (P[0] + t * (P[1] + t * (P[2] + t * (P[3] + t * P[4]))));
-  if (k == 0) return 1.0f - ((x * c) / (c - 2.0f) - x);
-  const float y = 1.0f - ((lo - (x * c) / (2.0f - c)) - hi);
-  if (k >= -125) return bits_f(f_bits(y) + ((uint32_t)k << 23));
-  return bits_f(f_bits(y) + ((uint32_t)(k + 100) << 23)) * 7.8886090522e-31f;
-}
 }  // namespace
+
+/* ---- host side ---------------------------------------------------------------------------------------------------- */
 
 /* what the sketch's calls set: one set per receiver group (one group = the whole object unless rdsp_engine_set_groups cut it) */
 struct EngSettings {
@@ -833,27 +794,6 @@ struct rdsp_engine {
 namespace {
 constexpr size_t TAB_SETS = 0, TAB_HILBERT = 300, TAB_SINE = 364, TAB_CURVE = 621, TAB_WORDS = 751;
 
-void engine_agc_curve(rdsp_engine_t *e) { /* 0xdd40: soft-knee compressor curve over the envelope, 1/128 per entry */
-  const double ln10ish = 2.3025, db_per_octave = 6.026; /* the library's own constants */
-  const double T = (double)e->agc_threshold_db, W = (double)e->agc_knee_db;
-  const float x_lo = engine_expf((float)(((T - W * 0.5) * ln10ish) / 20.0)), x_hi = engine_expf((float)(((T + W * 0.5) * ln10ish) / 20.0));
-  for (int i = 0; i < 130; i++) {
-    const float x = (float)i * 0.0078125f;
-    if (x_lo > x) { e->curve[i] = 1.0f; continue; }
-    int ex;
-    const float m = frexpf(x, &ex);
-    const float log2x = fmaf(m, fmaf(m, fmaf(m, 1.2314958572387695f, -4.1185250282287598f), 6.021970272064209f), -3.1339645385742188f) + (float)ex;
-    const float xdb = (float)((double)log2x * db_per_octave);
-    float gdb;
-    if (x_hi >= x) {
-      const double d = fma(W, 0.5, (double)(xdb - e->agc_threshold_db));
-      gdb = (float)(((((double)e->agc_slope - 1.0) * d) * d) / (W + W) + (double)xdb) - xdb;
-    } else {
-      gdb = fmaf(xdb - e->agc_threshold_db, e->agc_slope, e->agc_threshold_db) - xdb;
-    }
-    e->curve[i] = engine_expf((float)(((double)gdb * ln10ish) / 20.0));
-  }
-}
 void engine_sam_constants(rdsp_engine_t *e) { /* 0xed34 with the constructor's loop parameters */
   const float wn = bits_f(0x3e50fac7), zeta = 2.0f, kd = 1.0f, ko = 1.0f;
   const double k4 = (double)(1.0f / (kd * ko)) * 4.0, den = 1.0 / ((double)zeta * 4.0) + (double)zeta;
@@ -874,14 +814,12 @@ int for_selected(rdsp_engine_t *e, F f) {
   return RDSP_OK;
 }
 void settings_agc_mode(EngSettings &s, int mode) { /* 0xdfe0 */
-  static const uint32_t k[4][4] = {{0, 0, 0, 0}, {0x3f79673b, 0x3cd318a0, 0x3f7fddca, 0x3a08d800}, {0x3f7d5732, 0x3c2a3380, 0x3f7ff250, 0x395b0000},
-                                   {0x3f7eaab6, 0x3baaa500, 0x3f7ff928, 0x38db0000}};
-  static const int hang[4] = {0, 4410, 22050, 88200};
   if (mode == 0) { s.agc_on = 0; return; }
   if (mode < 0 || mode > 3) return; /* the engine ignores other values */
-  s.agc_attack_a = bits_f(k[mode][0]); s.agc_attack_b = bits_f(k[mode][1]);
-  s.agc_decay_a = bits_f(k[mode][2]); s.agc_decay_b = bits_f(k[mode][3]);
-  s.agc_hang_time = hang[mode];
+  const EngineAgcSet k = engine_agc_set(mode);
+  s.agc_attack_a = k.attack_a; s.agc_attack_b = k.attack_b;
+  s.agc_decay_a = k.decay_a; s.agc_decay_b = k.decay_b;
+  s.agc_hang_time = k.hang_time;
   s.agc_on = 1;
 }
 void settings_demod(const rdsp_engine_t *e, EngSettings &s, int mode) { /* 0xd798 */
@@ -903,7 +841,7 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.input_gain = s.gain_i = s.gain_q = s.iq_balance = s.output_gain = 1.0f;
   s.audio_set = 3; s.nb_on = 1; s.als_notch = 1; s.als_adaptive = 1;
   settings_agc_mode(s, 2); /* 0xdf14: the medium attack with the slow decay and the fast hang time */
-  s.agc_decay_a = bits_f(0x3f7ff928); s.agc_decay_b = bits_f(0x38db0000); s.agc_hang_time = 4410;
+  { const EngineAgcSet k = engine_agc_set(0); s.agc_decay_a = k.decay_a; s.agc_decay_b = k.decay_b; s.agc_hang_time = k.hang_time; }
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -1032,8 +970,9 @@ int rdsp_engine_create(int n_channels, int device, int max_blocks_per_call, rdsp
   e->tables = false;
   /* the constructor's values */
   e->if_centre = 6890.0f; e->ssb_band = 3000.0f; e->cw_band = 1000.0f;
-  e->agc_makeup = 10.0f; e->agc_threshold_db = -60.0f; e->agc_slope = bits_f(0x3dcccccd); e->agc_knee_db = 2.0f;
-  engine_agc_curve(e);
+  e->agc_makeup = ENGINE_AGC_MAKEUP; e->agc_threshold_db = ENGINE_AGC_THRESHOLD_DB; e->agc_slope = bits_f(ENGINE_AGC_SLOPE_BITS);
+  e->agc_knee_db = ENGINE_AGC_KNEE_DB;
+  engine_agc_curve(e->agc_threshold_db, e->agc_knee_db, e->agc_slope, e->curve);
   engine_sam_constants(e);
   for (int k = 0; k < 257; k++) e->sine[k] = (float)(round(sin(2.0 * 3.14159265358979323846 * k / 256.0) * 1e8) / 1e8);
   e->grp.assign(1, settings_as_constructed(e));

@@ -139,6 +139,34 @@ struct RdspTailParams {
   size_t st_status_stride;
 };
 
+/* the engine-law tail stage (rdsp_tail_engine.hip): AudioSDR's hang AGC (0xdb58) then its ALS line enhancer (0xda24),
+ * bit for bit, on the chain's float audio; 16 channels per one-wave workgroup */
+#define RDSP_ENG_ALS_HIST 64  /* ALS input kept from one call to the next (the 55 taps reach 57 samples back) */
+#define RDSP_ENG_ALS_TAPS 55
+#define RDSP_ENG_ALS_WORDS (RDSP_ENG_ALS_HIST + 64) /* per channel: the line's newest 64 samples, oldest first, then the taps */
+#define RDSP_ENG_ST_WORDS 4  /* per channel: envelope, gain, hang counter (int), active flag (int) */
+struct RdspTailEngineParams {
+  const float *in;         /* [ch][in_stride] audio in                                   */
+  size_t in_stride;
+  float *raw_out;          /* non-null: the stage's floats go here ([ch][in_stride], in place allowed), no gain / pack */
+  uint32_t *out_i16;       /* otherwise x out_gain, packed L = R; out_f32 may be null     */
+  float2 *out_f32;
+  size_t out_stride;
+  float out_gain;
+  int n_channels;          /* one past the last channel of this launch                    */
+  int ch_base;             /* first channel of this launch                                */
+  int n_blocks;
+  float *st;               /* [ch][RDSP_ENG_ST_WORDS]                                     */
+  float *als;              /* [ch][RDSP_ENG_ALS_WORDS]                                    */
+  int agc_on, als_on;
+  int als_notch;           /* 1: the error goes out (notch), 0: the prediction (peak)     */
+  int als_clear;           /* 1: line and taps start from zero (enableALSfilter, 0xdb2c)  */
+  int prio;
+  float agc_attack_a, agc_attack_b, agc_decay_a, agc_decay_b, agc_makeup;
+  int agc_hang_time;
+  float curve[130];        /* the AGC's gain curve (0xdd40)                               */
+};
+
 /* biquad cascades (rdsp_biquad.hip): four DF1 stages per channel, one stage per lane of a quad.
  * Float mode: `buf` [ch][stride] in place (the chain's mono intermediate).  int16 mode (in16 /
  * out16 non-null): samples taken / written every step16 / ostep16 int16 of [ch][stride16] rows. */
@@ -173,6 +201,8 @@ int rdsp_launch_front(int fft_l, int decim, const RdspFrontParams *p, int n_chan
                       hipStream_t stream);
 int rdsp_launch_tail(const RdspTailParams *p, int lanes_per_channel, hipStream_t stream);
 int rdsp_launch_sam(const RdspSamParams *p, hipStream_t stream);
+int rdsp_launch_tail_engine(const RdspTailEngineParams *p, hipStream_t stream);
+void rdsp_tail_engine_constants(RdspTailEngineParams *p, int agc_set);
 int rdsp_launch_group_store(RdspGroup *dst, const RdspGroup *val, hipStream_t stream);
 int rdsp_launch_iq_slip(const uint32_t *in, size_t in_stride, uint32_t *out, size_t out_stride, const uint32_t *carry_in,
                         size_t carry_stride, uint32_t *carry_out, int n_samples, int slip, int n_channels, hipStream_t stream);
