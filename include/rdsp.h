@@ -120,7 +120,9 @@ int rdsp_chain_call_unit_blocks(const rdsp_chain_t *c);
  * accepted in that form; such a call ends in a partial frame and re-anchors the grid at the next call's first
  * sample (valid output, rounds differently: <= 3e-7 of the peak). */
 int rdsp_chain_granule_blocks(const rdsp_chain_t *c);
-/* zero all per-channel state (overlap block, FIR history, NLMS, NFloor, AGC) */
+/* zero all per-channel state (overlap block, FIR history, NLMS, NFloor, AGC); settings kept.  An engine-literal chain
+ * (rdsp_sdr_set_engine_literal) also resets its pre-processor (rdsp_preproc_reset: detection off until
+ * rdsp_pre_startAutoI2SerrorDetection is called again, a one-shot command) and its engine (rdsp_engine_reset). */
 int rdsp_chain_reset(rdsp_chain_t *c, void *stream);
 
 /* doConvolutionalInitialize(), CONV:187 */
@@ -229,7 +231,8 @@ int rdsp_pre_startAutoI2SerrorDetection(rdsp_chain_t *c);         /* INO:117: ac
  * its own in front of the front kernel (8 bytes of HBM traffic per input sample while it is on), before
  * swapIQ and the input gains, on samples as they arrive from the next call on.  The first non-zero
  * value allocates the corrected-input buffer (n_channels x max_blocks_per_call x 128 words): a set-up
- * call.  Build-defined (the AudioSDR pre-processor is not in the reference tree). */
+ * call.  Build-defined (the AudioSDR pre-processor is not in the reference tree).  A non-zero slip on an
+ * engine-literal chain is refused (RDSP_ERR_UNSUPPORTED): its pre-processor repairs the slip itself. */
 int rdsp_pre_setIQslip(rdsp_chain_t *c, int slip);
 /* iq: n_samples interleaved int16 I,Q pairs of ONE channel (host memory).  *slip: the value to pass to
  * rdsp_pre_setIQslip; rejection_db (optional, 3 values): image rejection of the strongest line with the
@@ -412,7 +415,9 @@ int rdsp_chain_get_fir_taps(rdsp_chain_t *c, float *host_out);
  * rdsp_chain_state_bytes is an upper bound for every later rdsp_chain_save_state of that many channels; it
  * grows only with set-up calls that allocate optional state (a SAM group, RDSP_AUDIO_KIND_IIR, the first
  * non-zero rdsp_pre_setIQslip, rdsp_chain_set_groups): size the buffer after set-up.  Blobs carry a
- * version (4 in this library); a blob of another version is refused (RDSP_ERR_INVALID), nothing is restored. */
+ * version (4 in this library); a blob of another version is refused (RDSP_ERR_INVALID), nothing is restored.
+ * An engine-literal chain refuses both (RDSP_ERR_UNSUPPORTED): the blob does not carry the pre-processor's and the
+ * engine's state; use rdsp_engine_save_state / load_state on rdsp_chain_engine(chain) for the engine. */
 size_t rdsp_chain_state_bytes(const rdsp_chain_t *c, int n_channels);
 int rdsp_chain_save_state(rdsp_chain_t *c, int first_channel, int n_channels, void *host_buf, size_t bytes, void *stream);
 int rdsp_chain_load_state(rdsp_chain_t *c, int first_channel, const void *host_buf, size_t bytes, void *stream);
@@ -716,8 +721,15 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).
  * The setters above address the group chosen with rdsp_engine_select_group (-1, the default: every group);
- * rdsp_engine_setDemodMode returns the offset of the selected group (of group 0 for -1).  A channel's signal state does
- * not care which group it is in: regrouping in mid-stream only changes which settings reach it. */
+ * rdsp_engine_setDemodMode returns the offset of the selected group (of group 0 for -1).  Regrouping in mid-stream:
+ * - a new group's settings are copied from the old group its first channel was in;
+ * - signal state stays with the channel (filters, oscillator, AGC, side-band lines, blanker, ALS): a channel continues as
+ *   it would have in its old group with the new group's settings from the next update on;
+ * - pending resets (setDemodMode / setAudioFilter / enableALSfilter made since the last update) are settings too: a new
+ *   group whose channels come from old groups with different pending resets is refused (RDSP_ERR_UNSUPPORTED, "call
+ *   rdsp_engine_update first") and nothing changes;
+ * - the call takes no stream: before it moves a channel's side-band lines it waits for everything queued on the engine's
+ *   device, and the lines have moved when it returns. */
 int rdsp_engine_set_groups(rdsp_engine_t *e, int n_groups, const int *first_channel);
 int rdsp_engine_groups(const rdsp_engine_t *e);
 int rdsp_engine_select_group(rdsp_engine_t *e, int group);
@@ -745,6 +757,7 @@ int rdsp_preproc_create(int n_channels, int device, rdsp_preproc_t **out);
 void rdsp_preproc_destroy(rdsp_preproc_t *p);
 int rdsp_preproc_startAutoI2SerrorDetection(rdsp_preproc_t *p); /* INO:117; takes effect at the next update */
 int rdsp_preproc_swapIQ(rdsp_preproc_t *p, int on);             /* INO:118 */
+int rdsp_preproc_reset(rdsp_preproc_t *p, void *stream); /* state as constructed (not detecting); swapIQ kept, a pending start dropped */
 int rdsp_preproc_update(rdsp_preproc_t *p, const int16_t *d_iq, size_t in_stride, int n_blocks, int16_t *d_out,
                         size_t out_stride, void *stream);      /* [ch][t] int16 pairs (I, Q) in and out; in place allowed */
 int rdsp_preproc_get_state(rdsp_preproc_t *p, int16_t *host_out, void *stream); /* [ch][4]: remedy (0, 1 = I later, -1 = Q later), bad count, counted blocks, detecting */
@@ -761,7 +774,11 @@ int rdsp_engine_node_status(rdsp_node_t *n); /* either kind */
  * pre-processor and engine in front of it.  rdsp_chain_process then is INO:71-86 + :198 (preProcessor -> SDR ->
  * doConvolutionalProcessing), rdsp_sdr_node_create wires exactly that into the graph, and the rdsp_sdr_* / rdsp_pre_*
  * setters above reach rdsp_engine_t / rdsp_preproc_t (the image's arithmetic) instead of this build's stand-ins; mode and
- * filter arguments stay rdsp_demod_t / rdsp_audio_filter_t and are translated to the engine's numbers. */
+ * filter arguments stay rdsp_demod_t / rdsp_audio_filter_t and are translated to the engine's numbers.  Switching on is
+ * refused (RDSP_ERR_UNSUPPORTED) while the chain's own stand-ins are on -- rdsp_sdr_enableNoiseBlanker, rdsp_pre_swapIQ(1),
+ * a non-zero rdsp_pre_setIQslip -- since those setters reach the engine's objects afterwards and could not turn them off:
+ * turn them off first, make the calls again after the switch.  rdsp_chain_reset resets both objects;
+ * rdsp_chain_save_state / load_state are refused (see there). */
 int rdsp_sdr_set_engine_literal(rdsp_chain_t *c, int on);
 int rdsp_sdr_load_engine_tables(rdsp_chain_t *c, const float *biquad_sets15x20, const float *hilbert64);
 rdsp_engine_t *rdsp_chain_engine(rdsp_chain_t *c);   /* the objects themselves (NULL unless engine-literal) */

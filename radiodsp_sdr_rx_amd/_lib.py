@@ -298,6 +298,7 @@ SYMBOLS = [
     ("rdsp_preproc_destroy", None, [_vp]),
     ("rdsp_preproc_startAutoI2SerrorDetection", _i, [_vp]),
     ("rdsp_preproc_swapIQ", _i, [_vp, _i]),
+    ("rdsp_preproc_reset", _i, [_vp, _vp]),
     ("rdsp_preproc_update", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     ("rdsp_preproc_get_state", _i, [_vp, _i16p, _vp]),
     ("rdsp_preproc_channels", _i, [_vp]),

@@ -605,6 +605,11 @@ extern "C" int rdsp_chain_reset(rdsp_chain_t *c, void *stream_) {
     int rc = eng_tail_boot(c, 0, c->n_channels);
     if (rc != RDSP_OK) return rc;
   }
+  if (c->engine) { /* engine-literal: the pre-processor and the engine in front are part of the chain's signal state */
+    int rc = rdsp_preproc_reset(c->pre, stream);
+    if (rc == RDSP_OK) rc = rdsp_engine_reset(c->engine, stream);
+    if (rc != RDSP_OK) return rc;
+  }
   return RDSP_OK;
 }
 
@@ -1221,6 +1226,11 @@ extern "C" int rdsp_pre_startAutoI2SerrorDetection(rdsp_chain_t *c) { NEED(c); T
 extern "C" int rdsp_pre_setIQslip(rdsp_chain_t *c, int slip) {
   NEED(c);
   if (slip < -1 || slip > 1) return RDSP_ERR_INVALID;
+  if (slip != 0 && c->engine) {
+    rdsp_set_error("rdsp_pre_setIQslip: the chain is engine-literal; its pre-processor finds and repairs the slip itself "
+                   "(rdsp_pre_startAutoI2SerrorDetection)");
+    return RDSP_ERR_UNSUPPORTED;
+  }
   if (slip != 0 && !c->d_slip_buf) {
     if (check_device(c) != RDSP_OK) return RDSP_ERR_HIP;
     const size_t nch = (size_t)c->n_channels;
@@ -1814,6 +1824,11 @@ extern "C" int rdsp_chain_save_state(rdsp_chain_t *c, int first_channel, int n_c
                    first_channel + n_channels, c->n_channels, bytes, rdsp_chain_state_bytes(c, n_channels));
     return RDSP_ERR_INVALID;
   }
+  if (c->engine) {
+    rdsp_set_error("rdsp_chain_save_state: the chain is engine-literal and the blob does not carry the pre-processor's and "
+                   "the engine's state; save those with rdsp_engine_save_state on rdsp_chain_engine(chain)");
+    return RDSP_ERR_UNSUPPORTED;
+  }
   if (check_device(c) != RDSP_OK) return RDSP_ERR_HIP;
   if (c->s_tail) HIP_TRY(hipStreamSynchronize(c->s_tail));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -1858,6 +1873,11 @@ extern "C" int rdsp_chain_load_state(rdsp_chain_t *c, int first_channel, const v
     return RDSP_ERR_INVALID;
   }
   memcpy(&h, host_buf, sizeof(h));
+  if (c->engine) {
+    rdsp_set_error("rdsp_chain_load_state: the chain is engine-literal and a chain blob does not carry the pre-processor's "
+                   "and the engine's state; move those with rdsp_engine_save_state / load_state on rdsp_chain_engine(chain)");
+    return RDSP_ERR_UNSUPPORTED;
+  }
   if (h.magic != kStateMagic || h.version != kStateVersion || h.fft_l != c->N || h.decim != c->decim || h.n_channels <= 0 ||
       h.n_groups < 1 || first_channel < 0 || first_channel + h.n_channels > c->n_channels) {
     rdsp_set_error("rdsp_chain_load_state: blob (version %u) of %d channels, FFT_L %d, decimation %d does not fit channels %d.. "
@@ -2035,6 +2055,12 @@ extern "C" int rdsp_sdr_set_engine_literal(rdsp_chain_t *c, int on) {
     return RDSP_OK;
   }
   if (c->engine) return RDSP_OK;
+  if (c->nb_on || c->swap_iq || c->iq_slip) { /* after the switch these setters reach the engine's objects: nothing could turn the stand-ins off */
+    rdsp_set_error("rdsp_sdr_set_engine_literal: the chain's own noise blanker (%d), swapIQ (%d) or I2S slip correction (%d) is "
+                   "on; turn it off first (rdsp_sdr_disableNoiseBlanker, rdsp_pre_swapIQ(0), rdsp_pre_setIQslip(0)) and make "
+                   "those calls again after the switch", c->nb_on, c->swap_iq, c->iq_slip);
+    return RDSP_ERR_UNSUPPORTED;
+  }
   if (c->tail_law == RDSP_TAIL_ENGINE) {
     rdsp_set_error("rdsp_sdr_set_engine_literal: the chain runs the engine-law tail (rdsp_chain_set_tail_law); switch it back first");
     return RDSP_ERR_UNSUPPORTED;

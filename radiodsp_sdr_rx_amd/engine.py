@@ -125,6 +125,10 @@ class PreProcessor:
     def swapIQ(self, on):
         check(self.lib.rdsp_preproc_swapIQ(self.h, int(bool(on))))
 
+    def reset(self):
+        """state as constructed (not detecting until startAutoI2SerrorDetection); swapIQ kept"""
+        check(self.lib.rdsp_preproc_reset(self.h, None))
+
     def update(self, d_iq, out=None, stream=None):
         import torch
         nch, n, two = d_iq.shape

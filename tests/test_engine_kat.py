@@ -350,6 +350,18 @@ def test_gpu_engine_receiver_groups(kat, sessions, rdsp):
         eng.set_groups([0, 30])
     with pytest.raises(RdspError):
         eng.select_group(2)
+    # and the stream goes on: the channels whose settings the regrouping left as they were (lsb_sketch's, which keep
+    # group 0; session2's, whose group gives the new group 1 its settings) continue as their case would, 40 more blocks
+    import oracle_lib
+    more = 40
+    extra = np.stack([_drawn_session(900 + c, more)[0] for c in range(23)])
+    y = torch.cat([eng.update(torch.from_numpy(np.ascontiguousarray(extra[:, a * 128:(a + 8) * 128])).cuda()) for a in range(0, more, 8)], 1)
+    y = y[..., 0].cpu().numpy()
+    for c, n in ((0, "lsb_sketch"), (2, "lsb_sketch"), (12, "session2")):
+        whole = np.concatenate([x[c], extra[c]])
+        want = oracle_lib.OracleEngine().run(whole, [k for k in calls[n] if k[0] < nb])
+        assert np.array_equal(want[:nb * 128], fx[n][n + "_out"][:nb * 128])
+        assert np.array_equal(y[c], want[nb * 128:]), (n, c)
 
 
 @pytest.mark.gpu
@@ -383,3 +395,189 @@ def test_gpu_engine_state_as_data(kat, rdsp, name):
         b.load_state(0, np.zeros(64, np.uint8))                      # not a blob
     with pytest.raises(RdspError):
         b.load_state(6, blob)                                        # no such channel
+
+
+# ---- regrouping in mid-stream -------------------------------------------------------------------------------------------
+# Engine channels are independent, so a channel of a regrouped object is held to the restatement run on that channel's own
+# history of setter calls: its old group's calls up to the regrouping, then those of the group it joined.
+class _Groups:
+    """an engine whose channels sit in receiver groups, driven on a non-default stream (nothing is read back until the
+    end); `calls[c]` records every setter call that reached channel c, as OracleEngine.run takes them"""
+
+    def __init__(self, eng, firsts, x):
+        import torch
+        self.eng, self.n, self.x = eng, eng.n_channels, x
+        self.calls = [[] for _ in range(self.n)]
+        self.stream = torch.cuda.Stream()
+        with torch.cuda.stream(self.stream):
+            self.d = torch.from_numpy(x).cuda()
+        self.outs = []
+        self.set_groups(firsts)
+
+    def set_groups(self, firsts):
+        self.eng.set_groups(firsts)
+        self.firsts = list(firsts)
+
+    def call(self, block, group, name, *args):
+        self.eng.select_group(group)
+        getattr(self.eng, name)(*args)
+        ends = self.firsts[1:] + [self.n]
+        lo, hi = (0, self.n) if group < 0 else (self.firsts[group], ends[group])
+        for c in range(lo, hi):
+            self.calls[c].append([block, name] + list(args))
+
+    def run(self, a, b, split):
+        """blocks a .. b - 1 in calls of at most `split` blocks"""
+        import torch
+        with torch.cuda.stream(self.stream):
+            for u in range(a, b, split):
+                v = min(b, u + split)
+                self.outs.append(self.eng.update(self.d[:, u * 128:v * 128].contiguous(), stream=self.stream.cuda_stream))
+
+    def play(self, a, b, split, common=()):
+        """blocks a .. b - 1 with the calls of `common` (block, name, args...: every group) at their blocks"""
+        marks = sorted({a, b} | {c[0] for c in common if a <= c[0] < b})
+        for u, v in zip(marks[:-1], marks[1:]):
+            for c in common:
+                if c[0] == u:
+                    self.call(u, -1, *c[1:])
+            self.run(u, v, split)
+
+    def result(self):
+        import torch
+        with torch.cuda.stream(self.stream):
+            y = torch.cat(self.outs, 1)[..., 0].cpu().numpy()
+        return y
+
+    def check(self, y, channels=None):
+        import oracle_lib
+        for c in (range(self.n) if channels is None else channels):
+            want = oracle_lib.OracleEngine().run(self.x[c, :y.shape[1]], self.calls[c])
+            assert np.array_equal(y[c], want), (c, int(np.argmax(y[c] != want)))
+
+
+def _common_calls(seed, start, n_blocks):
+    """a drawn series of the sketch's setter calls at blocks start + 4 ... (the first blocks after a regrouping run the
+    modes the groups were in)"""
+    return [c for c in _drawn_session(seed, n_blocks)[1] if c[0] >= start + 4]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_blocks", [8, 24])
+def test_gpu_engine_regroup_merges_a_lagging_group(rdsp, max_blocks):
+    """two groups (channels 0-6 and 7-18: neither aligned to a workgroup); group 1 runs AM for blocks 0-4 while group 0
+    stays in LSB, so group 1's side-band lines lag by 640 samples (not a multiple of the ring: 2048 at 8 blocks a call,
+    4096 at 24).  At block 11 both groups are merged and run 310 more blocks (longer than the 256-tap line) through a
+    drawn series of calls: every channel against the restatement of its own calls, bit for bit.  Then a channel of the
+    lagging group is saved, loaded into an object of another ring size and continues there to the end"""
+    import torch
+    nch, m, R, nb, S = 19, 5, 11, 321, 300
+    x = np.stack([_drawn_session(7000 + c, nb + 30)[0] for c in range(nch)])
+    common = _common_calls(7100, R, nb)
+    eng = _engine(rdsp, nch, max_blocks)
+    eng.sketch_setup()
+    G = _Groups(eng, [0, 7], x)
+    G.call(0, 1, "setDemodMode", 4)
+    G.run(0, m, max_blocks)
+    G.call(m, 1, "setDemodMode", 0)
+    G.run(m, R, max_blocks)
+    G.set_groups([0])                                               # the updates before it are queued, not read back
+    G.play(R, S, max_blocks, common)
+    G.stream.synchronize()
+    blob = eng.save_state(10, 1)                                    # a channel of the lagging group
+    G.play(S, nb, max_blocks, common)
+    y = G.result()
+    G.check(y)
+    # channel 10 continues in another object: other channel count, other ring size, another index
+    other = 32 if max_blocks == 8 else 4
+    b = _engine(rdsp, 5, other)
+    b.sketch_setup()
+    for c in G.calls[10]:
+        if c[0] < S:
+            getattr(b, c[1])(*c[2:])                                # the settings are not in the blob
+    b.update(torch.from_numpy(np.zeros((5, 128, 2), np.int16)).cuda())
+    b.load_state(3, blob)
+    rest = np.zeros((5, (nb + 30 - S) * 128, 2), np.int16)
+    rest[3] = x[10, S * 128:]
+    got = _run_product(b, rest, [[c[0] - S] + c[1:] for c in G.calls[10] if c[0] >= S], other)
+    import oracle_lib
+    want = oracle_lib.OracleEngine().run(x[10], G.calls[10])
+    assert np.array_equal(got[3], want[S * 128:])
+
+
+@pytest.mark.gpu
+def test_gpu_engine_regroup_split_then_merge(rdsp):
+    """one group split into three at block 3 (channels 0-4, 5-12, 13-20), driven through SSB, AM, SAM and CW with calls of
+    their own, brought back to the same settings at block 40 and merged at block 41; 320 more blocks of common calls"""
+    nch, nb = 21, 361
+    x = np.stack([_drawn_session(7300 + c, nb)[0] for c in range(nch)])
+    eng = _engine(rdsp, nch, 8)
+    eng.sketch_setup()
+    G = _Groups(eng, [0], x)
+    G.run(0, 3, 8)
+    G.set_groups([0, 5, 13])
+    own = {0: [(3, "setDemodMode", 1), (9, "setAudioFilter", 3), (17, "setOutputGain", 0.9), (25, "setDemodMode", 6)],
+           1: [(3, "setDemodMode", 4), (8, "setAGCmode", 1), (14, "setDemodMode", 5), (22, "setAudioFilter", 0), (30, "setDemodMode", 3)],
+           2: [(3, "setDemodMode", 2), (6, "enableNoiseBlanker"), (12, "setDemodMode", 5), (19, "setInputGain", 3.0), (27, "setDemodMode", 4)]}
+    back = [("setDemodMode", 0), ("setAudioFilter", 6), ("setAGCmode", 2), ("setOutputGain", 0.5), ("setInputGain", 1.0), ("disableNoiseBlanker",)]
+    marks = sorted({3, 40} | {c[0] for v in own.values() for c in v})
+    for u, v in zip(marks[:-1], marks[1:]):
+        for g, cs in own.items():
+            for c in cs:
+                if c[0] == u:
+                    G.call(u, g, *c[1:])
+        G.run(u, v, 8)
+    for g in range(3):
+        for c in back:
+            G.call(40, g, *c)
+    G.run(40, 41, 8)
+    G.set_groups([0])
+    G.play(41, nb, 8, _common_calls(7400, 41, nb))
+    G.check(G.result())
+
+
+@pytest.mark.gpu
+def test_gpu_engine_regroup_with_a_reset_pending(rdsp):
+    """a group that called setAudioFilter in the block of the regrouping (a reset of its audio filter pending) cannot
+    join a group without one: set_groups refuses with a message and changes nothing; after the update it may.  Merged
+    groups with the same pending resets keep them (both reset their filter at the next update)"""
+    from radiodsp_sdr_rx_amd._lib import RdspError
+    nch, m, R, nb = 10, 3, 9, 320
+    x = np.stack([_drawn_session(7500 + c, nb)[0] for c in range(nch)])
+    eng = _engine(rdsp, nch, 8)
+    eng.sketch_setup()
+    G = _Groups(eng, [0, 4], x)
+    G.call(0, 1, "setDemodMode", 4)
+    G.run(0, m, 8)
+    G.call(m, 1, "setDemodMode", 0)
+    G.run(m, R, 8)
+    G.call(R, 1, "setAudioFilter", 3)
+    for firsts in ([0], [0, 7], [0, 2]):                           # group 1's channels would join a group without its reset
+        with pytest.raises(RdspError) as ex:
+            eng.set_groups(firsts)
+        assert ex.value.code == -5 and b"rdsp_engine_update" in eng.lib.rdsp_last_error()
+    assert eng.lib.rdsp_engine_groups(eng.h) == 2
+    G.set_groups([0, 4, 7])                                         # cutting group 1 in two keeps its reset in both halves
+    G.run(R, R + 1, 8)
+    G.call(R + 1, -1, "setAudioFilter", 3)                         # the same reset pending in every group
+    G.set_groups([0])
+    G.play(R + 1, nb, 8, _common_calls(7600, R + 1, nb))
+    G.check(G.result())
+
+
+@pytest.mark.gpu
+def test_gpu_engine_group_wider_than_a_grid_dimension(rdsp):
+    """one group of 65 537 channels (the side-band kernel's grid has a row per channel of the group), 2 blocks a call:
+    the same drawn row on every channel; the first, the 65 536th and the last channel against the restatement"""
+    import torch
+    import oracle_lib
+    nch, nb = 65537, 4
+    row, _ = _drawn_session(7700, nb)
+    eng = _engine(rdsp, nch, 2)
+    eng.sketch_setup()
+    d = torch.from_numpy(row).cuda()[None].expand(nch, -1, -1).contiguous()
+    y = torch.cat([eng.update(d[:, a * 128:(a + 2) * 128].contiguous()) for a in range(0, nb, 2)], 1)
+    got = y[[0, 65535, 65536], :, 0].cpu().numpy()
+    want = oracle_lib.OracleEngine().run(row)
+    for k in range(3):
+        assert np.array_equal(got[k], want), k

@@ -232,3 +232,148 @@ def test_gpu_one_chain_as_the_sketch_as_shipped(kat, rdsp):
         if b == 0:
             conv_ref = Chain(1, max_blocks_per_call=2, **dict(CONV, lms_nr=0))
         assert torch.equal(y, conv_ref.process(s))
+
+
+@pytest.mark.gpu
+def test_gpu_preprocessor_reset(kat, rdsp):
+    """rdsp_preproc_reset: the state as constructed -- nothing detected, NOT detecting (detection is a one-shot command, not
+    a setting), no carried sample; swapIQ kept.  Told to detect again, the object repeats the image's blocks and verdicts"""
+    import torch
+    from radiodsp_sdr_rx_amd.engine import PreProcessor
+    for name, swap in (("pre_slip_q", False), ("pre_slip_i", False), ("pre_swap", True)):
+        iq = kat[name + "_iq"]
+        x = torch.from_numpy(np.stack([iq, iq[::-1].copy()])).cuda()
+        p = PreProcessor(2)
+        p.startAutoI2SerrorDetection()
+        p.swapIQ(swap)
+        first = p.update(x).cpu().numpy()
+        assert np.array_equal(first[0], kat[name + "_pre"]), name
+        p.reset()
+        assert not p.state().any(), name                          # not detecting, no remedy, no counts
+        idle = p.update(x[:, :16 * 128].contiguous()).cpu().numpy()   # not told to detect: the rails pass as they come
+        assert np.array_equal(idle, (x[:, :16 * 128].flip(2) if swap else x[:, :16 * 128]).cpu().numpy()), name
+        assert not p.state().any(), name
+        p.reset()
+        p.startAutoI2SerrorDetection()
+        again = torch.cat([p.update(x[:, a:a + 3 * 128].contiguous()) for a in range(0, len(iq), 3 * 128)], 1).cpu().numpy()
+        assert np.array_equal(again, first), name
+        assert list(p.state()[0]) == list(kat[name + "_pre_state"][-1]), name
+
+
+def _sketch_chain(nch, max_blocks):
+    """tests/test_gpu_one_chain_as_the_sketch_as_shipped's engine-literal chain and set-up (INO:117-139, 177)"""
+    import oracle_lib
+    from radiodsp_sdr_rx_amd.chain import Chain
+    from radiodsp_sdr_rx_amd.config import AUDIO_FILTER, DEMOD
+    ch = Chain(nch, max_blocks_per_call=max_blocks, **CONV)
+    ch.set_engine_literal(True, oracle_lib.engine_tables())
+    ch.startAutoI2SerrorDetection()
+    ch.enableAGC(); ch.setAGCmode(2); ch.disableALSfilter(); ch.disableNoiseBlanker()
+    ch.setInputGain(1.0); ch.setOutputGain(0.5); ch.setIQgainBalance(1.020)
+    ch.enableAudioFilter(); ch.setAudioFilter(AUDIO_FILTER["audio2700"])
+    assert ch.lib.rdsp_sdr_setDemodMode(ch.h, DEMOD["LSB"], None) == 8390
+    ch.setMute(False)
+    return ch
+
+
+def _play(ch, x, cuts):
+    """x: cuda int16 [ch, n, 2] through the chain in calls of cuts[0], cuts[1], ... blocks (cycled)"""
+    import torch
+    out, a, k = [], 0, 0
+    while a < x.shape[1]:
+        b = min(x.shape[1], a + cuts[k % len(cuts)] * 128)
+        out.append(ch.process(x[:, a:b].contiguous()))
+        a, k = b, k + 1
+    return torch.cat(out, 1).cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_gpu_engine_literal_chain_reset(kat, rdsp):
+    """rdsp_chain_reset of an engine-literal chain resets the pre-processor and the engine in front of the CONV stage as
+    well: after a reset and a new startAutoI2SerrorDetection the slipped stream plays the same audio, bit for bit, cut
+    into other calls; a chain that is not told to detect again reports that it is not detecting"""
+    import ctypes as C
+    import torch
+    name = "sketch_path_slip"
+    iq = kat[name + "_iq"]
+    ch = _sketch_chain(2, 8)
+    x = torch.from_numpy(np.stack([iq, iq])).cuda()
+    first = _play(ch, x, [8])
+    assert one_count(first[0], kat[name + "_audio"])
+    lib = ch.lib
+    pre = lib.rdsp_chain_preproc(ch.h)
+    st = np.zeros((2, 4), np.int16)
+    ch.reset()
+    assert lib.rdsp_preproc_get_state(pre, st.ctypes.data_as(C.POINTER(C.c_int16)), None) == 0
+    assert not st.any()                                             # nothing detected, not detecting
+    ch.startAutoI2SerrorDetection()
+    again = _play(ch, x, [2, 6, 4])
+    assert np.array_equal(again, first)
+    assert one_count(again[0], kat[name + "_audio"])
+    assert lib.rdsp_preproc_get_state(pre, st.ctypes.data_as(C.POINTER(C.c_int16)), None) == 0
+    assert list(st[0]) == list(kat[name + "_pre_state"][-1])
+    ch.reset()                                                      # and without a new start: the slip is not repaired
+    assert lib.rdsp_preproc_get_state(pre, st.ctypes.data_as(C.POINTER(C.c_int16)), None) == 0
+    assert not st.any()
+    _play(ch, x[:, :16 * 128], [8])
+    assert lib.rdsp_preproc_get_state(pre, st.ctypes.data_as(C.POINTER(C.c_int16)), None) == 0
+    assert not st.any()
+
+
+@pytest.mark.gpu
+def test_gpu_engine_literal_chain_refuses_its_state_blob(kat, rdsp):
+    """the chain's blob does not carry the pre-processor's and the engine's state: an engine-literal chain refuses to save
+    one and to load one (RDSP_ERR_UNSUPPORTED), and says where the engine's state is saved"""
+    import torch
+    from radiodsp_sdr_rx_amd.chain import Chain
+    from radiodsp_sdr_rx_amd._lib import RdspError
+    iq = kat["sketch_path_slip_iq"][:16 * 128]
+    x = torch.from_numpy(np.stack([iq, iq])).cuda()
+    ch = _sketch_chain(2, 8)
+    _play(ch, x, [8])
+    with pytest.raises(RdspError) as ex:
+        ch.save_state(0, 1)
+    assert ex.value.code == -5 and b"rdsp_engine_save_state" in ch.lib.rdsp_last_error()
+    plain = Chain(2, max_blocks_per_call=8, **CONV)
+    blob = plain.save_state(0, 1)                                   # a blob of the bare CONV stage
+    fresh = _sketch_chain(2, 8)
+    with pytest.raises(RdspError) as ex:
+        fresh.load_state(blob, 0)
+    assert ex.value.code == -5 and b"rdsp_engine_save_state" in fresh.lib.rdsp_last_error()
+    plain.load_state(blob, 1)                                       # the same blob is fine without the engine
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("stand_in", ["enableNoiseBlanker", "swapIQ", "setIQslip+1", "setIQslip-1"])
+def test_gpu_engine_literal_switch_with_stand_ins_on(kat, rdsp, stand_in):
+    """the chain's own noise blanker, swapIQ and slip correction act in the CONV stage, and after the switch their setters
+    reach the engine's objects: a switch while one is on is refused and leaves the chain as it was; turned off, the switch
+    goes through and the chain plays what one that never called them plays.  A slip correction is refused afterwards"""
+    import torch
+    import oracle_lib
+    from radiodsp_sdr_rx_amd.chain import Chain
+    from radiodsp_sdr_rx_amd._lib import RdspError
+    on, off = {"enableNoiseBlanker": (("enableNoiseBlanker",), ("disableNoiseBlanker",)), "swapIQ": (("swapIQ", True), ("swapIQ", False)),
+               "setIQslip+1": (("setIQslip", 1), ("setIQslip", 0)), "setIQslip-1": (("setIQslip", -1), ("setIQslip", 0))}[stand_in]
+    ch = Chain(2, max_blocks_per_call=8, **CONV)
+    getattr(ch, on[0])(*on[1:])
+    with pytest.raises(RdspError) as ex:
+        ch.set_engine_literal(True, oracle_lib.engine_tables())
+    assert ex.value.code == -5
+    assert not ch.lib.rdsp_chain_engine(ch.h) and not ch.lib.rdsp_chain_preproc(ch.h)
+    getattr(ch, off[0])(*off[1:])
+    ch.set_engine_literal(True, oracle_lib.engine_tables())
+    ref = _sketch_chain(2, 8)
+    ch.startAutoI2SerrorDetection()
+    ch.enableAGC(); ch.setAGCmode(2); ch.disableALSfilter(); ch.disableNoiseBlanker()
+    ch.setInputGain(1.0); ch.setOutputGain(0.5); ch.setIQgainBalance(1.020)
+    from radiodsp_sdr_rx_amd.config import AUDIO_FILTER, DEMOD
+    ch.enableAudioFilter(); ch.setAudioFilter(AUDIO_FILTER["audio2700"])
+    assert ch.lib.rdsp_sdr_setDemodMode(ch.h, DEMOD["LSB"], None) == 8390
+    ch.setMute(False)
+    iq = kat["sketch_path_slip_iq"][:32 * 128]
+    x = torch.from_numpy(np.stack([iq, iq[::-1].copy()])).cuda()
+    assert np.array_equal(_play(ch, x, [8]), _play(ref, x, [8]))
+    with pytest.raises(RdspError) as ex:
+        ch.setIQslip(1)
+    assert ex.value.code == -5
