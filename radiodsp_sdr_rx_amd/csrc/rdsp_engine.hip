@@ -38,6 +38,9 @@
  * loads them (rdsp_engine_load_tables; tests take them from tests/golden/firmware_tables.npz); update() refuses to run
  * without them.  The sine table and the AGC's gain curve are generated here the way the library generates them.
  *
+ * The hang AGC, the ALS filter and the output word are the pieces of rdsp_engine_laws.h, which the chain's engine-law
+ * tail stage (rdsp_tail_engine.hip) calls too; the two tail kernels here keep their lanes, tiles and HBM layouts.
+ *
  * Compiled with -ffp-contract=off: every fused operation below is written as one (fmaf / fma).
  */
 #include <hip/hip_runtime.h>
@@ -48,13 +51,14 @@
 #include <algorithm>
 #include <vector>
 
-#include "rdsp_engine_agc.h"
+#include "rdsp_engine_laws.h"
 #include "rdsp_host.h"
 #include "rdsp_sync.h"
 
 namespace {
 
 constexpr int BS = RDSP_BLOCK_SAMPLES;
+static_assert(BS == RDSP_BLOCK, "the tail kernels hand rdsp_engine_laws.h rows of BS samples");
 constexpr int PITCH = BS + 1;
 constexpr float TWO_PI_F = 6.2831854820251465f;   /* the float the image holds for 2 pi */
 constexpr float RAD_PER_HZ = 0.00014247586659621447f; /* 2 pi / 44100, its float */
@@ -63,8 +67,7 @@ constexpr float RAD_PER_HZ = 0.00014247586659621447f; /* 2 pi / 44100, its float
 enum { ST_PRE = 0, ST_AM = 32, ST_AUDIO = 64, ST_NCO = 80, ST_AMPH, ST_SAM_COS, ST_SAM_SIN, ST_SAM_U, ST_SAM_ERR, ST_SAM_HZ,
        ST_SAM_PH, ST_SAM_LOCK, ST_AGC_ENV, ST_AGC_GAIN, ST_AGC_HANG, ST_AGC_ACTIVE, ST_NB_AVG, ST_NB_HIT, ST_NB_LAST, NF = 96 };
 enum { RESET_PRE = 1, RESET_AUDIO = 2, RESET_ALS = 4 };
-constexpr int ALS_TAPS = 55, ALS_DELAY = 3, ALS_WPITCH = 64; /* the constructor's values; the image has no setter for them */
-constexpr int ALS_WORDS = 256 + ALS_WPITCH;                /* per channel in HBM: the 256-sample line, then the taps */
+constexpr int ALS_WORDS = 256 + 64;                       /* per channel in HBM: the 256-sample line, then the taps (64 words) */
 constexpr int NB_WORDS = 3 * 384;                          /* per channel: I line, Q line, mask */
 
 struct EngParams {
@@ -79,7 +82,7 @@ struct EngParams {
   int mode, mute, audio_on, agc_on, als_notch, als_adaptive, resets;
   int pre_set, audio_set;
   float gain_i, gain_q, output_gain, tuning_offset, if_centre;
-  float agc_attack_a, agc_attack_b, agc_decay_a, agc_decay_b, agc_makeup; int agc_hang_time;
+  EngineAgcSet agc;
   float nb_keep, nb_new, nb_ratio; int nb_before, nb_after;
   float sam_keep, sam_new, sam_hz_per_rad, sam_lock_lo, sam_lock_hi, sam_ga, sam_gb;
 };
@@ -561,7 +564,7 @@ __global__ __launch_bounds__(FW, 2) void rdsp_engine_tail_kernel(const EngParams
   const bool als_lane = ALS && (tid >> 6) == 1;
   const int ac = (tid >> 2) & (TCH - 1), aq = tid & 3;
   const int ach = min(c0 + ac, p.n_channels - 1);
-  float w[ALS ? ALS_TAPS : 1];
+  float w[ALS ? RDSP_ENG_ALS_TAPS : 1];
   const bool casc = tid < 4 * TCH;
   const int row = (tid >> 2) & (TCH - 1), sct = tid & 3;
   const int rch = min(c0 + row, p.n_channels - 1);
@@ -571,9 +574,9 @@ __global__ __launch_bounds__(FW, 2) void rdsp_engine_tail_kernel(const EngParams
   const int sc = (tid - 64) & (TCH - 1);
   const bool ser_valid = ser && c0 + sc < p.n_channels;
   const int sch = min(c0 + sc, p.n_channels - 1);
-  float *sst = p.st + (size_t)sch * NF;
-  float env = sst[ST_AGC_ENV], g = sst[ST_AGC_GAIN];
-  int hang = __float_as_int(sst[ST_AGC_HANG]), active = __float_as_int(sst[ST_AGC_ACTIVE]);
+  float *sst = p.st + (size_t)sch * NF + ST_AGC_ENV;
+  EngineAgcState agc;
+  agc.load(sst);
   for (int i = tid; i < 130; i += FW) curve[i] = p.curve[i];
   if constexpr (ALS) {
     if (als_lane) {
@@ -581,7 +584,7 @@ __global__ __launch_bounds__(FW, 2) void rdsp_engine_tail_kernel(const EngParams
       const bool clear = (p.resets & RESET_ALS) != 0;
       for (int i = aq; i < 256; i += 4) line[ac][i] = clear ? 0.0f : a[i];
 #pragma unroll
-      for (int k = 0; k < ALS_TAPS; k++) w[k] = clear ? 0.0f : a[256 + k];
+      for (int k = 0; k < RDSP_ENG_ALS_TAPS; k++) w[k] = clear ? 0.0f : a[256 + k];
     }
   }
   constexpr int EP = TCH * BS / FW;
@@ -598,84 +601,40 @@ __global__ __launch_bounds__(FW, 2) void rdsp_engine_tail_kernel(const EngParams
     }
     if (p.agc_on) {
       if (ser) {
-        g_in[sc] = g;
-        float last = -1.0f;                      /* the envelope the current gain was looked up from; < 0: none in this block yet */
-        const float *a = ta[sc];
-        float anext = a[0];
-        for (int t = 0; t < BS; t++) {
-          float in = fabsf(anext);
-          anext = a[t + 1 < BS ? t + 1 : BS - 1];
-          if (in > 1.0f) in = 1.0f;
-          /* attack (the hang counter is re-armed) / decay (counter at 0) / hold (count down): both candidate envelopes
-           * are formed and one is selected -- the channels of a wave are in different states, and as branches every
-           * lane would walk all three arms */
-          const bool attack = env < in, decay = !attack && hang == 0;
-          const float ea = fmaf(env, p.agc_attack_a, in * p.agc_attack_b), ed = fmaf(env, p.agc_decay_a, in * p.agc_decay_b);
-          env = attack ? ea : (decay ? ed : env);
-          hang = attack ? p.agc_hang_time : (decay ? 0 : hang - 1);
-          last = (attack || decay) ? env : last;
-          ge[sc][t] = last;
-        }
-        if (last >= 0.0f) g = agc_lookup(curve, last);
-        active = (double)g < 0.98999999999999999;
+        g_in[sc] = agc.g;
+        agc_envelope(agc, p.agc, curve, ta[sc], ge[sc]);
       }
       __syncthreads();
       for (int j = 0; j < EP; j++) {
         const int e = tid + FW * j, r = e >> 7, t = e & 127;
-        const float le = ge[r][t];
-        const float gg = le < 0.0f ? g_in[r] : agc_lookup(curve, le);
-        float y = (gg * p.agc_makeup) * ta[r][t];
-        if (y > 1.0f) y = 1.0f;
-        else if (y < -1.0f) y = -1.0f;
-        ta[r][t] = y;
+        ta[r][t] = agc_gain_clamp(p.agc, curve, ge[r][t], g_in[r], ta[r][t]);
       }
       __syncthreads();
     }
     if constexpr (ALS) {
-      /* 0xda24: y[n] = sum_k w_k x[n - 3 - k] as a chain of 55 fused multiply-adds, e = x[n] - y; on every fourth sample of a
-       * block (its first one included) the taps move by w_k += (e x[n - 3 - k]) / 2.  The chain of one sample cannot be cut,
-       * but the four samples between two tap moves see the same taps: the four lanes of a quad take one each (the taps in
-       * registers, the same in all four), then every lane makes the move with the fourth lane's error.  Quads of four
-       * samples ending on a move: {125 .. 128} (only 128 is this block's), {129 .. 132}, ..., {253 .. 256} (256 is the next
-       * block's first: not computed here, no move). */
+      /* the line: the previous block, then this one (samples 128 .. 255) */
       if (als_lane) {
         float *x = line[ac], *rowp = ta[ac];
         for (int i = aq; i < 128; i += 4) { x[i] = x[i + 128]; x[i + 128] = rowp[i]; }
         wg_sync<1>();
-        for (int g = -1; g < 32; g++) {
-          const int n = 129 + 4 * g + aq;
-          float y = 0.0f;
-#pragma unroll
-          for (int k = 0; k < ALS_TAPS; k++) y = fmaf(w[k], x[n - ALS_DELAY - k], y);
-          const float err = x[n < 256 ? n : 255] - y;
-          if (n >= 128 && n < 256) rowp[n - 128] = p.als_notch ? err : y;
-          if (p.als_adaptive && g < 31) {
-            const float e3 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, err), 0xFF, 0xF, 0xF, false)); /* quad_perm [3,3,3,3] */
-            const float *xm = x + (132 + 4 * g) - ALS_DELAY;
-#pragma unroll
-            for (int k = 0; k < ALS_TAPS; k++) w[k] = fmaf(e3 * xm[-k], 0.5f, w[k]);
-          }
-        }
+        als_block<128>(w, x, rowp, aq, p.als_notch, p.als_adaptive);
       }
       __syncthreads();
     }
-    for (int j = 0; j < EP; j++) { /* 0xebfa: x output gain x 32767 toward zero, the low half-word, on both outputs */
+    for (int j = 0; j < EP; j++) {
       const int e = tid + FW * j, r = e >> 7, t = e & 127;
-      const uint32_t v = p.mute ? 0u : ((uint32_t)trunc_s32((double)(ta[r][t] * p.output_gain) * 32767.0) & 0xffffu);
-      if (c0 + r < p.n_channels) p.out[(size_t)(c0 + r) * p.out_stride + (size_t)b * BS + t] = (int32_t)(v | (v << 16));
+      if (c0 + r < p.n_channels) p.out[(size_t)(c0 + r) * p.out_stride + (size_t)b * BS + t] = engine_out_word(ta[r][t], p.output_gain, p.mute);
     }
   }
   if (casc && c0 + row < p.n_channels) aud.store(p.st + (size_t)rch * NF + ST_AUDIO + 4 * sct);
-  if (ser_valid) {
-    sst[ST_AGC_ENV] = env; sst[ST_AGC_GAIN] = g; sst[ST_AGC_HANG] = __int_as_float(hang); sst[ST_AGC_ACTIVE] = __int_as_float(active);
-  }
+  if (ser_valid) agc.store(sst);
   if constexpr (ALS) {
     if (als_lane && c0 + ac < p.n_channels) {
       float *a = p.als + (size_t)ach * ALS_WORDS;
       for (int i = aq; i < 256; i += 4) a[i] = line[ac][i];
       if (aq == 0) {
 #pragma unroll
-        for (int k = 0; k < ALS_TAPS; k++) a[256 + k] = w[k];
+        for (int k = 0; k < RDSP_ENG_ALS_TAPS; k++) a[256 + k] = w[k];
       }
     }
   }
@@ -699,9 +658,9 @@ __global__ __launch_bounds__(PW, 2) void rdsp_engine_tail_pipe_kernel(const EngP
   const int sc = tid & (TCH - 1);
   const bool ser = wave == 1 && (tid & 63) < TCH;
   const int sch = min(c0 + sc, p.n_channels - 1);
-  float *sst = p.st + (size_t)sch * NF;
-  float env = sst[ST_AGC_ENV], g = sst[ST_AGC_GAIN];
-  int hang = __float_as_int(sst[ST_AGC_HANG]), active = __float_as_int(sst[ST_AGC_ACTIVE]);
+  float *sst = p.st + (size_t)sch * NF + ST_AGC_ENV;
+  EngineAgcState agc;
+  agc.load(sst);
   for (int i = tid; i < 130; i += PW) curve[i] = p.curve[i];
   const int wl = tid - 128;
   constexpr int EP = TCH * BS / (PW - 128);
@@ -722,15 +681,8 @@ __global__ __launch_bounds__(PW, 2) void rdsp_engine_tail_pipe_kernel(const EngP
         for (int j = 0; j < EP; j++) {
           const int e = wl + (PW - 128) * j, r = e >> 7, t = e & 127;
           float y = t3[r][t];
-          if (p.agc_on) {
-            const float le = e3[r][t];
-            const float gg = le < 0.0f ? g_in[b & 3][r] : agc_lookup(curve, le);
-            y = (gg * p.agc_makeup) * y;
-            if (y > 1.0f) y = 1.0f;
-            else if (y < -1.0f) y = -1.0f;
-          }
-          const uint32_t v = p.mute ? 0u : ((uint32_t)trunc_s32((double)(y * p.output_gain) * 32767.0) & 0xffffu);
-          if (c0 + r < p.n_channels) p.out[(size_t)(c0 + r) * p.out_stride + (size_t)b * BS + t] = (int32_t)(v | (v << 16));
+          if (p.agc_on) y = agc_gain_clamp(p.agc, curve, e3[r][t], g_in[b & 3][r], y);
+          if (c0 + r < p.n_channels) p.out[(size_t)(c0 + r) * p.out_stride + (size_t)b * BS + t] = engine_out_word(y, p.output_gain, p.mute);
         }
       }
     } else if (wave == 0) {
@@ -739,32 +691,14 @@ __global__ __launch_bounds__(PW, 2) void rdsp_engine_tail_pipe_kernel(const EngP
     } else {
       const int b = step - 2;
       if (ser && p.agc_on && b >= 0 && b < p.n_blocks) {
-        g_in[b & 3][sc] = g;
-        float last = -1.0f;                      /* the envelope the current gain was looked up from; < 0: none in this block yet */
-        const float *a = ta[b & 3][sc];
-        float *lo = ge[b & 3][sc];
-        float anext = a[0];
-        for (int t = 0; t < BS; t++) {
-          float in = fabsf(anext);
-          anext = a[t + 1 < BS ? t + 1 : BS - 1];
-          if (in > 1.0f) in = 1.0f;
-          const bool attack = env < in, decay = !attack && hang == 0;
-          const float ea = fmaf(env, p.agc_attack_a, in * p.agc_attack_b), ed = fmaf(env, p.agc_decay_a, in * p.agc_decay_b);
-          env = attack ? ea : (decay ? ed : env);
-          hang = attack ? p.agc_hang_time : (decay ? 0 : hang - 1);
-          last = (attack || decay) ? env : last;
-          lo[t] = last;
-        }
-        if (last >= 0.0f) g = agc_lookup(curve, last);
-        active = (double)g < 0.98999999999999999;
+        g_in[b & 3][sc] = agc.g;
+        agc_envelope(agc, p.agc, curve, ta[b & 3][sc], ge[b & 3][sc]);
       }
     }
     __syncthreads();
   }
   if (casc && c0 + row < p.n_channels) aud.store(p.st + (size_t)rch * NF + ST_AUDIO + 4 * sct);
-  if (ser && c0 + sc < p.n_channels) {
-    sst[ST_AGC_ENV] = env; sst[ST_AGC_GAIN] = g; sst[ST_AGC_HANG] = __int_as_float(hang); sst[ST_AGC_ACTIVE] = __int_as_float(active);
-  }
+  if (ser && c0 + sc < p.n_channels) agc.store(sst);
 }
 
 }  // namespace
@@ -775,8 +709,7 @@ __global__ __launch_bounds__(PW, 2) void rdsp_engine_tail_pipe_kernel(const EngP
 struct EngSettings {
   float input_gain, gain_i, gain_q, iq_balance, output_gain, tuning_offset;
   int mode, mute, audio_on, audio_id, audio_set, pre_set, agc_on, als_on, als_notch, als_adaptive, nb_on, resets;
-  float agc_attack_a, agc_attack_b, agc_decay_a, agc_decay_b;
-  int agc_hang_time;
+  EngineAgcSet agc;
   uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
 };
 struct rdsp_engine {
@@ -786,7 +719,7 @@ struct rdsp_engine {
   float *d_st = nullptr, *d_ring_i = nullptr, *d_ring_q = nullptr, *d_audio = nullptr, *d_nb = nullptr, *d_als = nullptr, *d_tab = nullptr;
   float curve[130], sine[257];
   /* constants of the object (docs/engine.md has their places in the image's AudioSDR) */
-  float if_centre, ssb_band, cw_band, agc_makeup, agc_knee_db, agc_slope, agc_threshold_db, sam_ga, sam_gb;
+  float if_centre, ssb_band, cw_band, agc_knee_db, agc_slope, agc_threshold_db, sam_ga, sam_gb;
   std::vector<EngSettings> grp; /* at least one */
   std::vector<int> first;       /* first channel of each group, ascending; first[0] = 0 */
   int sel = -1;                 /* the group the setters address; -1: all of them */
@@ -817,10 +750,7 @@ int for_selected(rdsp_engine_t *e, F f) {
 void settings_agc_mode(EngSettings &s, int mode) { /* 0xdfe0 */
   if (mode == 0) { s.agc_on = 0; return; }
   if (mode < 0 || mode > 3) return; /* the engine ignores other values */
-  const EngineAgcSet k = engine_agc_set(mode);
-  s.agc_attack_a = k.attack_a; s.agc_attack_b = k.attack_b;
-  s.agc_decay_a = k.decay_a; s.agc_decay_b = k.decay_b;
-  s.agc_hang_time = k.hang_time;
+  s.agc = engine_agc_set(mode);
   s.agc_on = 1;
 }
 void settings_demod(const rdsp_engine_t *e, EngSettings &s, int mode) { /* 0xd798 */
@@ -841,8 +771,8 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   memset(&s, 0, sizeof s);
   s.input_gain = s.gain_i = s.gain_q = s.iq_balance = s.output_gain = 1.0f;
   s.audio_set = 3; s.nb_on = 1; s.als_notch = 1; s.als_adaptive = 1;
-  settings_agc_mode(s, 2); /* 0xdf14: the medium attack with the slow decay and the fast hang time */
-  { const EngineAgcSet k = engine_agc_set(0); s.agc_decay_a = k.decay_a; s.agc_decay_b = k.decay_b; s.agc_hang_time = k.hang_time; }
+  s.agc = engine_agc_set(0); /* 0xdf14: the medium attack with the slow decay and the fast hang time */
+  s.agc_on = 1;
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -1026,8 +956,7 @@ int rdsp_engine_create(int n_channels, int device, int max_blocks_per_call, rdsp
   e->tables = false;
   /* the constructor's values */
   e->if_centre = 6890.0f; e->ssb_band = 3000.0f; e->cw_band = 1000.0f;
-  e->agc_makeup = ENGINE_AGC_MAKEUP; e->agc_threshold_db = ENGINE_AGC_THRESHOLD_DB; e->agc_slope = bits_f(ENGINE_AGC_SLOPE_BITS);
-  e->agc_knee_db = ENGINE_AGC_KNEE_DB;
+  e->agc_threshold_db = ENGINE_AGC_THRESHOLD_DB; e->agc_slope = bits_f(ENGINE_AGC_SLOPE_BITS); e->agc_knee_db = ENGINE_AGC_KNEE_DB;
   engine_agc_curve(e->agc_threshold_db, e->agc_knee_db, e->agc_slope, e->curve);
   engine_sam_constants(e);
   for (int k = 0; k < 257; k++) e->sine[k] = (float)(round(sin(2.0 * 3.14159265358979323846 * k / 256.0) * 1e8) / 1e8);
@@ -1102,8 +1031,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     p.mode = q.mode; p.mute = q.mute; p.audio_on = q.audio_on; p.agc_on = q.agc_on; p.als_notch = q.als_notch;
     p.als_adaptive = q.als_adaptive; p.resets = q.resets; p.pre_set = q.pre_set; p.audio_set = q.audio_set;
     p.gain_i = q.gain_i; p.gain_q = q.gain_q; p.output_gain = q.output_gain; p.tuning_offset = q.tuning_offset; p.if_centre = e->if_centre;
-    p.agc_attack_a = q.agc_attack_a; p.agc_attack_b = q.agc_attack_b; p.agc_decay_a = q.agc_decay_a; p.agc_decay_b = q.agc_decay_b;
-    p.agc_makeup = e->agc_makeup; p.agc_hang_time = q.agc_hang_time;
+    p.agc = q.agc;
     p.nb_keep = 0.995f; p.nb_new = bits_f(0x3ba3d700); p.nb_ratio = 1.2f; p.nb_before = 10; p.nb_after = 10;
     p.sam_keep = 0.995f; p.sam_new = bits_f(0x3ba3d700); p.sam_hz_per_rad = bits_f(0x45db55dd); p.sam_lock_lo = 3890.0f; p.sam_lock_hi = 9890.0f;
     p.sam_ga = e->sam_ga; p.sam_gb = e->sam_gb;

@@ -145,6 +145,12 @@ struct RdspTailParams {
 #define RDSP_ENG_ALS_TAPS 55
 #define RDSP_ENG_ALS_WORDS (RDSP_ENG_ALS_HIST + 64) /* per channel: the line's newest 64 samples, oldest first, then the taps */
 #define RDSP_ENG_ST_WORDS 4  /* per channel: envelope, gain, hang counter (int), active flag (int) */
+/* the hang AGC's constants of a launch, rdsp_engine_t's and this stage's (engine_agc_set, rdsp_engine_laws.h) */
+struct EngineAgcSet {
+  float attack_a, attack_b, decay_a, decay_b;
+  float makeup;            /* the gain after the curve                                    */
+  int hang_time;           /* samples                                                     */
+};
 struct RdspTailEngineParams {
   const float *in;         /* [ch][in_stride] audio in                                   */
   size_t in_stride;
@@ -162,8 +168,7 @@ struct RdspTailEngineParams {
   int als_notch;           /* 1: the error goes out (notch), 0: the prediction (peak)     */
   int als_clear;           /* 1: line and taps start from zero (enableALSfilter, 0xdb2c)  */
   int prio;
-  float agc_attack_a, agc_attack_b, agc_decay_a, agc_decay_b, agc_makeup;
-  int agc_hang_time;
+  EngineAgcSet agc;
   float curve[130];        /* the AGC's gain curve (0xdd40)                               */
 };
 

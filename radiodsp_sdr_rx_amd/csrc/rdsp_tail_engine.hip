@@ -15,14 +15,15 @@
  *   - the ALS filter runs on a quad per channel: the four samples between two tap moves see the same taps, so each lane
  *     evaluates one sample's chain of 55 fused multiply-adds (the taps in registers, the same in all four lanes), and
  *     every lane then makes the move with the fourth lane's error (quad_perm DPP).
- * The per-sample arithmetic is rdsp_engine_tail_kernel's (rdsp_engine.hip), on the chain's buffers: float rows at any
- * stride in, int16 L = R pairs (arm_float_to_q15 rounding) and float pairs out, channel sub-batches by ch_base.
+ * The stage bodies are rdsp_engine_laws.h's, the ones rdsp_engine_t's tail kernels (rdsp_engine.hip) call; this kernel
+ * runs them on the chain's buffers: float rows at any stride in, int16 L = R pairs (arm_float_to_q15 rounding) and float
+ * pairs out, channel sub-batches by ch_base.
  * 180 VGPRs, no scratch.  (Holding the next block in registers through the current one took the kernel to 256 VGPRs
  * + 50 AGPRs: the ALS chain's 55 window loads are hoisted ahead of it.)  Measured cost: DESIGN.md 4.2b.
  *
- * Compiled with -ffp-contract=off: every fused operation below is written as one (fmaf).
+ * Compiled with -ffp-contract=off, as rdsp_engine_laws.h requires.
  */
-#include "rdsp_engine_agc.h"
+#include "rdsp_engine_laws.h"
 #include "rdsp_kernels.h"
 #include "rdsp_wave.h"
 
@@ -33,7 +34,6 @@ constexpr int TCH = 16;                   /* channels per wave */
 constexpr int H = RDSP_ENG_ALS_HIST;      /* ALS line: H samples of history, then the block */
 constexpr int LP = H + BS + 4;            /* pitch of a channel's line in LDS */
 constexpr int EP = TCH * BS / 64;         /* elements per lane and block (element e = lane + 64 j: row e / 128, sample e % 128) */
-constexpr int TAPS = RDSP_ENG_ALS_TAPS, DELAY = 3;
 
 __global__ __launch_bounds__(64) void rdsp_tail_engine_kernel(const RdspTailEngineParams p) {
   __shared__ float line[TCH][LP];
@@ -53,18 +53,18 @@ __global__ __launch_bounds__(64) void rdsp_tail_engine_kernel(const RdspTailEngi
   const int sc = tid & (TCH - 1);
   const int sch = min(c0 + sc, p.n_channels - 1);
   float *sst = p.st + (size_t)sch * RDSP_ENG_ST_WORDS;
-  float env = sst[0], g = sst[1];
-  int hang = __float_as_int(sst[2]), active = __float_as_int(sst[3]);
+  EngineAgcState agc;
+  agc.load(sst);
 
   /* ALS role: quad ac on channel c0 + ac, lane aq on every fourth sample */
   const int ac = tid >> 2, aq = tid & 3;
   const int ach = min(c0 + ac, p.n_channels - 1);
-  float w[TAPS];
+  float w[RDSP_ENG_ALS_TAPS];
   if (p.als_on) {
     const float *a = p.als + (size_t)ach * RDSP_ENG_ALS_WORDS;
     for (int i = aq; i < H; i += 4) line[ac][i] = p.als_clear ? 0.0f : a[i];
 #pragma unroll
-    for (int k = 0; k < TAPS; k++) w[k] = p.als_clear ? 0.0f : a[H + k];
+    for (int k = 0; k < RDSP_ENG_ALS_TAPS; k++) w[k] = p.als_clear ? 0.0f : a[H + k];
   }
 
   for (int b = 0; b < p.n_blocks; b++) {
@@ -85,63 +85,25 @@ __global__ __launch_bounds__(64) void rdsp_tail_engine_kernel(const RdspTailEngi
     wg_sync<1>();
     if (p.agc_on) {
       if (ser) {
-        g_in[sc] = g;
-        float last = -1.0f; /* the envelope the current gain was looked up from; < 0: none in this block yet */
-        const float *a = row[sc];
-        float anext = a[0];
-        for (int t = 0; t < BS; t++) {
-          float in = fabsf(anext);
-          anext = a[t + 1 < BS ? t + 1 : BS - 1];
-          if (in > 1.0f) in = 1.0f;
-          /* attack (the hang counter is re-armed) / decay (counter at 0) / hold (count down): both candidate envelopes
-           * are formed and one is selected -- the channels of a wave are in different states */
-          const bool attack = env < in, decay = !attack && hang == 0;
-          const float ea = fmaf(env, p.agc_attack_a, in * p.agc_attack_b), ed = fmaf(env, p.agc_decay_a, in * p.agc_decay_b);
-          env = attack ? ea : (decay ? ed : env);
-          hang = attack ? p.agc_hang_time : (decay ? 0 : hang - 1);
-          last = (attack || decay) ? env : last;
-          ge[sc][t] = last;
-        }
-        if (last >= 0.0f) g = agc_lookup(curve, last);
-        active = (double)g < 0.98999999999999999;
+        g_in[sc] = agc.g;
+        agc_envelope(agc, p.agc, curve, row[sc], ge[sc]);
       }
       wg_sync<1>();
 #pragma unroll 4
       for (int j = 0; j < EP; j++) {
         const int e = tid + 64 * j, r = e >> 7, t = e & 127;
-        const float le = ge[r][t];
-        const float gg = le < 0.0f ? g_in[r] : agc_lookup(curve, le);
-        float y = (gg * p.agc_makeup) * row[r][t];
-        if (y > 1.0f) y = 1.0f;
-        else if (y < -1.0f) y = -1.0f;
-        row[r][t] = y;
+        row[r][t] = agc_gain_clamp(p.agc, curve, ge[r][t], g_in[r], row[r][t]);
       }
       wg_sync<1>();
     }
     if (p.als_on) {
-      /* y[n] = sum_k w_k x[n - 3 - k] as one chain of 55 fused multiply-adds, e = x[n] - y; on every fourth sample of a
-       * block (its first one included) w_k += (e x[n - 3 - k]) / 2.  Block sample j sits at x[H + j].  Quads of four
-       * samples ending on a move: {-3 .. 0} (only 0 is this block's), {1 .. 4}, ..., {125 .. 128} (128 is the next
-       * block's first: not computed here, no move). */
+      /* the line: the newest H samples before the block, then the block */
       float *x = line[ac], *rowp = row[ac];
       if (b > 0)
         for (int i = aq; i < H; i += 4) x[i] = x[i + BS];
       for (int i = aq; i < BS; i += 4) x[H + i] = rowp[i];
       wg_sync<1>();
-      for (int q = -1; q < BS / 4; q++) {
-        const int m = H + 1 + 4 * q + aq;
-        float y = 0.0f;
-#pragma unroll
-        for (int k = 0; k < TAPS; k++) y = fmaf(w[k], x[m - DELAY - k], y);
-        const float err = x[m < H + BS ? m : H + BS - 1] - y;
-        if (m >= H && m < H + BS) rowp[m - H] = p.als_notch ? err : y;
-        if (q < BS / 4 - 1) {
-          const float e3 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, err), 0xFF, 0xF, 0xF, false)); /* quad_perm [3,3,3,3] */
-          const float *xm = x + (H + 4 + 4 * q) - DELAY;
-#pragma unroll
-          for (int k = 0; k < TAPS; k++) w[k] = fmaf(e3 * xm[-k], 0.5f, w[k]);
-        }
-      }
+      als_block<H>(w, x, rowp, aq, p.als_notch, 1);
       wg_sync<1>();
     }
 #pragma unroll 4
@@ -160,15 +122,13 @@ __global__ __launch_bounds__(64) void rdsp_tail_engine_kernel(const RdspTailEngi
     }
     wg_sync<1>();
   }
-  if (ser && c0 + sc < p.n_channels) {
-    sst[0] = env; sst[1] = g; sst[2] = __int_as_float(hang); sst[3] = __int_as_float(active);
-  }
+  if (ser && c0 + sc < p.n_channels) agc.store(sst);
   if (p.als_on && c0 + ac < p.n_channels) {
     float *a = p.als + (size_t)ach * RDSP_ENG_ALS_WORDS;
     for (int i = aq; i < H; i += 4) a[i] = line[ac][i + BS]; /* the newest H samples of the last block */
     if (aq == 0) {
 #pragma unroll
-      for (int k = 0; k < TAPS; k++) a[H + k] = w[k];
+      for (int k = 0; k < RDSP_ENG_ALS_TAPS; k++) a[H + k] = w[k];
     }
   }
 }
@@ -186,10 +146,6 @@ extern "C" int rdsp_launch_tail_engine(const RdspTailEngineParams *p, hipStream_
  * setAGCmode's), the makeup gain and the gain curve -- generated here, under this file's -ffp-contract=off, the way
  * rdsp_engine_t generates them */
 extern "C" void rdsp_tail_engine_constants(RdspTailEngineParams *p, int agc_set) {
-  const EngineAgcSet k = engine_agc_set(agc_set);
-  p->agc_attack_a = k.attack_a; p->agc_attack_b = k.attack_b;
-  p->agc_decay_a = k.decay_a; p->agc_decay_b = k.decay_b;
-  p->agc_hang_time = k.hang_time;
-  p->agc_makeup = ENGINE_AGC_MAKEUP;
+  p->agc = engine_agc_set(agc_set);
   engine_agc_curve(ENGINE_AGC_THRESHOLD_DB, ENGINE_AGC_KNEE_DB, bits_f(ENGINE_AGC_SLOPE_BITS), p->curve);
 }

@@ -243,6 +243,33 @@ def test_register_budget_of_the_two_kernels_that_share_a_simd(tmp_path):
     assert k2 and k3 and k2[0] <= 48 and k3[0] <= 24, (k2, k3)
 
 
+def test_register_budget_of_the_engine_law_tail_kernels(tmp_path):
+    """The three kernels that run the engine's hang AGC and ALS filter (csrc/rdsp_engine_laws.h) keep the registers they
+    had when their stage bodies were written out in each: no more VGPRs, nothing spilled, no scratch.  A serial
+    recursion that starts to spill waits out a scratch round trip on every sample."""
+    llvm = "/opt/rocm/lib/llvm/bin"
+    _device_disassembly(tmp_path)            # leaves the unbundled code objects b<n>.co in tmp_path
+    notes = {}
+    for co in sorted(tmp_path.glob("b*.co")):
+        ent = {}
+        for line in subprocess.run([llvm + "/llvm-readelf", "--notes", str(co)], capture_output=True, text=True,
+                                   check=True).stdout.splitlines():
+            if line.startswith("  - ."):          # a new entry of amdhsa.kernels
+                ent = {}
+            k, _, v = line.strip().lstrip("- ").partition(":")
+            ent[k] = v.strip()
+            if k == ".name":
+                notes[ent[k]] = ent
+    budget = {"rdsp_engine_tail_kernelILb1E": 209, "rdsp_engine_tail_pipe_kernel": 209, "rdsp_tail_engine_kernel": 180}
+    for key, vgpr in budget.items():
+        hit = [e for n, e in notes.items() if key in n]
+        assert len(hit) == 1, (key, sorted(notes)[:5])
+        e = hit[0]
+        assert int(e[".vgpr_count"]) <= vgpr and int(e[".agpr_count"]) == 0, (key, e[".vgpr_count"], e[".agpr_count"])
+        assert int(e[".vgpr_spill_count"]) == 0 and int(e[".sgpr_spill_count"]) == 0, key
+        assert int(e[".private_segment_fixed_size"]) == 0, key
+
+
 def test_branch_spectra_of_the_row_form_are_the_transforms_of_the_polyphase_taps():
     """rdsp_rd_decimator_image (rdsp_design.c): [r][bin] = DFT_256 of g_r[k] = h[4k - r] (k <= 64), divided by 256 -- what
     rdsp_front_rd_kernel multiplies the four low-rate transforms with.  Checked against numpy's FFT for a random tap
