@@ -714,9 +714,42 @@ int rdsp_engine_setAudioFilter(rdsp_engine_t *e, int id);          /* INO:138, C
 float rdsp_engine_setDemodMode(rdsp_engine_t *e, int mode);        /* INO:139: returns TuningOffset, Hz */
 int rdsp_engine_setMute(rdsp_engine_t *e, int on);                 /* INO:177 */
 /* AudioSDR::update() for n_blocks consecutive blocks of every channel, stream-ordered.  d_iq: [ch][t] int16 pairs (I, Q),
- * in_stride pairs between channel rows; d_lr: [ch][t] int16 pairs = the engine's two outputs (the same block on both). */
+ * in_stride pairs between channel rows; d_lr: [ch][t] int16 pairs = the engine's two outputs (the same block on both).
+ * Each row must already hold its station at the engine's IF; this call does not advance the tuning phases below. */
 int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, int n_blocks, int16_t *d_lr,
                        size_t out_stride, void *stream);
+/* Shared IQ streams: many receivers tuned to stations inside a few source rows -- the sketch's VFO, which puts its LO at
+ * vfoFreq - TuningOffset (RDSP_controls.h:447), done per receiver on the GPU.
+ * - Sources: d_src is int16 pairs [n_sources][src_stride] at 44 100 Hz; receiver ch listens to row source_of_channel[ch]
+ *   (several receivers may share a row).  rdsp_engine_set_sources sets the map; the first call allocates the engine's
+ *   tuned rows ([ch][max_blocks_per_call * 128] pairs) and per-channel phases (an engine that never calls it uses no more
+ *   memory than before).  It takes no stream: it waits for everything queued on the engine's device before it changes a map.
+ * - Station: station_hz[k] is where receiver first_channel + k's station sits in its source, from the stream's centre,
+ *   |f| < 22 050 (0 until tuned).  Positive frequency is I + jQ, the engine's own convention.  Stations are settings: kept
+ *   by rdsp_engine_reset, not part of a state blob.
+ * - Tuned row: x_ch[n] = sat16(rne(x_src[n] e^{+j phi_ch[n]})), phi_ch a uint32 phase accumulator (turns x 2^32) that is 0
+ *   at create and after rdsp_engine_reset, stays continuous across calls, retunes, mode changes and regroupings, and
+ *   advances per sample by dphi = round((TuningOffset of ch's group's mode - station_hz) 2^32 / 44100), computed from the
+ *   group's mode at every call (a receiver stays on its station when its mode changes, as the sketch re-tunes its LO;
+ *   round is half away from zero, taken mod 2^32).  The phasor comes from a 1024-entry table of cos / sin with linear
+ *   interpolation (error below 2^-17; phase 0 is exactly (1, 0), so a shift of 0 is the identity); the rotation is the
+ *   engine shifter's, I' = fmaf(I, c, -(Q s)), Q' = fmaf(Q, c, I s); rounding half to even, saturation to int16.
+ *   rdsp_engine_tune_table gives the table: [1024][4] = cos, sin of 2 pi k / 1024, and the steps to entry k + 1.
+ * - rdsp_engine_update_sources = the tuning pass, then rdsp_engine_update on the tuned rows, every group: the audio is
+ *   bit for bit what rdsp_engine_update returns on those rows.  Source rows must be 16-byte aligned, a multiple of 4 pairs
+ *   apart (src_stride) and at least n_blocks * 128 pairs long.
+ * - Refused with nothing changed (RDSP_ERR_INVALID): a source index outside [0, n_sources), n_sources < 1, |station| >=
+ *   22 050 (or NaN), a channel range outside the object, a short or misaligned src_stride or d_src, n_blocks > max_blocks;
+ *   rdsp_engine_update_sources before rdsp_engine_set_sources is RDSP_ERR_NOT_READY.
+ * - State as data: once an engine has sources, its blobs carry each channel's phase (a flag in the header word that was 0,
+ *   one word per channel appended; rdsp_engine_state_bytes says so), and a moved receiver continues bit for bit.  The blob
+ *   of an engine without sources is unchanged.  Loading a blob with phases needs sources (RDSP_ERR_NOT_READY); loading one
+ *   without phases into an engine with sources sets those channels' phases to 0. */
+int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_of_channel);
+int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const double *station_hz);
+int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr,
+                               size_t out_stride, void *stream);
+const float *rdsp_engine_tune_table(void);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).
@@ -724,7 +757,8 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
  * rdsp_engine_setDemodMode returns the offset of the selected group (of group 0 for -1).  Regrouping in mid-stream:
  * - a new group's settings are copied from the old group its first channel was in;
  * - signal state stays with the channel (filters, oscillator, AGC, side-band lines, blanker, ALS): a channel continues as
- *   it would have in its old group with the new group's settings from the next update on;
+ *   it would have in its old group with the new group's settings from the next update on; so do its station and tuning
+ *   phase (rdsp_engine_update_sources below), and its step follows the new group's mode from the next call on;
  * - pending resets (setDemodMode / setAudioFilter / enableALSfilter made since the last update) are settings too: a new
  *   group whose channels come from old groups with different pending resets is refused (RDSP_ERR_UNSUPPORTED, "call
  *   rdsp_engine_update first") and nothing changes;

@@ -282,6 +282,10 @@ SYMBOLS = [
     ("rdsp_engine_setDemodMode", _f, [_vp, _i]),
     ("rdsp_engine_setMute", _i, [_vp, _i]),
     ("rdsp_engine_update", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    ("rdsp_engine_set_sources", _i, [_vp, _i, C.POINTER(C.c_int)]),
+    ("rdsp_engine_tune", _i, [_vp, _i, _i, _f64p]),
+    ("rdsp_engine_update_sources", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    ("rdsp_engine_tune_table", _f32p, []),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

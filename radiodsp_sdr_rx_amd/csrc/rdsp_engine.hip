@@ -54,6 +54,7 @@
 #include "rdsp_engine_laws.h"
 #include "rdsp_host.h"
 #include "rdsp_sync.h"
+#include "rdsp_tune.h"
 
 namespace {
 
@@ -723,6 +724,16 @@ struct rdsp_engine {
   std::vector<EngSettings> grp; /* at least one */
   std::vector<int> first;       /* first channel of each group, ascending; first[0] = 0 */
   int sel = -1;                 /* the group the setters address; -1: all of them */
+  /* shared IQ streams (rdsp_engine_set_sources / tune / update_sources); the device side exists from the first
+   * set_sources on: phase accumulators and steps per channel, the source map, the tuned rows, the phasor table */
+  uint32_t *d_phase = nullptr, *d_dphi = nullptr, *d_tuned = nullptr;
+  int *d_source_of = nullptr, *d_order = nullptr;
+  float4 *d_tune_tab = nullptr;
+  std::vector<double> station;  /* per channel, Hz from its stream's centre (0 until tuned) */
+  std::vector<float> tune_to;   /* per group: the tuning offset d_dphi was computed with */
+  std::vector<uint32_t> dphi_stage; /* the host side of the last d_dphi upload; reused once dphi_ev has passed */
+  hipEvent_t dphi_ev = nullptr;
+  bool dphi_stale = true;
 };
 
 namespace {
@@ -893,6 +904,7 @@ int rdsp_engine_set_groups(rdsp_engine_t *e, int n_groups, const int *first_chan
   e->grp.swap(grp);
   e->first.assign(first_channel, first_channel + n_groups);
   e->sel = -1;
+  e->dphi_stale = true; /* a channel's step follows its new group's mode */
   return RDSP_OK;
 }
 int rdsp_engine_groups(const rdsp_engine_t *e) { return e ? (int)e->grp.size() : 0; }
@@ -907,6 +919,9 @@ void rdsp_engine_destroy(rdsp_engine_t *e) {
   (void)hipSetDevice(e->device);
   for (float *p : {e->d_st, e->d_ring_i, e->d_ring_q, e->d_audio, e->d_nb, e->d_als, e->d_tab})
     if (p) (void)hipFree(p);
+  for (void *p : {(void *)e->d_phase, (void *)e->d_dphi, (void *)e->d_tuned, (void *)e->d_source_of, (void *)e->d_order, (void *)e->d_tune_tab})
+    if (p) (void)hipFree(p);
+  if (e->dphi_ev) (void)hipEventDestroy(e->dphi_ev);
   delete e;
 }
 
@@ -929,6 +944,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess) err = hipMemsetAsync(e->d_ring_i, 0, n * e->ring_size * 4, s);
   if (err == hipSuccess) err = hipMemsetAsync(e->d_ring_q, 0, n * e->ring_size * 4, s);
   if (err == hipSuccess) err = hipMemsetAsync(e->d_als, 0, n * ALS_WORDS * 4, s);
+  if (err == hipSuccess && e->d_phase) err = hipMemsetAsync(e->d_phase, 0, n * 4, s); /* the stations are settings: kept */
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -1055,12 +1071,141 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
   return RDSP_OK;
 }
 
+/* ---- shared IQ streams: receivers tuned to stations inside source rows ----------------------------------------------------
+ * rdsp_engine_update_sources runs a tuning pass (rdsp_engine_tune.hip, arithmetic in rdsp_tune.h) that writes each
+ * receiver's row -- its source row times e^{+j phi}, phi advancing by round((TuningOffset - station) 2^32 / 44100) per
+ * sample -- into d_tuned, then the engine's own launches of rdsp_engine_update on those rows.  The steps are computed here
+ * from each channel's station and its group's current mode; they are uploaded only when one of them changed. */
+namespace {
+hipError_t upload_dphi(rdsp_engine_t *e, hipStream_t s) {
+  bool changed = e->dphi_stale || e->tune_to.size() != e->grp.size();
+  for (size_t g = 0; !changed && g < e->grp.size(); g++) changed = e->tune_to[g] != e->grp[g].tuning_offset;
+  if (!changed) return hipSuccess;
+  hipError_t err = hipEventSynchronize(e->dphi_ev); /* the last upload has left dphi_stage */
+  e->tune_to.resize(e->grp.size());
+  for (size_t g = 0; g < e->grp.size(); g++) {
+    const int c1 = g + 1 < e->grp.size() ? e->first[g + 1] : e->n_channels;
+    for (int c = e->first[g]; c < c1; c++) e->dphi_stage[(size_t)c] = rdsp_tune::tune_dphi(e->grp[g].tuning_offset, e->station[(size_t)c]);
+    e->tune_to[g] = e->grp[g].tuning_offset;
+  }
+  if (err == hipSuccess) err = hipMemcpyAsync(e->d_dphi, e->dphi_stage.data(), e->dphi_stage.size() * 4, hipMemcpyHostToDevice, s);
+  if (err == hipSuccess) err = hipEventRecord(e->dphi_ev, s);
+  if (err == hipSuccess) e->dphi_stale = false;
+  return err;
+}
+}  // namespace
+
+const float *rdsp_engine_tune_table(void) {
+  static const std::vector<float4> tab = [] {
+    std::vector<float4> t(rdsp_tune::TUNE_N);
+    rdsp_tune::tune_table(t.data());
+    return t;
+  }();
+  return (const float *)tab.data();
+}
+
+int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_of_channel) {
+  if (!e || n_sources < 1 || !source_of_channel) {
+    rdsp_set_error("rdsp_engine_set_sources: bad argument (n_sources %d)", n_sources);
+    return RDSP_ERR_INVALID;
+  }
+  for (int c = 0; c < e->n_channels; c++)
+    if (source_of_channel[c] < 0 || source_of_channel[c] >= n_sources) {
+      rdsp_set_error("rdsp_engine_set_sources: channel %d listens to source %d of %d", c, source_of_channel[c], n_sources);
+      return RDSP_ERR_INVALID;
+    }
+  const size_t n = (size_t)e->n_channels;
+  std::vector<int> order(n);
+  for (size_t c = 0; c < n; c++) order[c] = (int)c;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return source_of_channel[a] < source_of_channel[b]; });
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess && e->d_tuned) err = hipDeviceSynchronize(); /* queued passes may still read the old map */
+  if (err == hipSuccess && !e->d_tuned) {
+    err = hipMalloc((void **)&e->d_phase, n * 4);
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_dphi, n * 4);
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_source_of, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_order, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_tune_tab, rdsp_tune::TUNE_N * sizeof(float4));
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_tuned, n * (size_t)e->max_blocks * BS * 4);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->dphi_ev, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipEventRecord(e->dphi_ev, nullptr);
+    if (err == hipSuccess) err = hipMemset(e->d_phase, 0, n * 4);
+    if (err == hipSuccess) err = hipMemcpy(e->d_tune_tab, rdsp_engine_tune_table(), rdsp_tune::TUNE_N * sizeof(float4), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+      for (void **p : {(void **)&e->d_phase, (void **)&e->d_dphi, (void **)&e->d_source_of, (void **)&e->d_order, (void **)&e->d_tune_tab, (void **)&e->d_tuned})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+      if (e->dphi_ev) { (void)hipEventDestroy(e->dphi_ev); e->dphi_ev = nullptr; }
+      rdsp_set_error("rdsp_engine_set_sources: %s", hipGetErrorString(err));
+      return RDSP_ERR_NOMEM;
+    }
+    if (e->station.empty()) e->station.assign(n, 0.0);
+    e->dphi_stage.assign(n, 0u);
+  }
+  if (err == hipSuccess) err = hipMemcpy(e->d_source_of, source_of_channel, n * sizeof(int), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(e->d_order, order.data(), n * sizeof(int), hipMemcpyHostToDevice);
+  if (err != hipSuccess) return engine_fail("rdsp_engine_set_sources", err);
+  e->dphi_stale = true;
+  return RDSP_OK;
+}
+
+int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const double *station_hz) {
+  if (!e || !station_hz || first_channel < 0 || n_channels < 1 || n_channels > e->n_channels - first_channel) {
+    rdsp_set_error("rdsp_engine_tune: bad argument (channels %d .. %d of %d)", first_channel, first_channel + n_channels - 1, e ? e->n_channels : 0);
+    return RDSP_ERR_INVALID;
+  }
+  for (int k = 0; k < n_channels; k++)
+    if (!(fabs(station_hz[k]) < rdsp_tune::TUNE_MAX_HZ)) {
+      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], rdsp_tune::TUNE_MAX_HZ);
+      return RDSP_ERR_INVALID;
+    }
+  if (e->station.empty()) e->station.assign((size_t)e->n_channels, 0.0);
+  std::copy(station_hz, station_hz + n_channels, e->station.begin() + first_channel);
+  e->dphi_stale = true;
+  return RDSP_OK;
+}
+
+int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
+  if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS || src_stride % 4 != 0 ||
+      ((uintptr_t)d_src & 15) != 0 || out_stride < (size_t)n_blocks * BS) {
+    rdsp_set_error("rdsp_engine_update_sources: bad argument (n_blocks %d of at most %d; source rows 16-byte aligned, a multiple of 4 "
+                   "pairs apart and at least n_blocks * 128 long)", n_blocks, e ? e->max_blocks : 0);
+    return RDSP_ERR_INVALID;
+  }
+  if (!e->d_tuned) {
+    rdsp_set_error("rdsp_engine_update_sources: no sources; call rdsp_engine_set_sources first");
+    return RDSP_ERR_NOT_READY;
+  }
+  if (!e->tables) {
+    rdsp_set_error("rdsp_engine_update_sources: the engine's coefficient tables are not loaded (rdsp_engine_load_tables)");
+    return RDSP_ERR_NOT_READY;
+  }
+  if (n_blocks == 0) return RDSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = upload_dphi(e, s);
+  if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources", err);
+  rdsp_tune::TuneParams p;
+  p.src = (const uint32_t *)d_src; p.src_stride = src_stride;
+  p.dst = e->d_tuned; p.dst_stride = (size_t)e->max_blocks * BS;
+  p.order = e->d_order; p.source_of = e->d_source_of;
+  p.phase = e->d_phase; p.dphi = e->d_dphi; p.tab = e->d_tune_tab;
+  p.n_channels = e->n_channels;
+  p.cpw = std::min(rdsp_tune::TUNE_MAX_CPW, std::max(1, e->n_channels / 1024)); /* about a thousand workgroups or more */
+  p.n_samples = (uint32_t)n_blocks * BS;
+  err = rdsp_engine_tune_launch(p, s);
+  if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources launch", err);
+  return rdsp_engine_update(e, (const int16_t *)e->d_tuned, p.dst_stride, n_blocks, d_lr, out_stride, stream);
+}
+
 /* ---- the signal state of a channel range as data: resume, or move receivers between objects / GPUs ---------------------
- * Blob = header {magic, version, n_channels} + per channel: the 96 state words, the last 512 samples of both lines of the
- * side-band network in time order (whatever the ring's size and position here or there), the blanker's lines, the ALS
- * filter's line and taps.  Settings are not part of it (they belong to the group the channels land in). */
+ * Blob = header {magic, version, n_channels, flags} + per channel: the 96 state words, the last 512 samples of both lines
+ * of the side-band network in time order (whatever the ring's size and position here or there), the blanker's lines, the
+ * ALS filter's line and taps.  Settings are not part of it (they belong to the group the channels land in).  An engine with
+ * sources (rdsp_engine_set_sources) sets flag STATE_PHASES and appends each channel's tuning phase accumulator; the blob
+ * of any other engine is as it was before sources existed (flags 0, nothing appended). */
 namespace {
 constexpr uint32_t STATE_MAGIC = 0x45534452u; /* "RDSE" */
+constexpr uint32_t STATE_PHASES = 1u;
 constexpr size_t STATE_CH_WORDS = NF + 1024 + NB_WORDS + ALS_WORDS;
 uint32_t pos_of_channel(const rdsp_engine_t *e, int ch) {
   size_t g = 0;
@@ -1069,7 +1214,7 @@ uint32_t pos_of_channel(const rdsp_engine_t *e, int ch) {
 }
 }  // namespace
 size_t rdsp_engine_state_bytes(const rdsp_engine_t *e, int n_channels) {
-  return (e && n_channels > 0) ? 16 + (size_t)n_channels * STATE_CH_WORDS * 4 : 0;
+  return (e && n_channels > 0) ? 16 + (size_t)n_channels * (STATE_CH_WORDS + (e->d_phase ? 1 : 0)) * 4 : 0;
 }
 int rdsp_engine_save_state(rdsp_engine_t *e, int first_channel, int n_channels, void *host_buf, size_t bytes, void *stream) {
   if (!e || !host_buf || first_channel < 0 || n_channels < 1 || first_channel + n_channels > e->n_channels ||
@@ -1081,6 +1226,8 @@ int rdsp_engine_save_state(rdsp_engine_t *e, int first_channel, int n_channels, 
   hipError_t err = hipSetDevice(e->device);
   const size_t n = (size_t)n_channels, c0 = (size_t)first_channel, R = e->ring_size;
   std::vector<float> st(n * NF), ri(n * R), rq(n * R), nb(n * NB_WORDS), als(n * ALS_WORDS);
+  std::vector<uint32_t> ph(e->d_phase ? n : 0);
+  if (err == hipSuccess && e->d_phase) err = hipMemcpyAsync(ph.data(), e->d_phase + c0, n * 4, hipMemcpyDeviceToHost, s);
   if (err == hipSuccess) err = hipMemcpyAsync(st.data(), e->d_st + c0 * NF, st.size() * 4, hipMemcpyDeviceToHost, s);
   if (err == hipSuccess) err = hipMemcpyAsync(ri.data(), e->d_ring_i + c0 * R, ri.size() * 4, hipMemcpyDeviceToHost, s);
   if (err == hipSuccess) err = hipMemcpyAsync(rq.data(), e->d_ring_q + c0 * R, rq.size() * 4, hipMemcpyDeviceToHost, s);
@@ -1089,7 +1236,7 @@ int rdsp_engine_save_state(rdsp_engine_t *e, int first_channel, int n_channels, 
   if (err == hipSuccess) err = hipStreamSynchronize(s);
   if (err != hipSuccess) return engine_fail("rdsp_engine_save_state", err);
   uint32_t *hdr = (uint32_t *)host_buf;
-  hdr[0] = STATE_MAGIC; hdr[1] = 1; hdr[2] = (uint32_t)n_channels; hdr[3] = 0;
+  hdr[0] = STATE_MAGIC; hdr[1] = 1; hdr[2] = (uint32_t)n_channels; hdr[3] = e->d_phase ? STATE_PHASES : 0;
   float *w = (float *)(hdr + 4);
   for (size_t c = 0; c < n; c++, w += STATE_CH_WORDS) {
     const uint32_t pos = pos_of_channel(e, first_channel + (int)c);
@@ -1101,18 +1248,24 @@ int rdsp_engine_save_state(rdsp_engine_t *e, int first_channel, int n_channels, 
     memcpy(w + NF + 1024, &nb[c * NB_WORDS], NB_WORDS * 4);
     memcpy(w + NF + 1024 + NB_WORDS, &als[c * ALS_WORDS], ALS_WORDS * 4);
   }
+  if (e->d_phase) memcpy(w, ph.data(), n * 4); /* after the last channel's words */
   return RDSP_OK;
 }
 int rdsp_engine_load_state(rdsp_engine_t *e, int first_channel, const void *host_buf, size_t bytes, void *stream) {
   const uint32_t *hdr = (const uint32_t *)host_buf;
-  if (!e || !host_buf || bytes < 16 || hdr[0] != STATE_MAGIC || hdr[1] != 1) {
+  if (!e || !host_buf || bytes < 16 || hdr[0] != STATE_MAGIC || hdr[1] != 1 || (hdr[3] & ~STATE_PHASES) != 0) {
     rdsp_set_error("rdsp_engine_load_state: not an engine state blob of this version");
     return RDSP_ERR_INVALID;
   }
+  const bool phases = (hdr[3] & STATE_PHASES) != 0;
   const size_t n = hdr[2], c0 = (size_t)first_channel, R = e->ring_size;
-  if (first_channel < 0 || n < 1 || c0 + n > (size_t)e->n_channels || bytes < 16 + n * STATE_CH_WORDS * 4) {
+  if (first_channel < 0 || n < 1 || c0 + n > (size_t)e->n_channels || bytes < 16 + n * (STATE_CH_WORDS + (phases ? 1 : 0)) * 4) {
     rdsp_set_error("rdsp_engine_load_state: %zu channels at %d do not fit", n, first_channel);
     return RDSP_ERR_INVALID;
+  }
+  if (phases && !e->d_phase) {
+    rdsp_set_error("rdsp_engine_load_state: the blob carries tuning phases; call rdsp_engine_set_sources first");
+    return RDSP_ERR_NOT_READY;
   }
   std::vector<float> st(n * NF), ri(n * R, 0.0f), rq(n * R, 0.0f), nb(n * NB_WORDS), als(n * ALS_WORDS);
   const float *w = (const float *)(hdr + 4);
@@ -1126,8 +1279,11 @@ int rdsp_engine_load_state(rdsp_engine_t *e, int first_channel, const void *host
     memcpy(&nb[c * NB_WORDS], w + NF + 1024, NB_WORDS * 4);
     memcpy(&als[c * ALS_WORDS], w + NF + 1024 + NB_WORDS, ALS_WORDS * 4);
   }
+  std::vector<uint32_t> ph(e->d_phase ? n : 0, 0u); /* a blob without phases comes from an engine that never tuned: 0 */
+  if (phases) memcpy(ph.data(), w, n * 4);
   hipStream_t s = (hipStream_t)stream;
   hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess && e->d_phase) err = hipMemcpyAsync(e->d_phase + c0, ph.data(), n * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipMemcpyAsync(e->d_st + c0 * NF, st.data(), st.size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipMemcpyAsync(e->d_ring_i + c0 * R, ri.data(), ri.size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipMemcpyAsync(e->d_ring_q + c0 * R, rq.data(), rq.size() * 4, hipMemcpyHostToDevice, s);

@@ -1,0 +1,63 @@
+/*
+ * rdsp_engine_tune.hip -- the tuning pass of rdsp_engine_update_sources (include/rdsp.h): every receiver's int16 row is
+ * its source row times e^{+j phi[n]}, written to the engine's own [ch][max_blocks * 128] buffer, which the engine's
+ * front kernels then read as they read a caller's rows.  The arithmetic is rdsp_tune.h's.
+ *
+ * A workgroup takes cpw receivers that are neighbours in `order` (receivers sorted by source, so a source row is read by
+ * workgroups dispatched together and comes from the caches, not HBM), reads their phases and steps into LDS with the
+ * phasor table, and streams each row in 16-byte words: four pairs a lane, phases in closed form ph0 + t dphi.  The phase
+ * words are read before the one barrier and written after the last row, by the lanes that read them.
+ *
+ * Compiled with -ffp-contract=off: every fused operation is an fmaf.
+ */
+#include <hip/hip_runtime.h>
+
+#include "rdsp_tune.h"
+
+using namespace rdsp_tune;
+
+namespace {
+
+__global__ __launch_bounds__(TUNE_THREADS) void rdsp_engine_tune_kernel(TuneParams p) {
+  __shared__ float4 tab[TUNE_N];
+  __shared__ int ch_of[TUNE_MAX_CPW], src_of[TUNE_MAX_CPW];
+  __shared__ uint32_t ph0_of[TUNE_MAX_CPW], dphi_of[TUNE_MAX_CPW];
+  const int tid = threadIdx.x;
+  for (int k = tid; k < TUNE_N; k += TUNE_THREADS) tab[k] = p.tab[k];
+  const int i0 = blockIdx.x * p.cpw;
+  if (tid < p.cpw) {
+    const int i = i0 + tid;
+    const int ch = i < p.n_channels ? p.order[i] : -1;
+    ch_of[tid] = ch;
+    if (ch >= 0) { src_of[tid] = p.source_of[ch]; ph0_of[tid] = p.phase[ch]; dphi_of[tid] = p.dphi[ch]; }
+  }
+  __syncthreads();
+  for (int k = 0; k < p.cpw; k++) {
+    const int ch = ch_of[k];
+    if (ch < 0) break;
+    const uint4 *in = (const uint4 *)(p.src + (size_t)src_of[k] * p.src_stride);
+    uint4 *out = (uint4 *)(p.dst + (size_t)ch * p.dst_stride);
+    const uint32_t ph0 = ph0_of[k], dphi = dphi_of[k];
+    const uint32_t n4 = p.n_samples >> 2;
+#pragma unroll 2
+    for (uint32_t v = (uint32_t)tid; v < n4; v += TUNE_THREADS) {
+      const uint4 w = in[v];
+      const uint32_t ph = tune_phase(ph0, dphi, 4u * v);
+      uint4 r;
+      r.x = tune_pair(w.x, tune_phasor(tab, ph));
+      r.y = tune_pair(w.y, tune_phasor(tab, ph + dphi));
+      r.z = tune_pair(w.z, tune_phasor(tab, ph + 2u * dphi));
+      r.w = tune_pair(w.w, tune_phasor(tab, ph + 3u * dphi));
+      out[v] = r;
+    }
+  }
+  if (tid < p.cpw && ch_of[tid] >= 0) p.phase[ch_of[tid]] = tune_phase(ph0_of[tid], dphi_of[tid], p.n_samples);
+}
+
+}  // namespace
+
+hipError_t rdsp_engine_tune_launch(const TuneParams &p, hipStream_t s) {
+  const unsigned grid = (unsigned)((p.n_channels + p.cpw - 1) / p.cpw);
+  hipLaunchKernelGGL(rdsp_engine_tune_kernel, dim3(grid), dim3(TUNE_THREADS), 0, s, p);
+  return hipGetLastError();
+}

@@ -56,6 +56,31 @@ class Engine:
         check(self.lib.rdsp_engine_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, C.c_void_p(s)))
         return out
 
+    def set_sources(self, n_sources, source_of_channel):
+        """receiver ch listens to source row source_of_channel[ch] of the rows update_sources() takes"""
+        assert len(source_of_channel) == self.n_channels
+        a = (C.c_int * self.n_channels)(*[int(x) for x in source_of_channel])
+        check(self.lib.rdsp_engine_set_sources(self.h, int(n_sources), a))
+        self.n_sources = int(n_sources)
+
+    def tune(self, first_channel, station_hz):
+        """receivers first_channel ... get the stations station_hz (Hz from their source stream's centre, |f| < 22050)"""
+        st = np.ascontiguousarray(np.atleast_1d(station_hz), np.float64)
+        check(self.lib.rdsp_engine_tune(self.h, int(first_channel), st.size, st.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def update_sources(self, d_src, out=None, stream=None):
+        """d_src: torch int16 [n_sources, n, 2] on the engine's device, n a multiple of 128 -> int16 [n_channels, n, 2]:
+        every receiver tuned to its station in its source row, then update()"""
+        import torch
+        nsrc, n, two = d_src.shape
+        assert two == 2 and n % 128 == 0 and d_src.dtype == torch.int16 and d_src.is_contiguous()
+        assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
+        if out is None:
+            out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(self.lib.rdsp_engine_update_sources(self.h, d_src.data_ptr(), n, n // 128, out.data_ptr(), n, C.c_void_p(s)))
+        return out
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -85,6 +110,10 @@ class Engine:
 
     def sine_table(self):
         return np.ctypeslib.as_array(self.lib.rdsp_engine_sine_table(self.h), (257,)).copy()
+
+    def tune_table(self):
+        """the tuning pass's phasor table: [1024][4] = cos, sin of 2 pi k / 1024, steps to entry k + 1"""
+        return np.ctypeslib.as_array(self.lib.rdsp_engine_tune_table(), (1024, 4)).copy()
 
     def reset(self):
         check(self.lib.rdsp_engine_reset(self.h, None))
