@@ -750,6 +750,34 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
 int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr,
                                size_t out_stride, void *stream);
 const float *rdsp_engine_tune_table(void);
+/* Wide-band sources: rows at D x 44 100 Hz, D an integer 1 ... 64 (up to 2.8224 MHz), one D per engine.  The pass becomes a
+ * digital down-converter: shift the station to the engine's IF, low-pass, decimate by D to 44 100 Hz.
+ * - rdsp_engine_set_source_decimation(e, D, gain), after rdsp_engine_set_sources (RDSP_ERR_NOT_READY before).  It takes no
+ *   stream and waits for everything queued on the engine's device.  D = 1 (the state at create) is the tuning pass above,
+ *   no filter, gain unused.  For D > 1 output sample m of receiver ch, x its source row with the pairs of earlier calls
+ *   before it:
+ *     y[m] = sat16(rne(e^{+j phi_m} sum_{k < T} g_k x[(m + 1) D - 1 - k])),  g_k = h_k e^{-j 2 pi k dphi / 2^32},  T = 16 D,
+ *     phi_{m + 1} = phi_m + D dphi,  dphi = round((TuningOffset - station_hz) 2^32 / (D 44100)), half away from zero:
+ *   the prototype low-pass h translated onto the station, then the rotation to the IF; the window of output m ends at the
+ *   newest of its D source samples, so the filter delays by (T - 1) / 2 source samples.  The phasors are the table's, the
+ *   rotation, rounding and saturation the tuning pass's; the sum is one chain of fmaf over k ascending (csrc/rdsp_tune.h).
+ * - h (a design of this build, not the reference's): a sinc with its cutoff at 22 050 Hz under a Kaiser window, beta = 9,
+ *   16 D taps, normalised to sum 1, times gain (> 0, finite), rounded to float.  For every D in 2 ... 64: ripple <= 0.00041 dB
+ *   for |f| <= 12 000 Hz, >= 90.2 dB down from 32 100 Hz on (all that folds onto |f| <= 12 000 Hz), sum |h| <= 1.65.  The
+ *   gain is folded into h because a station in a wide band sits far below full scale: requantising to int16 at unit gain
+ *   would throw away the decimation's processing gain.  rdsp_engine_ddc_taps writes the 16 D taps; it needs no GPU.
+ * - Per channel the state stays the one phase, with the rules above (a retune re-centres the filter at once, phase
+ *   continuous).  Per SOURCE the engine keeps the last 15 D pairs of each row after every call: zero at create, after
+ *   rdsp_engine_reset, and when D or n_sources changes.  It is not part of a channel's blob: a moved receiver continues bit
+ *   for bit when both objects heard the same source stream.
+ * - With D set: |station_hz| < D x 22 050 in rdsp_engine_tune; source rows of rdsp_engine_update_sources are n_blocks x
+ *   128 x D pairs (src_stride at least that); d_lr, out_stride and max_blocks count 44 100 Hz samples as before.
+ * - Refused with nothing changed (RDSP_ERR_INVALID): D outside 1 ... 64, gain not above 0 or not finite, a channel already
+ *   tuned to |f| >= D x 22 050.
+ * - Out of scope: rational rate changes (the 48 kHz family) and decimation in several stages. */
+int rdsp_engine_set_source_decimation(rdsp_engine_t *e, int D, float gain);
+int rdsp_engine_source_decimation(const rdsp_engine_t *e);
+int rdsp_engine_ddc_taps(int D, float gain, float *out /* [16 D] */);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -286,6 +286,9 @@ SYMBOLS = [
     ("rdsp_engine_tune", _i, [_vp, _i, _i, _f64p]),
     ("rdsp_engine_update_sources", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     ("rdsp_engine_tune_table", _f32p, []),
+    ("rdsp_engine_set_source_decimation", _i, [_vp, _i, C.c_float]),
+    ("rdsp_engine_source_decimation", _i, [_vp]),
+    ("rdsp_engine_ddc_taps", _i, [_i, C.c_float, _f32p]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

@@ -49,6 +49,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "rdsp_engine_laws.h"
@@ -734,6 +735,14 @@ struct rdsp_engine {
   std::vector<uint32_t> dphi_stage; /* the host side of the last d_dphi upload; reused once dphi_ev has passed */
   hipEvent_t dphi_ev = nullptr;
   bool dphi_stale = true;
+  /* sources at ddc_D x 44 100 Hz (rdsp_engine_set_source_decimation): the workgroup list of the decimating pass (from the
+   * map, whatever D is); for D > 1 the prototype's taps, every receiver's translated taps, and per SOURCE the last 15 D pairs */
+  int n_sources = 0, ddc_D = 1, n_wg = 0;
+  float ddc_gain = 1.0f;
+  int *d_wg_first = nullptr, *d_wg_count = nullptr;
+  float *d_ddc_h = nullptr;
+  float2 *d_ddc_g = nullptr;
+  uint32_t *d_hist = nullptr;
 };
 
 namespace {
@@ -919,7 +928,8 @@ void rdsp_engine_destroy(rdsp_engine_t *e) {
   (void)hipSetDevice(e->device);
   for (float *p : {e->d_st, e->d_ring_i, e->d_ring_q, e->d_audio, e->d_nb, e->d_als, e->d_tab})
     if (p) (void)hipFree(p);
-  for (void *p : {(void *)e->d_phase, (void *)e->d_dphi, (void *)e->d_tuned, (void *)e->d_source_of, (void *)e->d_order, (void *)e->d_tune_tab})
+  for (void *p : {(void *)e->d_phase, (void *)e->d_dphi, (void *)e->d_tuned, (void *)e->d_source_of, (void *)e->d_order, (void *)e->d_tune_tab,
+                  (void *)e->d_wg_first, (void *)e->d_wg_count, (void *)e->d_ddc_h, (void *)e->d_ddc_g, (void *)e->d_hist})
     if (p) (void)hipFree(p);
   if (e->dphi_ev) (void)hipEventDestroy(e->dphi_ev);
   delete e;
@@ -945,6 +955,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess) err = hipMemsetAsync(e->d_ring_q, 0, n * e->ring_size * 4, s);
   if (err == hipSuccess) err = hipMemsetAsync(e->d_als, 0, n * ALS_WORDS * 4, s);
   if (err == hipSuccess && e->d_phase) err = hipMemsetAsync(e->d_phase, 0, n * 4, s); /* the stations are settings: kept */
+  if (err == hipSuccess && e->d_hist) err = hipMemsetAsync(e->d_hist, 0, (size_t)e->n_sources * rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D * 4, s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -1085,13 +1096,46 @@ hipError_t upload_dphi(rdsp_engine_t *e, hipStream_t s) {
   e->tune_to.resize(e->grp.size());
   for (size_t g = 0; g < e->grp.size(); g++) {
     const int c1 = g + 1 < e->grp.size() ? e->first[g + 1] : e->n_channels;
-    for (int c = e->first[g]; c < c1; c++) e->dphi_stage[(size_t)c] = rdsp_tune::tune_dphi(e->grp[g].tuning_offset, e->station[(size_t)c]);
+    for (int c = e->first[g]; c < c1; c++) e->dphi_stage[(size_t)c] = rdsp_tune::ddc_dphi(e->grp[g].tuning_offset, e->station[(size_t)c], e->ddc_D);
     e->tune_to[g] = e->grp[g].tuning_offset;
   }
   if (err == hipSuccess) err = hipMemcpyAsync(e->d_dphi, e->dphi_stage.data(), e->dphi_stage.size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipEventRecord(e->dphi_ev, s);
   if (err == hipSuccess) e->dphi_stale = false;
   return err;
+}
+/* the device side of a decimation D on n_sources rows: the history is new (zero) when either changed, the taps always.
+ * The caller has waited for queued work. */
+hipError_t ddc_setup(rdsp_engine_t *e, int D, float gain, int n_sources) {
+  hipError_t err = hipSuccess;
+  if (D != e->ddc_D || n_sources != e->n_sources) {
+    for (void **p : {(void **)&e->d_ddc_h, (void **)&e->d_ddc_g, (void **)&e->d_hist})
+      if (*p) { (void)hipFree(*p); *p = nullptr; }
+    e->ddc_D = 1; /* until everything below exists */
+    e->n_sources = n_sources;
+    if (D > 1) {
+      const size_t T = (size_t)rdsp_tune::DDC_TAPS_PER_PHASE * D, keep = (size_t)n_sources * rdsp_tune::DDC_HIST_PER_PHASE * D;
+      err = hipMalloc((void **)&e->d_ddc_h, T * 4);
+      if (err == hipSuccess) err = hipMalloc((void **)&e->d_ddc_g, (size_t)e->n_channels * T * sizeof(float2));
+      if (err == hipSuccess) err = hipMalloc((void **)&e->d_hist, keep * 4);
+      if (err == hipSuccess) err = hipMemset(e->d_hist, 0, keep * 4);
+      if (err != hipSuccess) {
+        for (void **p : {(void **)&e->d_ddc_h, (void **)&e->d_ddc_g, (void **)&e->d_hist})
+          if (*p) { (void)hipFree(*p); *p = nullptr; }
+        return err;
+      }
+    }
+  }
+  if (D > 1) {
+    std::vector<float> h((size_t)rdsp_tune::DDC_TAPS_PER_PHASE * D);
+    rdsp_tune::ddc_taps(D, (double)gain, h.data());
+    err = hipMemcpy(e->d_ddc_h, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+    if (err != hipSuccess) return err;
+  }
+  e->ddc_D = D;
+  e->ddc_gain = gain;
+  e->dphi_stale = true; /* the step is per source sample */
+  return hipSuccess;
 }
 }  // namespace
 
@@ -1118,6 +1162,15 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
   std::vector<int> order(n);
   for (size_t c = 0; c < n; c++) order[c] = (int)c;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return source_of_channel[a] < source_of_channel[b]; });
+  /* the decimating pass's workgroups: runs of at most DDC_RPW receivers of one source, in `order` */
+  std::vector<int> wg_first, wg_count;
+  for (size_t i = 0; i < n;) {
+    size_t j = i + 1;
+    while (j < n && j - i < (size_t)rdsp_tune::DDC_RPW && source_of_channel[order[j]] == source_of_channel[order[i]]) j++;
+    wg_first.push_back((int)i);
+    wg_count.push_back((int)(j - i));
+    i = j;
+  }
   hipError_t err = hipSetDevice(e->device);
   if (err == hipSuccess && e->d_tuned) err = hipDeviceSynchronize(); /* queued passes may still read the old map */
   if (err == hipSuccess && !e->d_tuned) {
@@ -1125,6 +1178,8 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
     if (err == hipSuccess) err = hipMalloc((void **)&e->d_dphi, n * 4);
     if (err == hipSuccess) err = hipMalloc((void **)&e->d_source_of, n * sizeof(int));
     if (err == hipSuccess) err = hipMalloc((void **)&e->d_order, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_wg_first, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_wg_count, n * sizeof(int));
     if (err == hipSuccess) err = hipMalloc((void **)&e->d_tune_tab, rdsp_tune::TUNE_N * sizeof(float4));
     if (err == hipSuccess) err = hipMalloc((void **)&e->d_tuned, n * (size_t)e->max_blocks * BS * 4);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&e->dphi_ev, hipEventDisableTiming);
@@ -1132,7 +1187,8 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
     if (err == hipSuccess) err = hipMemset(e->d_phase, 0, n * 4);
     if (err == hipSuccess) err = hipMemcpy(e->d_tune_tab, rdsp_engine_tune_table(), rdsp_tune::TUNE_N * sizeof(float4), hipMemcpyHostToDevice);
     if (err != hipSuccess) {
-      for (void **p : {(void **)&e->d_phase, (void **)&e->d_dphi, (void **)&e->d_source_of, (void **)&e->d_order, (void **)&e->d_tune_tab, (void **)&e->d_tuned})
+      for (void **p : {(void **)&e->d_phase, (void **)&e->d_dphi, (void **)&e->d_source_of, (void **)&e->d_order, (void **)&e->d_tune_tab, (void **)&e->d_tuned,
+                       (void **)&e->d_wg_first, (void **)&e->d_wg_count})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
       if (e->dphi_ev) { (void)hipEventDestroy(e->dphi_ev); e->dphi_ev = nullptr; }
       rdsp_set_error("rdsp_engine_set_sources: %s", hipGetErrorString(err));
@@ -1143,8 +1199,45 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
   }
   if (err == hipSuccess) err = hipMemcpy(e->d_source_of, source_of_channel, n * sizeof(int), hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(e->d_order, order.data(), n * sizeof(int), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(e->d_wg_first, wg_first.data(), wg_first.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(e->d_wg_count, wg_count.data(), wg_count.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = ddc_setup(e, e->ddc_D, e->ddc_gain, n_sources); /* another number of rows: their histories start at zero */
   if (err != hipSuccess) return engine_fail("rdsp_engine_set_sources", err);
+  e->n_wg = (int)wg_first.size();
   e->dphi_stale = true;
+  return RDSP_OK;
+}
+
+int rdsp_engine_set_source_decimation(rdsp_engine_t *e, int D, float gain) {
+  if (!e || D < 1 || D > rdsp_tune::DDC_MAX_D || !(gain > 0.0f) || !std::isfinite(gain)) {
+    rdsp_set_error("rdsp_engine_set_source_decimation: bad argument (D %d of 1 .. %d, gain %g must be finite and above 0)", D, rdsp_tune::DDC_MAX_D, (double)gain);
+    return RDSP_ERR_INVALID;
+  }
+  if (!e->d_tuned) {
+    rdsp_set_error("rdsp_engine_set_source_decimation: no sources; call rdsp_engine_set_sources first");
+    return RDSP_ERR_NOT_READY;
+  }
+  for (size_t c = 0; c < e->station.size(); c++)
+    if (!(fabs(e->station[c]) < (double)D * rdsp_tune::TUNE_MAX_HZ)) {
+      rdsp_set_error("rdsp_engine_set_source_decimation: channel %zu is tuned to %g Hz, outside a source at %d x 44100 Hz", c, e->station[c], D);
+      return RDSP_ERR_INVALID;
+    }
+  if ((uint64_t)e->n_channels * (uint64_t)(rdsp_tune::DDC_TAPS_PER_PHASE * D) > 0xffffffffull) {
+    rdsp_set_error("rdsp_engine_set_source_decimation: %d channels x %d taps do not fit the pass's tap table", e->n_channels, rdsp_tune::DDC_TAPS_PER_PHASE * D);
+    return RDSP_ERR_UNSUPPORTED;
+  }
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = hipDeviceSynchronize(); /* queued passes read the taps and the histories */
+  if (err == hipSuccess) err = ddc_setup(e, D, gain, e->n_sources);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_set_source_decimation", err);
+}
+int rdsp_engine_source_decimation(const rdsp_engine_t *e) { return e ? e->ddc_D : 0; }
+int rdsp_engine_ddc_taps(int D, float gain, float *out) {
+  if (D < 1 || D > rdsp_tune::DDC_MAX_D || !(gain > 0.0f) || !std::isfinite(gain) || !out) {
+    rdsp_set_error("rdsp_engine_ddc_taps: bad argument (D %d of 1 .. %d, gain %g)", D, rdsp_tune::DDC_MAX_D, (double)gain);
+    return RDSP_ERR_INVALID;
+  }
+  rdsp_tune::ddc_taps(D, (double)gain, out);
   return RDSP_OK;
 }
 
@@ -1154,8 +1247,8 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
     return RDSP_ERR_INVALID;
   }
   for (int k = 0; k < n_channels; k++)
-    if (!(fabs(station_hz[k]) < rdsp_tune::TUNE_MAX_HZ)) {
-      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], rdsp_tune::TUNE_MAX_HZ);
+    if (!(fabs(station_hz[k]) < (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ)) {
+      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ);
       return RDSP_ERR_INVALID;
     }
   if (e->station.empty()) e->station.assign((size_t)e->n_channels, 0.0);
@@ -1165,10 +1258,10 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
 }
 
 int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
-  if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS || src_stride % 4 != 0 ||
+  if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS * (size_t)e->ddc_D || src_stride % 4 != 0 ||
       ((uintptr_t)d_src & 15) != 0 || out_stride < (size_t)n_blocks * BS) {
     rdsp_set_error("rdsp_engine_update_sources: bad argument (n_blocks %d of at most %d; source rows 16-byte aligned, a multiple of 4 "
-                   "pairs apart and at least n_blocks * 128 long)", n_blocks, e ? e->max_blocks : 0);
+                   "pairs apart and at least n_blocks * 128 * D long, D = %d)", n_blocks, e ? e->max_blocks : 0, e ? e->ddc_D : 0);
     return RDSP_ERR_INVALID;
   }
   if (!e->d_tuned) {
@@ -1184,6 +1277,21 @@ int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t sr
   hipError_t err = hipSetDevice(e->device);
   if (err == hipSuccess) err = upload_dphi(e, s);
   if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources", err);
+  if (e->ddc_D > 1) { /* tune, low-pass and decimate: rdsp_engine_ddc.hip */
+    rdsp_tune::DdcParams q;
+    q.src = (const uint32_t *)d_src; q.src_stride = src_stride;
+    q.hist = e->d_hist;
+    q.dst = e->d_tuned; q.dst_stride = (size_t)e->max_blocks * BS;
+    q.order = e->d_order; q.source_of = e->d_source_of;
+    q.wg_first = e->d_wg_first; q.wg_count = e->d_wg_count;
+    q.phase = e->d_phase; q.dphi = e->d_dphi; q.tab = e->d_tune_tab;
+    q.h = e->d_ddc_h; q.g = e->d_ddc_g;
+    q.n_channels = e->n_channels; q.n_sources = e->n_sources; q.n_wg = e->n_wg; q.D = e->ddc_D;
+    q.n_out = (uint32_t)n_blocks * BS;
+    err = rdsp_engine_ddc_launch(q, s);
+    if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources launch", err);
+    return rdsp_engine_update(e, (const int16_t *)e->d_tuned, q.dst_stride, n_blocks, d_lr, out_stride, stream);
+  }
   rdsp_tune::TuneParams p;
   p.src = (const uint32_t *)d_src; p.src_stride = src_stride;
   p.dst = e->d_tuned; p.dst_stride = (size_t)e->max_blocks * BS;

@@ -66,10 +66,12 @@ RDSP_HD uint32_t tune_pair(uint32_t w, float2 cs) {
 /* phase of sample t of a call that starts at phase ph0; the accumulator after a call of n samples is tune_phase(ph0, dphi, n) */
 RDSP_HD uint32_t tune_phase(uint32_t ph0, uint32_t dphi, uint32_t t) { return ph0 + t * dphi; }
 
-/* host only: the step per sample that moves a station at station_hz (from the stream's centre) to the engine's IF */
-inline uint32_t tune_dphi(float tuning_offset, double station_hz) {
-  return (uint32_t)(unsigned long long)llround(((double)tuning_offset - station_hz) * 4294967296.0 / TUNE_FS);
+/* host only: the step per source sample that moves a station at station_hz (from the stream's centre) to the engine's IF, the
+ * source at D x 44 100 Hz (rdsp_engine_set_source_decimation below; D = 1 divides by TUNE_FS itself) */
+inline uint32_t ddc_dphi(float tuning_offset, double station_hz, int D) {
+  return (uint32_t)(unsigned long long)llround(((double)tuning_offset - station_hz) * 4294967296.0 / ((double)D * TUNE_FS));
 }
+inline uint32_t tune_dphi(float tuning_offset, double station_hz) { return ddc_dphi(tuning_offset, station_hz, 1); }
 
 /* the pass's arguments: receivers are visited in `order` (grouped by source); cpw receivers per workgroup */
 struct TuneParams {
@@ -84,8 +86,116 @@ struct TuneParams {
 constexpr int TUNE_THREADS = 256;
 constexpr int TUNE_MAX_CPW = 8;
 
+/* ---- sources at D x 44 100 Hz: tune, low-pass and decimate by D (rdsp_engine_set_source_decimation) ---------------------------
+ * Output m of a receiver whose source row is x (pairs before the call included):
+ *   y[m] = sat16(rne(e^{+j phi_m} * sum_{k < T} g_k x[(m + 1) D - 1 - k])),  g_k = h_k e^{-j 2 pi k dphi / 2^32},  T = 16 D,
+ *   phi_{m + 1} = phi_m + D dphi,  dphi = round((TuningOffset - station) 2^32 / (D 44100)).
+ * h is the prototype low-pass below (a design of this build).  The order of the operations, fixed here for the kernel
+ * (rdsp_engine_ddc.hip) and for the host restatement (tests/host/host_ddc_check.cpp): g_k = (h_k c, h_k s), (c, s) =
+ * tune_phasor(-k dphi); ONE serial chain over k = 0 ... T - 1 per component, four fmaf a tap (ddc_mac); the rotation,
+ * rounding and saturation of tune_pair (ddc_rot).  The chain has no tile, register block or call size in it, so neither
+ * has the result. */
+constexpr int DDC_MAX_D = 64;
+constexpr int DDC_TAPS_PER_PHASE = 16;          /* T = 16 D */
+constexpr int DDC_HIST_PER_PHASE = DDC_TAPS_PER_PHASE - 1; /* a source keeps its last 15 D pairs between calls */
+
+/* host only, libm-free (+ - * / sqrt in double, so any host evaluates the same bits): sin(pi r / (2 D)) for 0 <= r <= D */
+inline double ddc_sin_quarter(int r, int D) {
+  const double a = (3.141592653589793 * (double)r) / (2.0 * (double)D), a2 = a * a;
+  double term = a, sum = a;
+  for (int n = 1; n <= 14; n++) {
+    term = -(term * a2) / (double)((2 * n) * (2 * n + 1));
+    sum += term;
+  }
+  return sum;
+}
+/* sin(pi q / (2 D)), q >= 0: the argument is reduced in integers */
+inline double ddc_sin_halfpi(int q, int D) {
+  int r = q % (4 * D);
+  double sign = 1.0;
+  if (r >= 2 * D) { sign = -1.0; r -= 2 * D; }
+  if (r > D) r = 2 * D - r;
+  return sign * ddc_sin_quarter(r, D);
+}
+/* the modified Bessel function I0 by its power series, 40 terms (x <= 9: the 40th is below 1e-40 of the sum) */
+inline double ddc_i0(double x) {
+  const double y = x / 2.0;
+  double term = 1.0, sum = 1.0;
+  for (int n = 1; n <= 40; n++) {
+    const double t = y / (double)n;
+    term = term * (t * t);
+    sum += term;
+  }
+  return sum;
+}
+/* host only: the prototype, T = 16 D taps: a sinc with its cutoff at the output's Nyquist frequency (22 050 Hz) under a
+ * Kaiser window of beta = 9, normalised to sum 1 (summed in tap order), times gain, rounded to float.  Symmetric: every
+ * term is a function of |2 k - (T - 1)|. */
+constexpr double DDC_KAISER_BETA = 9.0;
+inline void ddc_taps(int D, double gain, float *out) {
+  const int T = DDC_TAPS_PER_PHASE * D;
+  double h[DDC_TAPS_PER_PHASE * DDC_MAX_D], sum = 0.0;
+  const double i0b = ddc_i0(DDC_KAISER_BETA);
+  for (int k = 0; k < T; k++) {
+    const int q = 2 * k - (T - 1) < 0 ? (T - 1) - 2 * k : 2 * k - (T - 1); /* odd: the sinc's argument is q / (2 D), never 0 */
+    const double u = (3.141592653589793 * (double)q) / (2.0 * (double)D);
+    const double rho = (double)q / (double)(T - 1);
+    h[k] = (ddc_sin_halfpi(q, D) / u) * (ddc_i0(DDC_KAISER_BETA * sqrt(1.0 - rho * rho)) / i0b);
+  }
+  for (int k = 0; k < T; k++) sum += h[k];
+  for (int k = 0; k < T; k++) out[k] = (float)((h[k] / sum) * gain);
+}
+
+/* tap k of a receiver: the prototype's tap translated onto the station */
+RDSP_HD float2 ddc_tap(const float4 *tab, float h, uint32_t dphi, uint32_t k) {
+  const float2 cs = tune_phasor(tab, 0u - k * dphi);
+  return make_float2(h * cs.x, h * cs.y);
+}
+/* acc += g x, one tap of the chain */
+RDSP_HD void ddc_mac(float &re, float &im, float2 g, float xi, float xq) {
+  re = fmaf(g.x, xi, re);
+  re = fmaf(-g.y, xq, re);
+  im = fmaf(g.x, xq, im);
+  im = fmaf(g.y, xi, im);
+}
+/* the filtered sample times (c + j s), as tune_pair rotates, rounds and saturates */
+RDSP_HD uint32_t ddc_rot(float re, float im, float2 cs) {
+  const float ir = fmaf(re, cs.x, -(im * cs.y));
+  const float qr = fmaf(im, cs.x, re * cs.y);
+  return tune_q16(ir) | tune_q16(qr) << 16;
+}
+/* one output: newest points at x[(m + 1) D - 1] (the T - 1 words before it are read), g at the receiver's T taps */
+RDSP_HD uint32_t ddc_output(const float2 *g, int T, const uint32_t *newest, float2 cs) {
+  float re = 0.0f, im = 0.0f;
+  for (int k = 0; k < T; k++) {
+    const uint32_t w = newest[-k];
+    ddc_mac(re, im, g[k], (float)(int16_t)(uint16_t)(w & 0xffffu), (float)(int16_t)(uint16_t)(w >> 16));
+  }
+  return ddc_rot(re, im, cs);
+}
+
+/* the decimating pass's arguments.  Receivers are visited in `order` (grouped by source); workgroup w of a tile takes the
+ * DDC_RPW-or-fewer receivers order[wg_first[w]] ... of ONE source. */
+constexpr int DDC_THREADS = 256;
+constexpr int DDC_C = 4;                          /* receivers per wave, a register block */
+constexpr int DDC_RPW = DDC_C * (DDC_THREADS / 64); /* receivers per workgroup */
+struct DdcParams {
+  const uint32_t *src; size_t src_stride;   /* [source][t] words I | Q << 16, n_out * D per row */
+  uint32_t *hist;                           /* [source][15 D]: the pairs before the call; rewritten after the pass */
+  uint32_t *dst; size_t dst_stride;         /* [ch][m] */
+  const int *order, *source_of;             /* [n_channels] */
+  const int *wg_first, *wg_count;           /* [n_wg] */
+  uint32_t *phase; const uint32_t *dphi;    /* [n_channels] */
+  const float4 *tab;                        /* [TUNE_N] */
+  const float *h;                           /* [16 D] */
+  float2 *g;                                /* [n_channels][16 D], written by the pass's first kernel */
+  int n_channels, n_sources, n_wg, D;
+  uint32_t n_out;                           /* a multiple of 128 */
+};
+
 }  // namespace rdsp_tune
 
 hipError_t rdsp_engine_tune_launch(const rdsp_tune::TuneParams &p, hipStream_t s);
+hipError_t rdsp_engine_ddc_launch(const rdsp_tune::DdcParams &p, hipStream_t s);
 
 #endif

@@ -63,22 +63,34 @@ class Engine:
         check(self.lib.rdsp_engine_set_sources(self.h, int(n_sources), a))
         self.n_sources = int(n_sources)
 
+    def set_source_decimation(self, D, gain=1.0):
+        """the source rows are at D x 44100 Hz (D = 1 ... 64): update_sources() tunes, low-passes (16 D taps, times gain) and
+        decimates by D.  After set_sources()."""
+        check(self.lib.rdsp_engine_set_source_decimation(self.h, int(D), float(gain)))
+        self.D = int(D)
+
+    def source_decimation(self):
+        return int(self.lib.rdsp_engine_source_decimation(self.h))
+
     def tune(self, first_channel, station_hz):
-        """receivers first_channel ... get the stations station_hz (Hz from their source stream's centre, |f| < 22050)"""
+        """receivers first_channel ... get the stations station_hz (Hz from their source stream's centre, |f| < D x 22050)"""
         st = np.ascontiguousarray(np.atleast_1d(station_hz), np.float64)
         check(self.lib.rdsp_engine_tune(self.h, int(first_channel), st.size, st.ctypes.data_as(C.POINTER(C.c_double))))
 
     def update_sources(self, d_src, out=None, stream=None):
-        """d_src: torch int16 [n_sources, n, 2] on the engine's device, n a multiple of 128 -> int16 [n_channels, n, 2]:
-        every receiver tuned to its station in its source row, then update()"""
+        """d_src: torch int16 [n_sources, n D, 2] on the engine's device, n a multiple of 128, D the source decimation ->
+        int16 [n_channels, n, 2]: every receiver tuned to its station in its source row (and for D > 1 low-passed and
+        decimated), then update()"""
         import torch
-        nsrc, n, two = d_src.shape
-        assert two == 2 and n % 128 == 0 and d_src.dtype == torch.int16 and d_src.is_contiguous()
+        nsrc, n_in, two = d_src.shape
+        D = getattr(self, "D", 1)
+        n = n_in // D
+        assert two == 2 and n_in == n * D and n % 128 == 0 and d_src.dtype == torch.int16 and d_src.is_contiguous()
         assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
         if out is None:
             out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(self.lib.rdsp_engine_update_sources(self.h, d_src.data_ptr(), n, n // 128, out.data_ptr(), n, C.c_void_p(s)))
+        check(self.lib.rdsp_engine_update_sources(self.h, d_src.data_ptr(), n_in, n // 128, out.data_ptr(), n, C.c_void_p(s)))
         return out
 
     def set_groups(self, first_channels):
@@ -117,6 +129,13 @@ class Engine:
 
     def reset(self):
         check(self.lib.rdsp_engine_reset(self.h, None))
+
+
+def ddc_taps(D, gain=1.0):
+    """the prototype low-pass of set_source_decimation(D, gain): 16 D float32 taps (host only, no GPU)"""
+    o = np.zeros(16 * int(D), np.float32)
+    check(load().rdsp_engine_ddc_taps(int(D), float(gain), o.ctypes.data_as(_F32P)))
+    return o
 
 
 def _setter(name):
