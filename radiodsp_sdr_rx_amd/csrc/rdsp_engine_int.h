@@ -1,12 +1,13 @@
 /*
  * rdsp_engine_int.h -- what rdsp_engine_t's kernels (rdsp_engine.hip) and its host object (rdsp_engine_host.hip) share: the
  * kernels' arguments, a channel's state words, the launch of one group's kernels; and what the engine's and the
- * pre-processor's (rdsp_preproc.hip) host sides share: the owner of a device allocation, the HIP error return. */
+ * pre-processor's (rdsp_preproc.hip) host sides share: the owner of a device allocation (rdsp_dev.h), the HIP error return. */
 #ifndef RDSP_ENGINE_INT_H
 #define RDSP_ENGINE_INT_H
 
 #include <hip/hip_runtime.h>
 
+#include "rdsp_dev.h"
 #include "rdsp_host.h"
 #include "rdsp_kernels.h"
 
@@ -37,17 +38,7 @@ struct EngParams {
   float sam_keep, sam_new, sam_hz_per_rad, sam_lock_lo, sam_lock_hi, sam_ga, sam_gb;
 };
 
-/* the one owner of a device allocation: freed with its owner (whose destroy makes the device current first) */
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { release(); }
-  hipError_t alloc(size_t n) { release(); return hipMalloc((void **)&p, n * sizeof(T)); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; }
-  operator T *() const { return p; }
-};
+using rdsp_dev::DevBuf; /* the one owner of a device allocation: freed with its owner (whose destroy makes the device current first) */
 static inline int engine_fail(const char *what, hipError_t err) {
   rdsp_set_error("%s: %s", what, hipGetErrorString(err));
   return RDSP_ERR_HIP;

@@ -1,6 +1,6 @@
 /*
  * rdsp_host.h -- internal host-side declarations shared by rdsp_design.c,
- * rdsp_chain.hip and rdsp_graph.c (the public boundary is include/rdsp.h).
+ * the rdsp_chain*.hip files and rdsp_graph.c (the public boundary is include/rdsp.h).
  */
 #ifndef RDSP_HOST_H
 #define RDSP_HOST_H

@@ -15,7 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* the two error helpers live in rdsp_chain.hip; this build has no HIP objects */
+/* the two error helpers live in rdsp_chain.hip (with the chain object); this build has no HIP objects */
 static char g_err[256];
 void rdsp_set_error(const char *fmt, ...) {
   va_list ap;
