@@ -17,7 +17,17 @@
  * hand-interleaved issue order: tests/micro/not_adopted/rdsp_tail_lookahead.h) was built and measured in round 3
  * and loses: its two extra scans cost more issue slots than the chain it removes.
  * Input blocks are fetched from HBM a whole block ahead (round 3: 0.967 -> 0.912 ms alone).
+ * In pipelined K3 the lone wave shares its CU's LDS with eight front workgroups and issues more LDS instructions
+ * than they do, so LDS work that the result does not need is taken out rather than hidden:
+ *   - the scalars of a 64-step group (step size, B, last E) are not tables in LDS: lane `sub` of the row prepares
+ *     steps 4 sub .. 4 sub + 3, iteration q of the unrolled step loop consumes steps 4 q .. 4 q + 3, so they are read
+ *     out of lane q's registers by row_newbcast:q on the instruction that consumes them (mul_row_lane, fnma_row_lane);
+ *     two register sets, the group that runs and the one being prepared;
+ *   - blocks are not moved in LDS: a ring is four slots [M | S0 | S1 | S2], block b in S(b mod 3), M a mirror of S2
+ *     (tail_body), so [previous | current] is contiguous wherever the block lies.
+ * LDS per workgroup: 4 channels x (4 x 128 ring + 128 outputs + 32 pad) floats = 10.5 KiB (two instances: 18.5 KiB).
  */
+#include <utility>
 #include "rdsp_wave.h"
 
 using namespace rdsp;
@@ -31,6 +41,34 @@ template <int CTRL>
 __device__ __forceinline__ float dpp0_f(float v) {
   return __builtin_bit_cast(
       float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+
+/* The step scalars of NlmsB are consumed out of the registers of the lane that prepared them: x * (g of lane Q
+ * of the row) and fmaf(-x, b of lane Q of the row, acc), each ONE instruction with row_newbcast:Q on the scalar's
+ * operand.  The multiply is left to the compiler, whose DPP combiner folds the broadcast into it (v_mul_f32_dpp).
+ * The fused multiply-add is written out: the compiler takes the three-operand v_fma_f32 for it, which has no DPP
+ * form on gfx950, and moves b across with a v_mov_b32_dpp of its own; v_fmac_f32_dpp with the sign as a source
+ * modifier is the same operation, rounded once.  b was written a whole group of steps earlier (no wait states due
+ * for the DPP read); x and acc are ordinary sources.
+ * (Both multiplies as asm statements too were compiled and counted against this form: the hazard recognizer then
+ * puts a wait state behind every statement whose result the next instruction reads, 61 s_nop more per 64 steps of
+ * the notch instance against 32 here, where it gives x, fresh out of the reduction, the two wait states that only
+ * an operand read through DPP needs.) */
+template <int Q>
+__device__ __forceinline__ float mul_row_lane(float x, float g) {
+  static_assert(Q >= 0 && Q < 16, "a lane of the row");
+  return x * dpp_f<0x150 + Q>(g);
+}
+template <int Q>
+__device__ __forceinline__ float fnma_row_lane(float x, float b, float acc) {
+  static_assert(Q >= 0 && Q < 16, "a lane of the row");
+  asm("v_fmac_f32_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(b), "v"(x), "n"(Q));
+  return acc;
+}
+/* f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose counter is a constant expression */
+template <typename F, int... Q>
+__device__ __forceinline__ void unrolled(F &&f, std::integer_sequence<int, Q...>) {
+  (f(std::integral_constant<int, Q>{}), ...);
 }
 
 /* The reduction of NlmsB: a0 / a1 are a lane's parts of A_0 / A_1.  Lanes 0-7 of the row end up
@@ -76,8 +114,8 @@ __device__ __forceinline__ float reduce_halves(float a0, float a1) {
  * pairs that went out of use two blocks earlier. */
 struct NlmsB {
   /* 64 steps per group of scalars: the two prefix scans (8 DPP operations) serve four steps per lane */
-  static constexpr int TPL = 6, GS = 64, SCR = 3 * GS;
-  static constexpr int LDS_SCR = 2 * SCR;      /* double-buffered groups */
+  static constexpr int TPL = 6, GS = 64;
+  static constexpr int LDS_SCR = 0;            /* the scalars of a group stay in the registers of the lane that made them */
   static constexpr bool OUT_IN_SCR = false;    /* block() writes its 128 outputs to `out` */
   v2f w2[TPL / 2];
   v2f P[8];
@@ -109,9 +147,13 @@ struct NlmsB {
 
   /* the 16 lanes of a channel prepare the 64 steps of a group, four consecutive steps each: E_n and
    * B_n by prefix sums of their increments (x_n^2 - x_{n-96}^2, x_n x_{n-1} - x_{n-96} x_{n-97}),
-   * step size mu / (E_n + eps); dst = [step size x 64 | B x 64 | E x 64] */
-  static __device__ __forceinline__ void prepare(const float *cur, int s0, int sub, float mu, float e_base,
-                                                 float b_base, float *dst, float &emin) {
+   * step size mu / (E_n + eps).  Lane `sub` keeps the scalars of steps 4 sub .. 4 sub + 3: iteration q of the
+   * unrolled step loop consumes exactly those of lane q, and reads them there (mul_row_lane, fnma_row_lane) */
+  struct Scal {
+    float g[4], b[4], e3; /* step sizes, B, and E of the lane's last step */
+  };
+  static __device__ __forceinline__ Scal prepare(const float *cur, int s0, int sub, float mu, float e_base,
+                                                 float b_base, float &emin) {
     const float *x = cur + s0 + 4 * sub; /* the previous block sits right below the current one */
     const float xm = x[-1], qm = x[-97];
     const float4 xv = *reinterpret_cast<const float4 *>(x), qv = *reinterpret_cast<const float4 *>(x - 96);
@@ -130,25 +172,23 @@ struct NlmsB {
     ie += dpp0_f<0x114>(ie); ib += dpp0_f<0x114>(ib);
     ie += dpp0_f<0x118>(ie); ib += dpp0_f<0x118>(ib);
     const float oe = e_base + (ie - ea[3]), ob = b_base + (ib - ba[3]); /* everything before this lane */
-    float e[4], g[4], b[4];
+    Scal r;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      e[k] = oe + ea[k];
-      b[k] = ob + ba[k];
-      const float den = e[k] + 0.000000119209289f;
-      g[k] = mu * __builtin_amdgcn_rcpf(den);
+      const float e = oe + ea[k];
+      r.b[k] = ob + ba[k];
+      const float den = e + 0.000000119209289f;
+      r.g[k] = mu * __builtin_amdgcn_rcpf(den);
       emin = fminf(emin, den);
+      r.e3 = e;
     }
-    float4 *d4 = reinterpret_cast<float4 *>(dst);
-    d4[sub] = make_float4(g[0], g[1], g[2], g[3]);
-    d4[GS / 4 + sub] = make_float4(b[0], b[1], b[2], b[3]);
-    d4[GS / 2 + sub] = make_float4(e[0], e[1], e[2], e[3]);
+    return r;
   }
 
   /* one 128-sample block.  ring is [previous block | current block], 256 floats, so every sample a
    * step looks back at is at a fixed distance below it (no wrap) */
   template <bool OUT_E>
-  __device__ __forceinline__ void block(const float *ring, bool first, float mu, float *out, float *scr, int sub, bool running) {
+  __device__ __forceinline__ void block(const float *ring, bool first, float mu, float *out, float *, int sub, bool running) {
     const float *cur = ring + RDSP_BLOCK;
     const float *dsrc = first ? cur : ring; /* NR:69-79 */
     const float *mine = cur - TPL * sub;
@@ -177,28 +217,19 @@ struct NlmsB {
      * step carries on (`energy -= x0 * x0; energy += in * in` over the whole stream, NR:73 / arm_lms_norm_f32),
      * residue and all; B is this kernel's own quantity and stays the window sum */
     e_base = running ? energy : e_base;
-    prepare(cur, 0, sub, mu, e_base, b_base, scr, emin);
+    Scal sc = prepare(cur, 0, sub, mu, e_base, b_base, emin), nx = sc;
 #pragma unroll
     for (int m = -5; m <= 0; m++) P[m & 7] = (m & 1) ? pair_ld(mine, m) : pair_ld_even(mine, m);
 #pragma unroll 1
     for (int s0 = 0; s0 < RDSP_BLOCK; s0 += GS) {
-      const float *sc = scr + ((s0 / GS) & 1) * SCR;
-      wg_sync<1>();
-      float4 gq = *reinterpret_cast<const float4 *>(sc);
-      float4 bq = *reinterpret_cast<const float4 *>(sc + GS);
       float4 dq = *reinterpret_cast<const float4 *>(dsrc + s0);
-      e_base = sc[2 * GS + GS - 1];
-      b_base = sc[GS + GS - 1];
-      if (s0 + GS < RDSP_BLOCK) prepare(cur, s0 + GS, sub, mu, e_base, b_base, scr + (((s0 / GS) + 1) & 1) * SCR, emin);
-#pragma unroll
-      for (int q = 0; q < GS / 4; q++) {
-        const float gi[4] = {gq.x, gq.y, gq.z, gq.w}, bn[4] = {bq.x, bq.y, bq.z, bq.w};
+      e_base = dpp_f<0x15F>(sc.e3); /* row_newbcast:15, the lane the group ends in */
+      b_base = dpp_f<0x15F>(sc.b[3]);
+      if (s0 + GS < RDSP_BLOCK) nx = prepare(cur, s0 + GS, sub, mu, e_base, b_base, emin);
+      unrolled([&](auto qc) __attribute__((always_inline)) {
+        constexpr int q = decltype(qc)::value; /* lane q of the row holds this iteration's scalars */
         const float dd[4] = {dq.x, dq.y, dq.z, dq.w};
-        if (q < GS / 4 - 1) {
-          gq = *reinterpret_cast<const float4 *>(sc + 4 * (q + 1));
-          bq = *reinterpret_cast<const float4 *>(sc + GS + 4 * (q + 1));
-          dq = *reinterpret_cast<const float4 *>(dsrc + s0 + 4 * (q + 1));
-        }
+        if (q < GS / 4 - 1) dq = *reinterpret_cast<const float4 *>(dsrc + s0 + 4 * (q + 1));
         float o4[4];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
@@ -220,9 +251,9 @@ struct NlmsB {
           const float t = reduce_halves(acc[0], acc[1]);
           const float dA0 = dd[2 * h] - dpp_f<0x150>(t);     /* row_newbcast:0 */
           const float dA1 = dd[2 * h + 1] - dpp_f<0x158>(t); /* row_newbcast:8 */
-          const float g0 = dA0 * gi[2 * h];                  /* e_{n0} = d - A_0 */
-          const float e1 = fmaf(-g0, bn[2 * h + 1], dA1);    /* d - (A_1 + g_{n0} B_{n0+1}) */
-          const float g1 = e1 * gi[2 * h + 1];
+          const float g0 = mul_row_lane<q>(dA0, sc.g[2 * h]);            /* e_{n0} = d - A_0 */
+          const float e1 = fnma_row_lane<q>(g0, sc.b[2 * h + 1], dA1);   /* d - (A_1 + g_{n0} B_{n0+1}) */
+          const float g1 = mul_row_lane<q>(e1, sc.g[2 * h + 1]);
           o4[2 * h] = OUT_E ? dA0 : dd[2 * h] - dA0;
           o4[2 * h + 1] = OUT_E ? e1 : dd[2 * h + 1] - e1;
           /* W += g_{n0} X_{n0} + g_{n0+1} X_{n0+1}: tap pair kk against the swapped sample pairs */
@@ -236,7 +267,8 @@ struct NlmsB {
         }
         *reinterpret_cast<float4 *>(out + s0 + 4 * q) = make_float4(o4[0], o4[1], o4[2], o4[3]);
         __builtin_amdgcn_sched_barrier(0);
-      }
+      }, std::make_integer_sequence<int, GS / 4>{});
+      sc = nx;
     }
     energy = e_base;
   }
@@ -281,7 +313,12 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
   constexpr int FIN = NL::OUT_IN_SCR ? 0 : RDSP_BLOCK;
   /* consecutive channels start 32 dwords apart mod 64: the even sample pairs of the two channels of a
    * 32-lane group (float2 index -3 sub each) then fall on disjoint halves of the 64 banks */
-  constexpr int PER_CH0 = 2 * RINGS * RDSP_BLOCK + FIN + NL::LDS_SCR;
+  /* A ring is four block slots, [M | S0 | S1 | S2].  Block b lives in S(b mod 3) and M mirrors S2, so the block in
+   * front of the current one always lies right below it -- [previous | current], which is what NL::block() takes --
+   * and no block is ever moved: the slot of the block after next is simply written over.  Keeping M costs two
+   * stores per lane every third block (the block that lands in S2 is stored twice). */
+  constexpr int SLOTS = 4;
+  constexpr int PER_CH0 = SLOTS * RINGS * RDSP_BLOCK + FIN + NL::LDS_SCR;
   constexpr int PER_CH = PER_CH0 + (96 - PER_CH0 % 64) % 64;
   static_assert(PER_CH % 64 == 32 && PER_CH % 4 == 0, "channel pitch in LDS");
   static_assert(!(DUAL && NL::OUT_IN_SCR), "the two-instance kernel hands a block on through `out`");
@@ -296,9 +333,9 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
   if (!valid) ch = p.n_channels - 1; /* compute on a real channel, store nothing */
 
   float *ringA = &lds[cw][0];
-  float *ringB = DUAL ? &lds[cw][2 * RDSP_BLOCK] : ringA;
-  float *fin = &lds[cw][2 * RINGS * RDSP_BLOCK];
-  float *scr = &lds[cw][2 * RINGS * RDSP_BLOCK + FIN];
+  float *ringB = DUAL ? &lds[cw][SLOTS * RDSP_BLOCK] : ringA;
+  float *fin = &lds[cw][SLOTS * RINGS * RDSP_BLOCK];
+  float *scr = &lds[cw][SLOTS * RINGS * RDSP_BLOCK + FIN]; /* NL::LDS_SCR floats (none for NlmsB) */
 
   const bool has_inst = DUAL || p.nr_on || p.als_mode;
   const bool one_is_nr = !DUAL && p.nr_on;
@@ -318,7 +355,7 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
   }
   float agc_g = p.st_scal[ch * 4 + 1];
 
-  /* the lower half of a ring is the previous block */
+  /* the block in front of block 0 (S0) goes into M */
   if constexpr (DUAL) {
 #pragma unroll
     for (int k = 0; k < SPL; k++) {
@@ -350,24 +387,33 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
     }
   }
 
+  int slot = 0; /* b mod 3 */
 #pragma unroll 1
   for (int b = 0; b < p.n_blocks; b++) {
+    const float *rA = ringA + slot * RDSP_BLOCK; /* [previous | current] of this block */
     wg_sync<1>();
     RDSP_TP(0);
     if constexpr (DUAL) { /* CONV:326-337, then the ALS filter */
-      float *o = ringB + RDSP_BLOCK;
-      nr.template block<false>(ringA, p.nr_first && b == 0, p.nr_mu, o, scr, sub, p.energy_running != 0);
+      float *rB = ringB + slot * RDSP_BLOCK;
+      float *o = rB + RDSP_BLOCK;
+      nr.template block<false>(rA, p.nr_first && b == 0, p.nr_mu, o, scr, sub, p.energy_running != 0);
       wg_sync<1>();
       if (p.nr_mode == 0) { /* CONV:334 */
 #pragma unroll
         for (int k = 0; k < SPL; k++) o[sub * SPL + k] = mul_1p1(o[sub * SPL + k]);
         wg_sync<1>();
       }
-      if (p.als_mode == 1) als.template block<true>(ringB, p.als_first && b == 0, p.als_mu, fin, scr, sub, p.energy_running != 0);
-      else als.template block<false>(ringB, p.als_first && b == 0, p.als_mu, fin, scr, sub, p.energy_running != 0);
+      if (slot == 2) { /* ring B's mirror: the block just produced */
+        const float4 *o4 = reinterpret_cast<const float4 *>(o + sub * SPL);
+        float4 *m4 = reinterpret_cast<float4 *>(ringB + sub * SPL);
+#pragma unroll
+        for (int k = 0; k < SPL / 4; k++) m4[k] = o4[k];
+      }
+      if (p.als_mode == 1) als.template block<true>(rB, p.als_first && b == 0, p.als_mu, fin, scr, sub, p.energy_running != 0);
+      else als.template block<false>(rB, p.als_first && b == 0, p.als_mu, fin, scr, sub, p.energy_running != 0);
     } else if (has_inst) {
-      if (o_mode == 1) als.template block<true>(ringA, o_first && b == 0, o_mu, fin, scr, sub, p.energy_running != 0);
-      else als.template block<false>(ringA, o_first && b == 0, o_mu, fin, scr, sub, p.energy_running != 0);
+      if (o_mode == 1) als.template block<true>(rA, o_first && b == 0, o_mu, fin, scr, sub, p.energy_running != 0);
+      else als.template block<false>(rA, o_first && b == 0, o_mu, fin, scr, sub, p.energy_running != 0);
     }
     wg_sync<1>();
     RDSP_TP(1);
@@ -376,24 +422,23 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
 #pragma unroll
     for (int k = 0; k < SPL / 4; k++) {
       const float4 a = has_inst ? NL::out4(fin, scr, sub * SPL + 4 * k)
-                                : *reinterpret_cast<const float4 *>(ringA + RDSP_BLOCK + sub * SPL + 4 * k);
+                                : *reinterpret_cast<const float4 *>(rA + RDSP_BLOCK + sub * SPL + 4 * k);
       L[4 * k] = a.x; L[4 * k + 1] = a.y; L[4 * k + 2] = a.z; L[4 * k + 3] = a.w;
     }
     if (!DUAL && has_inst && o_mode == 0) { /* CONV:334 */
 #pragma unroll
       for (int k = 0; k < SPL; k++) L[k] = mul_1p1(L[k]);
     }
-    if (b + 1 < p.n_blocks) { /* the block just processed becomes the previous one, the next one moves in */
-      float4 *r4 = reinterpret_cast<float4 *>(ringA + sub * SPL);
-#pragma unroll
-      for (int k = 0; k < SPL / 4; k++) r4[k] = r4[RDSP_BLOCK / 4 + k];
-      if constexpr (DUAL) {
-        float4 *q4 = reinterpret_cast<float4 *>(ringB + sub * SPL);
-#pragma unroll
-        for (int k = 0; k < SPL / 4; k++) q4[k] = q4[RDSP_BLOCK / 4 + k];
+    slot = slot == 2 ? 0 : slot + 1;
+    if (b + 1 < p.n_blocks) { /* the next block goes into its slot (over the block before the one just processed) */
+      float4 *r4 = reinterpret_cast<float4 *>(ringA + (slot + 1) * RDSP_BLOCK + sub * SPL);
+      r4[0] = nx0;
+      r4[1] = nx1;
+      if (slot == 2) { /* ... and into the mirror */
+        float4 *m4 = reinterpret_cast<float4 *>(ringA + sub * SPL);
+        m4[0] = nx0;
+        m4[1] = nx1;
       }
-      r4[RDSP_BLOCK / 4] = nx0;
-      r4[RDSP_BLOCK / 4 + 1] = nx1;
       if (b + 2 < p.n_blocks) {
         const float4 *n4 = src4 + (size_t)(b + 2) * (RDSP_BLOCK / 4);
         nx0 = n4[0];
@@ -469,19 +514,20 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
       if (h_als) p.st_status[p.st_status_stride + ch] |= h_als;
     }
   }
-  if (valid) { /* the last block processed is the upper half of the ring */
+  if (valid) { /* the last block processed: slot (n_blocks - 1) mod 3 (M, the state as it came, after no block at all) */
+    const int last = p.n_blocks > 0 ? ((p.n_blocks - 1) % 3 + 1) * RDSP_BLOCK : 0;
     if constexpr (DUAL) {
       nr.store(p.nr_w, p.nr_energy, ch, sub);
       als.store(p.als_w, p.als_energy, ch, sub);
 #pragma unroll
       for (int k = 0; k < SPL; k++) {
-        p.nr_prev[ch * RDSP_BLOCK + sub * SPL + k] = ringA[RDSP_BLOCK + sub * SPL + k];
-        p.als_prev[ch * RDSP_BLOCK + sub * SPL + k] = ringB[RDSP_BLOCK + sub * SPL + k];
+        p.nr_prev[ch * RDSP_BLOCK + sub * SPL + k] = ringA[last + sub * SPL + k];
+        p.als_prev[ch * RDSP_BLOCK + sub * SPL + k] = ringB[last + sub * SPL + k];
       }
     } else if (has_inst) {
       als.store(o_w, o_energy, ch, sub);
 #pragma unroll
-      for (int k = 0; k < SPL; k++) o_prev[ch * RDSP_BLOCK + sub * SPL + k] = ringA[RDSP_BLOCK + sub * SPL + k];
+      for (int k = 0; k < SPL; k++) o_prev[ch * RDSP_BLOCK + sub * SPL + k] = ringA[last + sub * SPL + k];
     }
     if (sub == 0 && !p.raw_out) p.st_scal[ch * 4 + 1] = agc_g;
   }
@@ -490,7 +536,7 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
 /* two NLMS instances (DSP-NR feeding the ALS filter; the sketch's menu never enables both, CTL:240-296) */
 __global__ void __launch_bounds__(64) rdsp_tail_dual_kernel(RdspTailParams p) { tail_body<true, NlmsB>(p); }
 
-/* The default (one NLMS instance).  124 VGPRs, 128 allocated: in pipelined mode it shares a SIMD's 512 with
+/* The default (one NLMS instance).  116 VGPRs, 128 allocated: in pipelined mode it shares a SIMD's 512 with
  * two waves of the frequency-domain front kernel (176 allocated each: 480 in all); a tail wave that does
  * not fit waits for a front wave to retire (measured in round 1: 1.8 -> 2.4 ms per K3 step).  The CPU suite
  * reads both counts out of the built code object (test_generated_code_keeps_...). */
