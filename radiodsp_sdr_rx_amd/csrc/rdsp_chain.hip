@@ -3,7 +3,7 @@
  * HBM, shared tables) and the calls declared in include/rdsp.h that create, destroy,
  * reset and run it.  Its groups, setters and state live in rdsp_chain_groups.hip,
  * rdsp_chain_ctl.hip and rdsp_chain_state.hip (rdsp_chain_int.h).  Host logic
- * only; the arithmetic lives in rdsp_kernels.hip.  No CPU fallback exists: if
+ * only; the arithmetic lives in the kernel files (rdsp_front_*.hip, rdsp_tail*.hip, ...).  No CPU fallback exists: if
  * HIP reports no device every compute entry point returns RDSP_ERR_NO_DEVICE.
  */
 #include <stdarg.h>
@@ -389,8 +389,8 @@ static void front_params(rdsp_chain_t *c, Call &k) {
   if (c->fir_mode == -1 && fp.fir_fd == 2 && !fp.to_mid) fp.fir_fd = 3;
   fp.fd_mask = c->d_fd_mask;
   fp.rd_mask = c->d_rd_mask;
-  c->front_name = !fp.fir_fd ? "rdsp_front_kernel"
-                             : ((fp.fir_fd >= 3 && !fp.nb_on) ? "rdsp_front_rd_kernel" : "rdsp_front_fd_kernel");
+  RdspFrontPick pick; /* the kernel this call runs, for the timing records (a refusal leaves the name: the launch reports it) */
+  if (rdsp_front_pick(c->N, c->decim, &fp, &pick) == 0) c->front_name = rdsp_front_kernel_name(pick.family);
   /* the intermediate buffers of this call: slot 0 is d_mid */
   fp.mid = (k.piped && k.slot) ? c->d_midx[k.slot - 1].p : c->d_mid.p;
   fp.mid_q = c->d_mid_q[k.piped ? k.slot : 0];

@@ -2,7 +2,7 @@
  * rdsp_chain_int.h -- what the host files of rdsp_chain_t share: the object, the error returns, the table of per-channel
  * state planes.  rdsp_chain.hip creates, destroys, resets and runs it; rdsp_chain_groups.hip holds the receiver groups and
  * what selects their filters and demodulators; rdsp_chain_ctl.hip the setters; rdsp_chain_state.hip the state planes, the
- * blob and the read-backs.  Host logic only; the arithmetic lives in rdsp_kernels.hip and the other kernel files.
+ * blob and the read-backs.  Host logic only; the arithmetic lives in the kernel files (rdsp_front_*.hip, rdsp_tail*.hip, ...).
  */
 #ifndef RDSP_CHAIN_INT_H
 #define RDSP_CHAIN_INT_H

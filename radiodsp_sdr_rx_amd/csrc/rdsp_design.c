@@ -116,7 +116,7 @@ int rdsp_init_filter_mask(float *mask, const double *coef_I, const double *coef_
   return 0;
 }
 
-/* radix P used by the kernels for each FFT_L (rdsp_kernels.hip dispatch) */
+/* radix P used by the kernels for each FFT_L (with_front_plan, rdsp_front_launch.h) */
 int rdsp_plan_radix(int fft_l) {
   switch (fft_l) {
     case 256: return 4;

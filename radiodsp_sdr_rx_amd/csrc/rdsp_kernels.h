@@ -91,6 +91,21 @@ struct RdspFrontParams {
   int ch_base;             /* first channel of this launch (workgroup b works on ch_base + b) */
 };
 
+/* Which front-kernel instance a call runs: the one statement of that choice (rdsp_front_pick, rdsp_kernels.hip).
+ * rdsp_launch_front launches what it names, and the chain takes the kernel's name for its timing records from it. */
+enum { RDSP_FRONT_DIRECT = 0, RDSP_FRONT_FD = 1, RDSP_FRONT_RD = 2 };
+struct RdspFrontPick {
+  int family;  /* RDSP_FRONT_DIRECT: rdsp_front_kernel (decimator in direct form, or none); _FD: rdsp_front_fd_kernel
+                  (frequency domain, wave-wide frames); _RD: rdsp_front_rd_kernel (frequency domain, 16-lane rows) */
+  int radix;   /* P of the overlap-save filter's transform: 4, 8 or 16 points per thread */
+  int lean;    /* LEAN: FFT twiddles rebuilt per pass */
+  int pre;     /* PRE: IQ swap, noise blanker, two input gains and a history from other settings compiled in */
+  int fmx;     /* FMX: decimating FIR on the matrix cores (direct family, EXPERIMENTAL=1 builds) */
+  int q4;      /* Q4: FFT_L 256, four overlap-save frames per pass (front_frame_quad) */
+  int frame;   /* fd: VC, new quad columns per decimator frame (4 or 7); rd: RV, outputs per window (128 or 192);
+                  direct: 0 */
+};
+
 /* SAM demodulator (PLL, serial in time): one channel per lane, in place on `mid`
  * for the channels whose group demodulates SAM */
 struct RdspSamParams {
@@ -204,6 +219,11 @@ int rdsp_launch_biquad_coef_store(float *dst, const float *coef20, hipStream_t s
 /* returns hipError_t as int */
 int rdsp_launch_front(int fft_l, int decim, const RdspFrontParams *p, int n_channels,
                       hipStream_t stream);
+/* the instance rdsp_launch_front runs for these arguments; returns hipError_t as int (hipErrorInvalidValue: no such
+ * FFT_L / decimation, or a row form without its masks; hipErrorNotSupported: a variant this build does not carry), and
+ * leaves *pick alone then.  Looks at no pointer of *p but rd_mask (null or not). */
+int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, RdspFrontPick *pick);
+const char *rdsp_front_kernel_name(int family); /* "rdsp_front_kernel", "rdsp_front_fd_kernel", "rdsp_front_rd_kernel" */
 int rdsp_launch_tail(const RdspTailParams *p, int lanes_per_channel, hipStream_t stream);
 int rdsp_launch_sam(const RdspSamParams *p, hipStream_t stream);
 int rdsp_launch_tail_engine(const RdspTailEngineParams *p, hipStream_t stream);

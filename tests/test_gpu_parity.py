@@ -186,7 +186,7 @@ def test_spectral_stage_as_written_matches_the_oracle_as_written(rdsp, oracle, t
             out.append(oc.process(iq[c])[1])
         return np.stack(out)
 
-    g_lit, s_lit = gpu(1)            # the table's interpolation in closed form (csrc/rdsp_kernels.hip spec_table_factor)
+    g_lit, s_lit = gpu(1)            # the table's interpolation in closed form (csrc/rdsp_front_frame.h spec_table_factor)
     g_tab, _ = gpu(2)                # atan2f and the table looked up
     g_eq, s_eq = gpu(False)
     o_lit, o_eq = orc(True), orc(False)

@@ -455,7 +455,7 @@ def test_bench_k1_line_on_the_host(tmp_path):
 
 def test_as_written_resynthesis_in_closed_form_is_the_tables_own_arithmetic():
     """SPEC:229-232 multiplies the new magnitude by arm_cos_f32(phi) and arm_sin_f32(phi): CMSIS' 513-entry table with
-    linear interpolation.  csrc/rdsp_kernels.hip (spec_table_factor) evaluates that interpolation in closed form: the table
+    linear interpolation.  csrc/rdsp_front_frame.h (spec_table_factor) evaluates that interpolation in closed form: the table
     value is the exact sine / cosine times A(f) = 1 - (h^2 / 2) f (1 - f), h = 2 pi / 512, f the fraction between nodes,
     with f from a degree-11 arctangent of min / max (f (1 - f) is the same in all eight octants).  Here, over the whole
     circle and in float32 like the kernel: the closed form against the table's own arithmetic (the published routine,
