@@ -40,6 +40,7 @@
 
 #include "rdsp_host.h"
 #include "rdsp_kernels.h"
+#include "rdsp_node_dev.h"
 #include "rdsp_sync.h"
 
 namespace {
@@ -281,17 +282,8 @@ struct rdsp_biquad {
   int n_stages = 0;   /* update() runs stage 0, then every next stage while the one before it is chained to it */
   bool dirty = true;
   std::vector<int> clear_sum; /* stages whose residue the next update zeroes (`*dest &= 0x80000000`) */
-  int32_t *d_coef = nullptr, *d_state = nullptr;
+  rdsp_dev::DevBuf<int32_t> d_coef, d_state;
 };
-
-#define BQ_TRY(expr)                                                            \
-  do {                                                                          \
-    hipError_t e_ = (expr);                                                     \
-    if (e_ != hipSuccess) {                                                     \
-      rdsp_set_error("%s failed: %s", #expr, hipGetErrorString(e_));            \
-      return RDSP_ERR_HIP;                                                      \
-    }                                                                           \
-  } while (0)
 
 namespace {
 struct ICoefWords { int32_t w[20]; };
@@ -319,8 +311,7 @@ extern "C" int rdsp_biquad_create(int n_channels, int device, double fs, rdsp_bi
   b->device = device;
   b->fs = fs;
   memset(b->coef, 0, sizeof(b->coef)); /* "by default, the filter will not pass anything" (the library's constructor) */
-  if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&b->d_coef, sizeof(b->coef)) != hipSuccess ||
-      hipMalloc((void **)&b->d_state, sizeof(int32_t) * 20 * (size_t)n_channels) != hipSuccess ||
+  if (hipSetDevice(device) != hipSuccess || b->d_coef.alloc(20) != hipSuccess || b->d_state.alloc(20 * (size_t)n_channels) != hipSuccess ||
       hipMemset(b->d_state, 0, sizeof(int32_t) * 20 * (size_t)n_channels) != hipSuccess) {
     rdsp_set_error("rdsp_biquad_create: device allocation failed");
     rdsp_biquad_destroy(b);
@@ -332,8 +323,6 @@ extern "C" int rdsp_biquad_create(int n_channels, int device, double fs, rdsp_bi
 extern "C" void rdsp_biquad_destroy(rdsp_biquad_t *b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  if (b->d_coef) (void)hipFree(b->d_coef);
-  if (b->d_state) (void)hipFree(b->d_state);
   delete b;
 }
 /* void setCoefficients(uint32_t stage, const int *coefficients): {b0, b1, b2, a1, a2} x 2^30; a1 and a2 are stored
@@ -400,7 +389,7 @@ extern "C" int rdsp_biquad_update(rdsp_biquad_t *b, const int16_t *d_in, size_t 
     rdsp_set_error("rdsp_biquad_update: bad argument");
     return RDSP_ERR_INVALID;
   }
-  BQ_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipSetDevice(b->device));
   hipStream_t stream = (hipStream_t)stream_;
   if (b->dirty) {
     ICoefWords v;
@@ -433,38 +422,19 @@ namespace {
 struct BiquadNode {
   rdsp_biquad_t *bq;
   int n_channels;
-  int16_t *d_in = nullptr, *d_out = nullptr;
-  hipStream_t stream = nullptr;
-  int status = RDSP_OK;
-  int device = 0; /* the object's device: selected in update and destroy (a process may drive several GPUs) */
+  rdsp_node_dev::NodeDev<> dev; /* on the object's device (a process may drive several GPUs) */
 };
-void biquad_node_destroy(void *u) {
-  BiquadNode *s = static_cast<BiquadNode *>(u);
-  (void)hipSetDevice(s->device); /* the node's buffers and stream live on its object's device */
-  if (s->d_in) (void)hipFree(s->d_in);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
 void biquad_node_update(rdsp_node_t *n, void *u) {
   BiquadNode *s = static_cast<BiquadNode *>(u);
   rdsp_block_t *in = rdsp_receive_readonly(n, 0);
   if (!in) return; /* no input this tick: nothing is transmitted */
-  (void)hipSetDevice(s->device);
-  rdsp_block_t *out = rdsp_allocate(n);
+  rdsp_block_t *out = rdsp_allocate(n); /* before the upload: the download goes straight into it */
   if (!out) { rdsp_release(in); return; }
-  const size_t bytes = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES * sizeof(int16_t);
-  hipError_t e = hipMemcpyAsync(s->d_in, rdsp_block_data(in), bytes, hipMemcpyHostToDevice, s->stream);
-  int rc = RDSP_OK;
-  if (e == hipSuccess) rc = rdsp_biquad_update(s->bq, s->d_in, RDSP_BLOCK_SAMPLES, 1, 1, s->d_out, RDSP_BLOCK_SAMPLES, 1, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK) e = hipMemcpyAsync(rdsp_block_data(out), s->d_out, bytes, hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess || rc != RDSP_OK) {
-    s->status = (rc != RDSP_OK) ? rc : RDSP_ERR_HIP;
-    if (e != hipSuccess) rdsp_set_error("biquad node: %s", hipGetErrorString(e));
-  } else {
-    rdsp_transmit(n, out, 0);
-  }
+  const size_t len = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES;
+  const bool ok = s->dev.run("biquad node", rdsp_block_data(in), len, [&](int16_t *d_in, int16_t *d_out, hipStream_t st) {
+    return rdsp_biquad_update(s->bq, d_in, RDSP_BLOCK_SAMPLES, 1, 1, d_out, RDSP_BLOCK_SAMPLES, 1, st);
+  }, rdsp_block_data(out), len);
+  if (ok) rdsp_transmit(n, out, 0);
   rdsp_release(out);
   rdsp_release(in);
 }
@@ -478,20 +448,10 @@ extern "C" rdsp_node_t *rdsp_biquad_node_create(rdsp_graph_t *g, rdsp_biquad_t *
   BiquadNode *s = new BiquadNode();
   s->bq = bq;
   s->n_channels = bq->n_channels;
-  s->device = bq->device;
-  const size_t bytes = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES * sizeof(int16_t);
-  if (hipSetDevice(bq->device) != hipSuccess || hipMalloc((void **)&s->d_in, bytes) != hipSuccess ||
-      hipMalloc((void **)&s->d_out, bytes) != hipSuccess || hipStreamCreate(&s->stream) != hipSuccess) {
-    rdsp_set_error("rdsp_biquad_node_create: device allocation failed");
-    biquad_node_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_t *n = rdsp_node_create(g, 1, biquad_node_update, s);
-  if (!n) { biquad_node_destroy(s); return nullptr; }
-  rdsp_node_set_destructor(n, biquad_node_destroy);
-  return n;
+  const size_t len = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES;
+  return rdsp_node_dev::make_node(g, 1, biquad_node_update, s, "rdsp_biquad_node_create", bq->device, len, len);
 }
 extern "C" int rdsp_biquad_node_status(rdsp_node_t *n) {
   BiquadNode *s = static_cast<BiquadNode *>(rdsp_node_user(n));
-  return s ? s->status : RDSP_ERR_INVALID;
+  return s ? s->dev.status : RDSP_ERR_INVALID;
 }

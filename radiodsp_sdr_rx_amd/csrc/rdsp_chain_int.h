@@ -23,13 +23,6 @@ using namespace rdsp_dev; /* DevBuf, PinnedBuf, Stream, Event */
 
 /* the error text and the code to return with it (rdsp_chain.hip) */
 int chain_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return chain_fail(RDSP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);           \
-  } while (0)
-#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_ != RDSP_OK) return rc_; } while (0)
 #define NEED(c) do { if (!(c)) return RDSP_ERR_INVALID; } while (0)
 /* a setter's first line: with rdsp_sdr_set_engine_literal(chain, 1) the `SDR.` / `preProcessor.` calls reach the reference's own objects */
 #define TO_ENGINE(c, call) do { NEED(c); if ((c)->engine) return (call); } while (0)

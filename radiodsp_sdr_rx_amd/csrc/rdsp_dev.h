@@ -9,6 +9,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rdsp_host.h"
+
 namespace rdsp_dev {
 
 template <typename T>
@@ -50,5 +52,20 @@ struct Event {
   operator hipEvent_t() const { return e; }
 };
 
+/* a HIP call returned e != hipSuccess */
+static inline int hip_fail(const char *expr, hipError_t e, const char *file, int line) {
+  rdsp_set_error("%s failed: %s (%s:%d)", expr, hipGetErrorString(e), file, line);
+  return RDSP_ERR_HIP;
+}
+
 }  // namespace rdsp_dev
+
+/* the try macros of every host file: a failed HIP call sets the error text and returns RDSP_ERR_HIP, a failed rdsp call
+ * returns its code */
+#define HIP_TRY(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess) return rdsp_dev::hip_fail(#expr, e_, __FILE__, __LINE__);           \
+  } while (0)
+#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_ != RDSP_OK) return rc_; } while (0)
 #endif

@@ -33,8 +33,7 @@ struct EngSources {
   DevBuf<uint32_t> phase, dphi, tuned;
   DevBuf<int> source_of, order, wg_first, wg_count;
   DevBuf<float4> tune_tab;
-  hipEvent_t dphi_ev = nullptr; /* the last upload of dphi has left dphi_stage */
-  ~EngSources() { if (dphi_ev) (void)hipEventDestroy(dphi_ev); }
+  rdsp_dev::Event dphi_ev; /* the last upload of dphi has left dphi_stage */
 };
 /* sources at D > 1: the prototype's taps, every receiver's translated taps, and per SOURCE the last 15 D pairs */
 struct EngDdc { DevBuf<float> h; DevBuf<float2> g; DevBuf<uint32_t> hist; };
@@ -481,7 +480,7 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
     if (err == hipSuccess) err = q->wg_count.alloc(n);
     if (err == hipSuccess) err = q->tune_tab.alloc(rdsp_tune::TUNE_N);
     if (err == hipSuccess) err = q->tuned.alloc(n * (size_t)e->max_blocks * BS);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&q->dphi_ev, hipEventDisableTiming);
+    if (err == hipSuccess) err = q->dphi_ev.create(hipEventDisableTiming);
     if (err == hipSuccess) err = hipEventRecord(q->dphi_ev, nullptr);
     if (err == hipSuccess) err = hipMemset(q->phase, 0, n * 4);
     if (err == hipSuccess) err = hipMemcpy(q->tune_tab, rdsp_engine_tune_table(), rdsp_tune::TUNE_N * sizeof(float4), hipMemcpyHostToDevice);

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rdsp_host.h"
+#include "rdsp_node_dev.h"
 #include "rdsp_q15.h"
 #include "rdsp_sync.h"
 
@@ -135,23 +136,14 @@ struct rdsp_fft1024 {
   int n_channels, device;
   int has_window = 0;
   int have = 0; /* samples buffered per channel */
-  int16_t *d_window = nullptr, *d_hist = nullptr;
-  uint16_t *d_guess = nullptr;
-  uint32_t *d_twid = nullptr;
+  rdsp_dev::DevBuf<int16_t> d_window, d_hist;
+  rdsp_dev::DevBuf<uint16_t> d_guess;
+  rdsp_dev::DevBuf<uint32_t> d_twid;
 };
-
-#define F1K_TRY(expr)                                                           \
-  do {                                                                          \
-    hipError_t e_ = (expr);                                                     \
-    if (e_ != hipSuccess) {                                                     \
-      rdsp_set_error("%s failed: %s", #expr, hipGetErrorString(e_));            \
-      return RDSP_ERR_HIP;                                                      \
-    }                                                                           \
-  } while (0)
 
 static int fft1024_upload_window(rdsp_fft1024_t *s, const int16_t *w1024) {
   s->has_window = w1024 != nullptr;
-  if (w1024) F1K_TRY(hipMemcpy(s->d_window, w1024, 1024 * sizeof(int16_t), hipMemcpyHostToDevice));
+  if (w1024) HIP_TRY(hipMemcpy(s->d_window, w1024, 1024 * sizeof(int16_t), hipMemcpyHostToDevice));
   return RDSP_OK;
 }
 static int fft1024_upload_window_id(rdsp_fft1024_t *s, int window_id) {
@@ -179,10 +171,8 @@ extern "C" int rdsp_fft1024_create(int n_channels, int device, int window_id, rd
   s->device = device;
   std::vector<uint32_t> tw(768);
   rdsp_q15_twiddles(1024, tw.data());
-  if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&s->d_window, 1024 * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_twid, 768 * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_guess, 33 * sizeof(uint16_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_hist, (size_t)n_channels * 896 * sizeof(int16_t)) != hipSuccess ||
+  if (hipSetDevice(device) != hipSuccess || s->d_window.alloc(1024) != hipSuccess || s->d_twid.alloc(768) != hipSuccess ||
+      s->d_guess.alloc(33) != hipSuccess || s->d_hist.alloc((size_t)n_channels * 896) != hipSuccess ||
       hipMemset(s->d_hist, 0, (size_t)n_channels * 896 * sizeof(int16_t)) != hipSuccess ||
       hipMemcpy(s->d_twid, tw.data(), 768 * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(s->d_guess, rdsp_sqrt_guess_table(), 33 * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess ||
@@ -197,24 +187,20 @@ extern "C" int rdsp_fft1024_create(int n_channels, int device, int window_id, rd
 extern "C" void rdsp_fft1024_destroy(rdsp_fft1024_t *s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  if (s->d_window) (void)hipFree(s->d_window);
-  if (s->d_twid) (void)hipFree(s->d_twid);
-  if (s->d_guess) (void)hipFree(s->d_guess);
-  if (s->d_hist) (void)hipFree(s->d_hist);
   delete s;
 }
 extern "C" int rdsp_fft1024_windowFunction(rdsp_fft1024_t *s, int window_id) {
   if (!s) return RDSP_ERR_INVALID;
-  F1K_TRY(hipSetDevice(s->device));
-  F1K_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
   return fft1024_upload_window_id(s, window_id);
 }
 /* windowFunction(const int16_t *w) with the library's own argument: a host pointer to 1024 q15 taps
  * (AudioWindowHanning1024, INO:147) or NULL */
 extern "C" int rdsp_fft1024_windowFunction_table(rdsp_fft1024_t *s, const int16_t *w1024) {
   if (!s) return RDSP_ERR_INVALID;
-  F1K_TRY(hipSetDevice(s->device));
-  F1K_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
   return fft1024_upload_window(s, w1024);
 }
 /* AudioFFT.averageTogether(30) (INO:148): the library's 1024-point analyser declares it and does
@@ -240,7 +226,7 @@ extern "C" int rdsp_fft1024_update(rdsp_fft1024_t *s, const int16_t *d_audio, si
     rdsp_set_error("rdsp_fft1024_update: output buffer holds %zu spectra per channel, %d needed", out_stride, nf);
     return RDSP_ERR_INVALID;
   }
-  F1K_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->device));
   const int total = s->have + n_blocks * 128;
   RdspFft1024Params p;
   memset(&p, 0, sizeof(p));
@@ -275,40 +261,20 @@ struct Fft1024Node {
   rdsp_fft1024_t *an;
   int n_channels;
   std::vector<uint16_t> h_out; /* [ch][512] */
-  int16_t *d_in = nullptr;
-  uint16_t *d_out = nullptr;
-  hipStream_t stream = nullptr;
-  int outputflag = 0, status = RDSP_OK;
-  int device = 0; /* the object's device: selected in update and destroy (a process may drive several GPUs) */
+  rdsp_node_dev::NodeDev<uint16_t> dev; /* on the object's device (a process may drive several GPUs) */
+  int outputflag = 0;
 };
-void fft1024_node_destroy(void *u) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(u);
-  (void)hipSetDevice(s->device); /* the node's buffers and stream live on its object's device */
-  if (s->d_in) (void)hipFree(s->d_in);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
 void fft1024_node_update(rdsp_node_t *n, void *u) {
   Fft1024Node *s = static_cast<Fft1024Node *>(u);
   rdsp_block_t *b = rdsp_receive_readonly(n, 0);
   if (!b) return;
-  (void)hipSetDevice(s->device);
-  const size_t bytes = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES * sizeof(int16_t);
   int n_out = 0;
-  hipError_t e = hipMemcpyAsync(s->d_in, rdsp_block_data(b), bytes, hipMemcpyHostToDevice, s->stream);
-  int rc = RDSP_OK;
-  if (e == hipSuccess) rc = rdsp_fft1024_update(s->an, s->d_in, RDSP_BLOCK_SAMPLES, 1, 1, s->d_out, 1, &n_out, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK && n_out > 0)
-    e = hipMemcpyAsync(s->h_out.data(), s->d_out, s->h_out.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK) e = hipStreamSynchronize(s->stream); /* the block is released below */
-  rdsp_release(b);
-  if (e != hipSuccess || rc != RDSP_OK) {
-    s->status = (rc != RDSP_OK) ? rc : RDSP_ERR_HIP;
-    if (e != hipSuccess) rdsp_set_error("fft1024 node: %s", hipGetErrorString(e));
-    return;
-  }
-  if (n_out > 0) s->outputflag = 1;
+  const bool ok = s->dev.run("fft1024 node", rdsp_block_data(b), (size_t)s->n_channels * RDSP_BLOCK_SAMPLES,
+                             [&](int16_t *d_in, uint16_t *d_out, hipStream_t st) {
+                               return rdsp_fft1024_update(s->an, d_in, RDSP_BLOCK_SAMPLES, 1, 1, d_out, 1, &n_out, st);
+                             }, s->h_out.data(), s->h_out.size(), &n_out);
+  rdsp_release(b); /* after the synchronize: the upload read it */
+  if (ok && n_out > 0) s->outputflag = 1;
 }
 }  // namespace
 
@@ -320,20 +286,9 @@ extern "C" rdsp_node_t *rdsp_fft1024_node_create(rdsp_graph_t *g, rdsp_fft1024_t
   Fft1024Node *s = new Fft1024Node();
   s->an = an;
   s->n_channels = an->n_channels;
-  s->device = an->device;
   s->h_out.assign((size_t)s->n_channels * 512, 0);
-  if (hipSetDevice(an->device) != hipSuccess ||
-      hipMalloc((void **)&s->d_in, (size_t)s->n_channels * RDSP_BLOCK_SAMPLES * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_out, s->h_out.size() * sizeof(uint16_t)) != hipSuccess ||
-      hipStreamCreate(&s->stream) != hipSuccess) {
-    rdsp_set_error("rdsp_fft1024_node_create: device allocation failed");
-    fft1024_node_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_t *n = rdsp_node_create(g, 1, fft1024_node_update, s);
-  if (!n) { fft1024_node_destroy(s); return nullptr; }
-  rdsp_node_set_destructor(n, fft1024_node_destroy);
-  return n;
+  return rdsp_node_dev::make_node(g, 1, fft1024_node_update, s, "rdsp_fft1024_node_create", an->device,
+                                  (size_t)s->n_channels * RDSP_BLOCK_SAMPLES, s->h_out.size());
 }
 extern "C" int rdsp_fft1024_node_available(rdsp_node_t *n) {
   Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
@@ -358,5 +313,5 @@ extern "C" float rdsp_fft1024_node_read_range(rdsp_node_t *n, int ch, unsigned i
 }
 extern "C" int rdsp_fft1024_node_status(rdsp_node_t *n) {
   Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
-  return s ? s->status : RDSP_ERR_INVALID;
+  return s ? s->dev.status : RDSP_ERR_INVALID;
 }

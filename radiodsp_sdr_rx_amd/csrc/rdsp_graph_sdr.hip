@@ -16,6 +16,9 @@
 #include <vector>
 
 #include "rdsp_host.h"
+#include "rdsp_node_dev.h"
+
+using namespace rdsp_node_dev;
 
 namespace {
 struct SdrNode {
@@ -24,37 +27,17 @@ struct SdrNode {
   int have; /* input blocks staged */
   std::vector<int16_t> h_iq;  /* [ch][gran*128][2] */
   std::vector<int16_t> h_out; /* [ch][gran*128/decim][2] */
-  int16_t *d_iq = nullptr, *d_out = nullptr;
-  hipStream_t stream = nullptr;
-  int device = 0;
+  NodeDev<> dev;
   std::deque<std::vector<int16_t>> out_l, out_r; /* audio tiles waiting for a tick */
-  int status = RDSP_OK;
 };
-
-void sdr_destroy(void *u) {
-  SdrNode *s = static_cast<SdrNode *>(u);
-  (void)hipSetDevice(s->device);
-  if (s->d_iq) (void)hipFree(s->d_iq);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
 
 void sdr_update(rdsp_node_t *n, void *u) {
   SdrNode *s = static_cast<SdrNode *>(u);
   rdsp_block_t *bi = rdsp_receive_readonly(n, 0);
   rdsp_block_t *bq = rdsp_receive_readonly(n, 1);
   if (bi && bq) {
-    const int16_t *pi = rdsp_block_data(bi), *pq = rdsp_block_data(bq);
-    const size_t row = (size_t)s->gran * RDSP_BLOCK_SAMPLES;
-    for (int c = 0; c < s->n_channels; c++) {
-      int16_t *dst = &s->h_iq[((size_t)c * row + (size_t)s->have * RDSP_BLOCK_SAMPLES) * 2];
-      const int16_t *si = pi + (size_t)c * RDSP_BLOCK_SAMPLES, *sq = pq + (size_t)c * RDSP_BLOCK_SAMPLES;
-      for (int i = 0; i < RDSP_BLOCK_SAMPLES; i++) {
-        dst[2 * i] = si[i];
-        dst[2 * i + 1] = sq[i];
-      }
-    }
+    tiles_to_pairs(rdsp_block_data(bi), rdsp_block_data(bq), s->n_channels, s->h_iq.data(), (size_t)s->gran * RDSP_BLOCK_SAMPLES,
+                   (size_t)s->have * RDSP_BLOCK_SAMPLES);
     s->have++;
   }
   rdsp_release(bi); /* a lone I or Q block is dropped, like a node returning early */
@@ -63,35 +46,16 @@ void sdr_update(rdsp_node_t *n, void *u) {
   if (s->have == s->gran) {
     const size_t in_row = (size_t)s->gran * RDSP_BLOCK_SAMPLES;
     const size_t out_row = in_row / (size_t)s->decim;
-    hipError_t e = hipSetDevice(s->device);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(s->d_iq, s->h_iq.data(), s->h_iq.size() * sizeof(int16_t), hipMemcpyHostToDevice, s->stream);
-    int rc = RDSP_OK;
-    if (e == hipSuccess)
-      rc = rdsp_chain_process(s->chain, s->d_iq, in_row, s->gran, s->d_out, out_row, nullptr, s->stream);
-    /* a chain in pipelined mode finishes d_out on its internal tail stream: the copy below waits for it */
-    if (e == hipSuccess && rc == RDSP_OK) rc = rdsp_chain_flush(s->chain, s->stream);
-    if (e == hipSuccess && rc == RDSP_OK)
-      e = hipMemcpyAsync(s->h_out.data(), s->d_out, s->h_out.size() * sizeof(int16_t),
-                         hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && rc == RDSP_OK) e = hipStreamSynchronize(s->stream);
-    if (e != hipSuccess || rc != RDSP_OK) {
-      s->status = (rc != RDSP_OK) ? rc : RDSP_ERR_HIP;
-      if (e != hipSuccess) rdsp_set_error("sdr node: %s", hipGetErrorString(e));
-    } else {
-      const int n_tiles = (int)(out_row / RDSP_BLOCK_SAMPLES);
-      for (int t = 0; t < n_tiles; t++) {
-        std::vector<int16_t> L((size_t)s->n_channels * RDSP_BLOCK_SAMPLES), R(L.size());
-        for (int c = 0; c < s->n_channels; c++) {
-          const int16_t *src = &s->h_out[((size_t)c * out_row + (size_t)t * RDSP_BLOCK_SAMPLES) * 2];
-          for (int i = 0; i < RDSP_BLOCK_SAMPLES; i++) {
-            L[(size_t)c * RDSP_BLOCK_SAMPLES + i] = src[2 * i];
-            R[(size_t)c * RDSP_BLOCK_SAMPLES + i] = src[2 * i + 1];
-          }
-        }
-        s->out_l.push_back(std::move(L));
-        s->out_r.push_back(std::move(R));
-      }
+    /* a chain in pipelined mode finishes d_out on its internal tail stream: the flush makes the copy back wait for it */
+    const bool ok = s->dev.run("sdr node", s->h_iq.data(), s->h_iq.size(), [&](int16_t *d_iq, int16_t *d_out, hipStream_t st) {
+      const int rc = rdsp_chain_process(s->chain, d_iq, in_row, s->gran, d_out, out_row, nullptr, st);
+      return rc != RDSP_OK ? rc : rdsp_chain_flush(s->chain, st);
+    }, s->h_out.data(), s->h_out.size());
+    for (size_t t = 0; ok && t < out_row / RDSP_BLOCK_SAMPLES; t++) {
+      std::vector<int16_t> L((size_t)s->n_channels * RDSP_BLOCK_SAMPLES), R(L.size());
+      pairs_to_tiles(s->h_out.data(), out_row, t * RDSP_BLOCK_SAMPLES, s->n_channels, L.data(), R.data());
+      s->out_l.push_back(std::move(L));
+      s->out_r.push_back(std::move(R));
     }
     s->have = 0;
   }
@@ -126,27 +90,12 @@ extern "C" rdsp_node_t *rdsp_sdr_node_create(rdsp_graph_t *g, rdsp_chain_t *chai
   const size_t in_n = (size_t)s->n_channels * s->gran * RDSP_BLOCK_SAMPLES * 2;
   s->h_iq.assign(in_n, 0);
   s->h_out.assign(in_n / s->decim, 0);
-  s->device = rdsp_chain_device(chain); /* the node's buffers and stream live where the chain does */
-  if (hipSetDevice(s->device) != hipSuccess ||
-      hipMalloc((void **)&s->d_iq, in_n * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_out, in_n / s->decim * sizeof(int16_t)) != hipSuccess ||
-      hipStreamCreate(&s->stream) != hipSuccess) {
-    rdsp_set_error("rdsp_sdr_node_create: device allocation failed");
-    sdr_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_t *n = rdsp_node_create(g, 2, sdr_update, s);
-  if (!n) {
-    sdr_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_set_destructor(n, sdr_destroy);
-  return n;
+  return make_node(g, 2, sdr_update, s, "rdsp_sdr_node_create", rdsp_chain_device(chain), in_n, in_n / s->decim);
 }
 
 extern "C" int rdsp_sdr_node_status(rdsp_node_t *n) {
   SdrNode *s = static_cast<SdrNode *>(rdsp_node_user(n));
-  return s ? s->status : RDSP_ERR_INVALID;
+  return s ? s->dev.status : RDSP_ERR_INVALID;
 }
 
 /* ---- AudioAnalyzeFFT256IQ as a graph node (analyze_fft256iq.h:52-110) -----------------
@@ -161,22 +110,9 @@ struct SpectrumNode {
   int n_channels;
   std::vector<int16_t> h_iq;      /* [ch][128][2] */
   std::vector<uint16_t> h_out;    /* [ch][256]    */
-  int16_t *d_iq = nullptr;
-  uint16_t *d_out = nullptr;
-  hipStream_t stream = nullptr;
-  int device = 0;
+  NodeDev<uint16_t> dev;
   int outputflag = 0;             /* FFTIQ.h:63 */
-  int status = RDSP_OK;
 };
-
-void spectrum_destroy(void *u) {
-  SpectrumNode *s = static_cast<SpectrumNode *>(u);
-  (void)hipSetDevice(s->device);
-  if (s->d_iq) (void)hipFree(s->d_iq);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
 
 void spectrum_update(rdsp_node_t *n, void *u) {
   SpectrumNode *s = static_cast<SpectrumNode *>(u);
@@ -187,31 +123,14 @@ void spectrum_update(rdsp_node_t *n, void *u) {
     rdsp_release(bq);
     return;
   }
-  const int16_t *pi = rdsp_block_data(bi), *pq = rdsp_block_data(bq);
-  for (int c = 0; c < s->n_channels; c++) {
-    int16_t *dst = &s->h_iq[(size_t)c * RDSP_BLOCK_SAMPLES * 2];
-    for (int i = 0; i < RDSP_BLOCK_SAMPLES; i++) {
-      dst[2 * i] = pi[(size_t)c * RDSP_BLOCK_SAMPLES + i];
-      dst[2 * i + 1] = pq[(size_t)c * RDSP_BLOCK_SAMPLES + i];
-    }
-  }
+  tiles_to_pairs(rdsp_block_data(bi), rdsp_block_data(bq), s->n_channels, s->h_iq.data(), RDSP_BLOCK_SAMPLES, 0);
   rdsp_release(bi); /* FFTIQ.cpp:114-115 (the previous block lives on the device) */
   rdsp_release(bq);
   int n_out = 0;
-  hipError_t e = hipSetDevice(s->device);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(s->d_iq, s->h_iq.data(), s->h_iq.size() * sizeof(int16_t), hipMemcpyHostToDevice, s->stream);
-  int rc = RDSP_OK;
-  if (e == hipSuccess)
-    rc = rdsp_spectrum_update(s->spec, s->d_iq, RDSP_BLOCK_SAMPLES, 1, s->d_out, 1, &n_out, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK && n_out > 0)
-    e = hipMemcpyAsync(s->h_out.data(), s->d_out, s->h_out.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess || rc != RDSP_OK) {
-    s->status = (rc != RDSP_OK) ? rc : RDSP_ERR_HIP;
-    if (e != hipSuccess) rdsp_set_error("spectrum node: %s", hipGetErrorString(e));
-    return;
-  }
+  const bool ok = s->dev.run("spectrum node", s->h_iq.data(), s->h_iq.size(), [&](int16_t *d_iq, uint16_t *d_out, hipStream_t st) {
+    return rdsp_spectrum_update(s->spec, d_iq, RDSP_BLOCK_SAMPLES, 1, d_out, 1, &n_out, st);
+  }, s->h_out.data(), s->h_out.size(), &n_out);
+  if (!ok) return;
   if (n_out > 0) s->outputflag = 1; /* FFTIQ.cpp:112 */
 }
 }  // namespace
@@ -226,22 +145,7 @@ extern "C" rdsp_node_t *rdsp_spectrum_node_create(rdsp_graph_t *g, rdsp_spectrum
   s->n_channels = rdsp_graph_channels(g);
   s->h_iq.assign((size_t)s->n_channels * RDSP_BLOCK_SAMPLES * 2, 0);
   s->h_out.assign((size_t)s->n_channels * 256, 0);
-  s->device = rdsp_spectrum_device(spec);
-  if (hipSetDevice(s->device) != hipSuccess ||
-      hipMalloc((void **)&s->d_iq, s->h_iq.size() * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_out, s->h_out.size() * sizeof(uint16_t)) != hipSuccess ||
-      hipStreamCreate(&s->stream) != hipSuccess) {
-    rdsp_set_error("rdsp_spectrum_node_create: device allocation failed");
-    spectrum_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_t *n = rdsp_node_create(g, 2, spectrum_update, s);
-  if (!n) {
-    spectrum_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_set_destructor(n, spectrum_destroy);
-  return n;
+  return make_node(g, 2, spectrum_update, s, "rdsp_spectrum_node_create", rdsp_spectrum_device(spec), s->h_iq.size(), s->h_out.size());
 }
 
 /* FFTIQ.h:62-68: true once per finished average, cleared by the call */
@@ -270,7 +174,7 @@ extern "C" float rdsp_spectrum_node_read_range(rdsp_node_t *n, int ch, unsigned 
 }
 extern "C" int rdsp_spectrum_node_status(rdsp_node_t *n) {
   SpectrumNode *s = static_cast<SpectrumNode *>(rdsp_node_user(n));
-  return s ? s->status : RDSP_ERR_INVALID;
+  return s ? s->dev.status : RDSP_ERR_INVALID;
 }
 
 /* ---- the reference's own engine objects as graph nodes -------------------------------------------------------------------
@@ -281,20 +185,10 @@ namespace {
 struct PairNode {
   rdsp_engine_t *engine = nullptr;
   rdsp_preproc_t *pre = nullptr;
-  int n_channels = 0, device = 0;
+  int n_channels = 0;
   std::vector<int16_t> h_in, h_out; /* [ch][128][2] */
-  int16_t *d_in = nullptr, *d_out = nullptr;
-  hipStream_t stream = nullptr;
-  int status = RDSP_OK;
+  NodeDev<> dev;
 };
-void pair_destroy(void *u) {
-  PairNode *s = static_cast<PairNode *>(u);
-  (void)hipSetDevice(s->device);
-  if (s->d_in) (void)hipFree(s->d_in);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
 void pair_update(rdsp_node_t *n, void *u) {
   PairNode *s = static_cast<PairNode *>(u);
   rdsp_block_t *bi = rdsp_receive_readonly(n, 0), *bq = rdsp_receive_readonly(n, 1);
@@ -303,36 +197,17 @@ void pair_update(rdsp_node_t *n, void *u) {
     rdsp_release(bq);
     return;
   }
-  const int16_t *pi = rdsp_block_data(bi), *pq = rdsp_block_data(bq);
-  for (int c = 0; c < s->n_channels; c++)
-    for (int i = 0; i < RDSP_BLOCK_SAMPLES; i++) {
-      s->h_in[((size_t)c * RDSP_BLOCK_SAMPLES + i) * 2] = pi[(size_t)c * RDSP_BLOCK_SAMPLES + i];
-      s->h_in[((size_t)c * RDSP_BLOCK_SAMPLES + i) * 2 + 1] = pq[(size_t)c * RDSP_BLOCK_SAMPLES + i];
-    }
+  tiles_to_pairs(rdsp_block_data(bi), rdsp_block_data(bq), s->n_channels, s->h_in.data(), RDSP_BLOCK_SAMPLES, 0);
   rdsp_release(bi);
   rdsp_release(bq);
-  hipError_t e = hipSetDevice(s->device);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->d_in, s->h_in.data(), s->h_in.size() * sizeof(int16_t), hipMemcpyHostToDevice, s->stream);
-  int rc = RDSP_OK;
-  if (e == hipSuccess)
-    rc = s->engine ? rdsp_engine_update(s->engine, s->d_in, RDSP_BLOCK_SAMPLES, 1, s->d_out, RDSP_BLOCK_SAMPLES, s->stream)
-                   : rdsp_preproc_update(s->pre, s->d_in, RDSP_BLOCK_SAMPLES, 1, s->d_out, RDSP_BLOCK_SAMPLES, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK)
-    e = hipMemcpyAsync(s->h_out.data(), s->d_out, s->h_out.size() * sizeof(int16_t), hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess && rc == RDSP_OK) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess || rc != RDSP_OK) {
-    s->status = rc != RDSP_OK ? rc : RDSP_ERR_HIP;
-    if (e != hipSuccess) rdsp_set_error("engine node: %s", hipGetErrorString(e));
-    return;
-  }
+  const bool ok = s->dev.run("engine node", s->h_in.data(), s->h_in.size(), [&](int16_t *d_in, int16_t *d_out, hipStream_t st) {
+    return s->engine ? rdsp_engine_update(s->engine, d_in, RDSP_BLOCK_SAMPLES, 1, d_out, RDSP_BLOCK_SAMPLES, st)
+                     : rdsp_preproc_update(s->pre, d_in, RDSP_BLOCK_SAMPLES, 1, d_out, RDSP_BLOCK_SAMPLES, st);
+  }, s->h_out.data(), s->h_out.size());
+  if (!ok) return;
   rdsp_block_t *b0 = rdsp_allocate(n), *b1 = rdsp_allocate(n);
   if (b0 && b1) {
-    int16_t *o0 = rdsp_block_data(b0), *o1 = rdsp_block_data(b1);
-    for (int c = 0; c < s->n_channels; c++)
-      for (int i = 0; i < RDSP_BLOCK_SAMPLES; i++) {
-        o0[(size_t)c * RDSP_BLOCK_SAMPLES + i] = s->h_out[((size_t)c * RDSP_BLOCK_SAMPLES + i) * 2];
-        o1[(size_t)c * RDSP_BLOCK_SAMPLES + i] = s->h_out[((size_t)c * RDSP_BLOCK_SAMPLES + i) * 2 + 1];
-      }
+    pairs_to_tiles(s->h_out.data(), RDSP_BLOCK_SAMPLES, 0, s->n_channels, rdsp_block_data(b0), rdsp_block_data(b1));
     rdsp_transmit(n, b0, 0);
     rdsp_transmit(n, b1, 1);
   }
@@ -347,19 +222,10 @@ rdsp_node_t *pair_create(rdsp_graph_t *g, rdsp_engine_t *engine, rdsp_preproc_t 
   }
   PairNode *s = new PairNode();
   s->engine = engine; s->pre = pre; s->n_channels = nch;
-  s->device = engine ? rdsp_engine_device(engine) : rdsp_preproc_device(pre);
   s->h_in.assign((size_t)nch * RDSP_BLOCK_SAMPLES * 2, 0);
   s->h_out.assign(s->h_in.size(), 0);
-  if (hipSetDevice(s->device) != hipSuccess || hipMalloc((void **)&s->d_in, s->h_in.size() * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void **)&s->d_out, s->h_in.size() * sizeof(int16_t)) != hipSuccess || hipStreamCreate(&s->stream) != hipSuccess) {
-    rdsp_set_error("engine / pre-processor node: device allocation failed");
-    pair_destroy(s);
-    return nullptr;
-  }
-  rdsp_node_t *n = rdsp_node_create(g, 2, pair_update, s);
-  if (!n) { pair_destroy(s); return nullptr; }
-  rdsp_node_set_destructor(n, pair_destroy);
-  return n;
+  return make_node(g, 2, pair_update, s, "engine / pre-processor node", engine ? rdsp_engine_device(engine) : rdsp_preproc_device(pre),
+                   s->h_in.size(), s->h_in.size());
 }
 }  // namespace
 
@@ -367,5 +233,5 @@ extern "C" rdsp_node_t *rdsp_engine_node_create(rdsp_graph_t *g, rdsp_engine_t *
 extern "C" rdsp_node_t *rdsp_preproc_node_create(rdsp_graph_t *g, rdsp_preproc_t *p) { return p ? pair_create(g, nullptr, p) : nullptr; }
 extern "C" int rdsp_engine_node_status(rdsp_node_t *n) {
   PairNode *s = static_cast<PairNode *>(rdsp_node_user(n));
-  return s ? s->status : RDSP_ERR_INVALID;
+  return s ? s->dev.status : RDSP_ERR_INVALID;
 }

@@ -22,6 +22,7 @@
 
 #include <vector>
 
+#include "rdsp_dev.h"
 #include "rdsp_host.h"
 #include "rdsp_q15.h"
 #include "rdsp_sync.h"
@@ -174,25 +175,16 @@ struct rdsp_spectrum {
   int naverage;
   int has_window; /* `const int16_t *window` non-NULL, FFTIQ.h:101, FFTIQ.cpp:81 */
   int have_prev, count;
-  int16_t *d_window = nullptr;
-  uint16_t *d_guess = nullptr;
-  uint32_t *d_twid = nullptr, *d_prev = nullptr, *d_sum = nullptr;
+  rdsp_dev::DevBuf<int16_t> d_window;
+  rdsp_dev::DevBuf<uint16_t> d_guess;
+  rdsp_dev::DevBuf<uint32_t> d_twid, d_prev, d_sum;
 };
-
-#define SPEC_TRY(expr)                                                          \
-  do {                                                                          \
-    hipError_t e_ = (expr);                                                     \
-    if (e_ != hipSuccess) {                                                     \
-      rdsp_set_error("%s failed: %s", #expr, hipGetErrorString(e_));            \
-      return RDSP_ERR_HIP;                                                      \
-    }                                                                           \
-  } while (0)
 
 /* windowFunction(const int16_t *w), FFTIQ.h:93-95: the analyser keeps the caller's table (a copy
  * here: the table lives in device memory); NULL switches the window off (FFTIQ.cpp:81) */
 static int upload_window(rdsp_spectrum_t *s, const int16_t *w256) {
   s->has_window = w256 != nullptr;
-  if (w256) SPEC_TRY(hipMemcpy(s->d_window, w256, 256 * sizeof(int16_t), hipMemcpyHostToDevice));
+  if (w256) HIP_TRY(hipMemcpy(s->d_window, w256, 256 * sizeof(int16_t), hipMemcpyHostToDevice));
   return RDSP_OK;
 }
 static int upload_window_id(rdsp_spectrum_t *s, int window_id) {
@@ -204,6 +196,22 @@ static int upload_window_id(rdsp_spectrum_t *s, int window_id) {
   }
   rdsp_window_q15(window_id, w);
   return upload_window(s, w);
+}
+static int spectrum_setup(rdsp_spectrum_t *s, int window_id) {
+  const size_t nch = (size_t)s->n_channels;
+  uint32_t tw[192];
+  rdsp_q15_twiddles(256, tw);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->d_window.alloc(256));
+  HIP_TRY(s->d_twid.alloc(192));
+  HIP_TRY(s->d_guess.alloc(33));
+  HIP_TRY(s->d_prev.alloc(nch * 128));
+  HIP_TRY(s->d_sum.alloc(nch * 256));
+  HIP_TRY(hipMemset(s->d_prev, 0, nch * 128 * sizeof(uint32_t)));
+  HIP_TRY(hipMemset(s->d_sum, 0, nch * 256 * sizeof(uint32_t)));
+  HIP_TRY(hipMemcpy(s->d_twid, tw, sizeof(tw), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->d_guess, rdsp_sqrt_guess_table(), 33 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  return upload_window_id(s, window_id);
 }
 
 /* AudioAnalyzeFFT256IQ() with explicit settings (the constructor's own are rdsp_spectrum_create_default) */
@@ -224,27 +232,8 @@ extern "C" int rdsp_spectrum_create(int n_channels, int device, int naverage, in
   s->has_window = 0;
   s->have_prev = 0;
   s->count = 0;
-  uint32_t tw[192];
-  rdsp_q15_twiddles(256, tw);
-  auto setup = [&]() -> int { /* on any failure the half-made object is destroyed below, not leaked */
-    SPEC_TRY(hipSetDevice(device));
-    SPEC_TRY(hipMalloc((void **)&s->d_window, 256 * sizeof(int16_t)));
-    SPEC_TRY(hipMalloc((void **)&s->d_twid, 192 * sizeof(uint32_t)));
-    SPEC_TRY(hipMalloc((void **)&s->d_guess, 33 * sizeof(uint16_t)));
-    SPEC_TRY(hipMalloc((void **)&s->d_prev, (size_t)n_channels * 128 * sizeof(uint32_t)));
-    SPEC_TRY(hipMalloc((void **)&s->d_sum, (size_t)n_channels * 256 * sizeof(uint32_t)));
-    SPEC_TRY(hipMemset(s->d_prev, 0, (size_t)n_channels * 128 * sizeof(uint32_t)));
-    SPEC_TRY(hipMemset(s->d_sum, 0, (size_t)n_channels * 256 * sizeof(uint32_t)));
-    SPEC_TRY(hipMemcpy(s->d_twid, tw, sizeof(tw), hipMemcpyHostToDevice));
-    SPEC_TRY(hipMemcpy(s->d_guess, rdsp_sqrt_guess_table(), 33 * sizeof(uint16_t), hipMemcpyHostToDevice));
-    return RDSP_OK;
-  };
-  if (setup() != RDSP_OK) {
-    rdsp_spectrum_destroy(s);
-    return RDSP_ERR_HIP;
-  }
-  int rc = upload_window_id(s, window_id);
-  if (rc != RDSP_OK) {
+  const int rc = spectrum_setup(s, window_id);
+  if (rc != RDSP_OK) { /* the half-made object is destroyed, not leaked */
     rdsp_spectrum_destroy(s);
     return rc;
   }
@@ -260,11 +249,6 @@ extern "C" int rdsp_spectrum_device(const rdsp_spectrum_t *s) { return s ? s->de
 extern "C" void rdsp_spectrum_destroy(rdsp_spectrum_t *s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  (void)hipFree(s->d_window);
-  (void)hipFree(s->d_twid);
-  (void)hipFree(s->d_guess);
-  (void)hipFree(s->d_prev);
-  (void)hipFree(s->d_sum);
   delete s;
 }
 
@@ -275,16 +259,16 @@ extern "C" int rdsp_spectrum_averageTogether(rdsp_spectrum_t *s, int n) { /* FFT
 }
 extern "C" int rdsp_spectrum_windowFunction(rdsp_spectrum_t *s, int window_id) { /* FFTIQ.h:93-95 */
   if (!s) return RDSP_ERR_INVALID;
-  SPEC_TRY(hipSetDevice(s->device));
-  SPEC_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
   return upload_window_id(s, window_id);
 }
 /* void windowFunction(const int16_t *w), FFTIQ.h:93-95, with the reference's own argument: a
  * host pointer to 256 q15 taps (e.g. AudioWindowHanning256, INO:144), or NULL for no window */
 extern "C" int rdsp_spectrum_windowFunction_table(rdsp_spectrum_t *s, const int16_t *w256) {
   if (!s) return RDSP_ERR_INVALID;
-  SPEC_TRY(hipSetDevice(s->device));
-  SPEC_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
   return upload_window(s, w256);
 }
 
@@ -337,7 +321,7 @@ extern "C" int rdsp_spectrum_update(rdsp_spectrum_t *s, const int16_t *d_iq, siz
     rdsp_set_error("rdsp_spectrum_update: output buffer holds %zu spectra per channel, %d needed", out_stride, nout);
     return RDSP_ERR_INVALID;
   }
-  SPEC_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->device));
   RdspSpecParams p;
   memset(&p, 0, sizeof(p));
   p.iq = reinterpret_cast<const uint32_t *>(d_iq);

@@ -14,21 +14,168 @@
 
 #include <chrono>
 
+#include "rdsp_dev.h"
 #include "rdsp_host.h"
 
-#define HIP_TRYS(expr)                                                             \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      rdsp_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      rc = RDSP_ERR_HIP;                                                           \
-      goto done;                                                                   \
-    }                                                                              \
-  } while (0)
+namespace {
+using namespace rdsp_dev;
 
-static double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+/* what a run has done so far */
+struct Progress {
+  int64_t blocks = 0;
+  double t_read = 0.0, t_write = 0.0; /* inside the source and the sink */
+  const double t_begin = now_s();
+};
+void fill_stats(rdsp_stream_stats_t *stats, const Progress &r, int decim) {
+  if (!stats) return;
+  stats->blocks = r.blocks;
+  stats->samples_in = r.blocks * RDSP_BLOCK_SAMPLES;
+  stats->samples_out = r.blocks * RDSP_BLOCK_SAMPLES / decim;
+  stats->seconds = now_s() - r.t_begin;
+  stats->read_seconds = r.t_read;
+  stats->write_seconds = r.t_write;
 }
+
+int check_call_unit(rdsp_chain_t *c, int blocks_per_call) {
+  const int gran = rdsp_chain_call_unit_blocks(c);
+  if (blocks_per_call <= 0 || blocks_per_call % gran != 0) {
+    rdsp_set_error("blocks_per_call %d is not a multiple of the call unit %d", blocks_per_call, gran);
+    return RDSP_ERR_NOT_READY;
+  }
+  return RDSP_OK;
+}
+/* a run's buffers, streams and events live on the chain's device, whatever the calling thread had selected (a host that
+ * drives several GPUs from one process) */
+int use_chain_device(rdsp_chain_t *c) {
+  if (hipSetDevice(rdsp_chain_device(c)) != hipSuccess) {
+    rdsp_set_error("hipSetDevice(%d) failed", rdsp_chain_device(c));
+    return RDSP_ERR_HIP;
+  }
+  return RDSP_OK;
+}
+
+/* The three streams and two device slots both runners drive: batch `it` goes through slot it & 1, uploaded on s_up, computed
+ * on s_comp, downloaded on s_down; the events order a slot's three steps and keep batch it + 2 off a slot still in use.
+ * Rows are IQ pairs per channel; `contiguous` is a whole slot in one copy (host rows at the slot's pitch, all of them full). */
+struct Pipeline {
+  rdsp_chain_t *c = nullptr;
+  size_t nch = 0, in_row = 0, out_row = 0; /* a slot: [nch][in_row][2] in, [nch][out_row][2] out */
+  DevBuf<int16_t> din[2], dout[2];
+  Stream s_up, s_comp, s_down;
+  Event ev_up[2], ev_comp[2], ev_down[2];
+
+  int create(rdsp_chain_t *chain, int blocks_per_call) {
+    c = chain;
+    nch = (size_t)rdsp_chain_channels(c);
+    in_row = (size_t)blocks_per_call * RDSP_BLOCK_SAMPLES;
+    out_row = in_row / (size_t)rdsp_chain_decim(c);
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(din[i].alloc(in_row * 2 * nch));
+      HIP_TRY(dout[i].alloc(out_row * 2 * nch));
+      HIP_TRY(ev_up[i].create(hipEventDisableTiming));
+      HIP_TRY(ev_comp[i].create(hipEventDisableTiming));
+      HIP_TRY(ev_down[i].create(hipEventDisableTiming));
+    }
+    HIP_TRY(s_up.create(hipStreamNonBlocking));
+    HIP_TRY(s_comp.create(hipStreamNonBlocking));
+    HIP_TRY(s_down.create(hipStreamNonBlocking));
+    return RDSP_OK;
+  }
+  /* after the compute of two batches ago has finished reading din[slot] */
+  int upload(int slot, int64_t it, const int16_t *src, size_t src_pitch, size_t pairs, bool contiguous) {
+    if (it >= 2) HIP_TRY(hipStreamWaitEvent(s_up, ev_comp[slot], 0));
+    if (contiguous) HIP_TRY(hipMemcpyAsync(din[slot], src, in_row * 4 * nch, hipMemcpyHostToDevice, s_up));
+    else HIP_TRY(hipMemcpy2DAsync(din[slot], in_row * 4, src, src_pitch * 4, pairs * 4, nch, hipMemcpyHostToDevice, s_up));
+    HIP_TRY(hipEventRecord(ev_up[slot], s_up));
+    return RDSP_OK;
+  }
+  /* needs the upload, and dout[slot] drained by the download of two batches ago; s_down then waits for the whole chain of
+   * this batch (pipelined mode: its tail stage) */
+  int compute(int slot, int64_t it, int blocks) {
+    HIP_TRY(hipStreamWaitEvent(s_comp, ev_up[slot], 0));
+    if (it >= 2) HIP_TRY(hipStreamWaitEvent(s_comp, ev_down[slot], 0));
+    RC_TRY(rdsp_chain_process(c, din[slot], in_row, blocks, dout[slot], out_row, nullptr, s_comp));
+    HIP_TRY(hipEventRecord(ev_comp[slot], s_comp));
+    HIP_TRY(hipStreamWaitEvent(s_down, ev_comp[slot], 0));
+    return rdsp_chain_flush(c, s_down);
+  }
+  int download(int slot, int16_t *dst, size_t dst_pitch, size_t pairs, bool contiguous) {
+    if (contiguous) HIP_TRY(hipMemcpyAsync(dst, dout[slot], out_row * 4 * nch, hipMemcpyDeviceToHost, s_down));
+    else HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * 4, dout[slot], out_row * 4, pairs * 4, nch, hipMemcpyDeviceToHost, s_down));
+    HIP_TRY(hipEventRecord(ev_down[slot], s_down));
+    return RDSP_OK;
+  }
+  int wait_up(int slot) { HIP_TRY(hipEventSynchronize(ev_up[slot])); return RDSP_OK; }
+  int wait_down(int slot) { HIP_TRY(hipEventSynchronize(ev_down[slot])); return RDSP_OK; }
+  void drain() { /* before a run returns, failed or not: nothing of it is in flight when its buffers go */
+    for (hipStream_t s : {s_up.s, s_comp.s, s_down.s})
+      if (s) (void)hipStreamSynchronize(s);
+  }
+};
+
+/* the staged runner: the callbacks fill and empty two slots of pinned host memory, so that reading the next batch, the copies
+ * and the kernels of consecutive batches overlap; the host only ever waits for the download of the batch before the one it
+ * just queued */
+struct Staged {
+  Pipeline p;
+  PinnedBuf<int16_t> hin[2], hout[2];
+  int out_pairs[2] = {0, 0}; /* what hout[slot] holds for the sink */
+  rdsp_sink_fn sink;
+  void *sink_user;
+
+  int hand_over(int slot, Progress &r) {
+    if (out_pairs[slot] <= 0) return RDSP_OK;
+    RC_TRY(p.wait_down(slot));
+    const double t0 = now_s();
+    const int w = sink(sink_user, hout[slot], p.out_row, out_pairs[slot]); /* Q_out_L/R.playBuffer(), CONV:344-349 */
+    r.t_write += now_s() - t0;
+    out_pairs[slot] = 0;
+    if (w < 0) {
+      rdsp_set_error("stream sink failed (%d)", w);
+      return RDSP_ERR_INVALID;
+    }
+    return RDSP_OK;
+  }
+  int run(rdsp_chain_t *c, rdsp_source_fn source, void *source_user, int blocks_per_call, int64_t max_blocks, Progress &r) {
+    const int gran = rdsp_chain_call_unit_blocks(c), decim = rdsp_chain_decim(c);
+    RC_TRY(p.create(c, blocks_per_call));
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(hin[i].alloc(p.in_row * 2 * p.nch));
+      HIP_TRY(hout[i].alloc(p.out_row * 2 * p.nch));
+    }
+    int64_t it = 0;
+    for (bool ended = false; !ended; it++) {
+      const int slot = (int)(it & 1);
+      int want = blocks_per_call;
+      if (max_blocks > 0 && max_blocks - r.blocks < (int64_t)want) want = (int)(max_blocks - r.blocks);
+      want -= want % gran;
+      if (want <= 0) break;
+      if (it >= 2) RC_TRY(p.wait_up(slot)); /* the pinned input slot is free again */
+      const double t0 = now_s();
+      int got = source(source_user, hin[slot], p.in_row, want); /* Q_in_L/R.readBuffer(), CONV:236-244 */
+      r.t_read += now_s() - t0;
+      if (got < 0) {
+        rdsp_set_error("stream source failed (%d)", got);
+        return RDSP_ERR_INVALID;
+      }
+      if (got < want) ended = true; /* the sketch would keep waiting for a full granule (CONV:231): stop */
+      got -= got % gran;
+      if (got > 0) {
+        const bool full = got == blocks_per_call;
+        RC_TRY(p.upload(slot, it, hin[slot], p.in_row, (size_t)got * RDSP_BLOCK_SAMPLES, full));
+        RC_TRY(p.compute(slot, it, got));
+        out_pairs[slot] = got * RDSP_BLOCK_SAMPLES / decim;
+        RC_TRY(p.download(slot, hout[slot], p.out_row, (size_t)out_pairs[slot], full));
+        r.blocks += got;
+      }
+      RC_TRY(hand_over(slot ^ 1, r)); /* the previous batch goes to the sink while this one is in flight */
+    }
+    return hand_over((int)((it - 1) & 1), r); /* the last batch */
+  }
+};
+}  // namespace
 
 extern "C" int rdsp_stream_run(rdsp_chain_t *c, rdsp_source_fn source, void *source_user, rdsp_sink_fn sink,
                                void *sink_user, int blocks_per_call, int64_t max_blocks,
@@ -37,149 +184,15 @@ extern "C" int rdsp_stream_run(rdsp_chain_t *c, rdsp_source_fn source, void *sou
     rdsp_set_error("rdsp_stream_run: bad argument");
     return RDSP_ERR_INVALID;
   }
-  const int gran = rdsp_chain_call_unit_blocks(c);
-  if (blocks_per_call % gran != 0) {
-    rdsp_set_error("blocks_per_call %d is not a multiple of the call unit %d", blocks_per_call, gran);
-    return RDSP_ERR_NOT_READY;
-  }
-  /* the runner's buffers, streams and events live on the chain's device, whatever the calling thread had
-   * selected (a host that drives several GPUs from one process) */
-  if (hipSetDevice(rdsp_chain_device(c)) != hipSuccess) {
-    rdsp_set_error("hipSetDevice(%d) failed", rdsp_chain_device(c));
-    return RDSP_ERR_HIP;
-  }
-  const int nch = rdsp_chain_channels(c);
-  const int decim = rdsp_chain_decim(c);
-  const size_t in_stride = (size_t)blocks_per_call * RDSP_BLOCK_SAMPLES; /* IQ pairs per channel row */
-  const size_t out_stride = in_stride / (size_t)decim;
-  const size_t in_bytes = in_stride * 4 * (size_t)nch, out_bytes = out_stride * 4 * (size_t)nch;
-
-  int rc = RDSP_OK;
-  int16_t *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
-          *dout[2] = {nullptr, nullptr};
-  hipStream_t s_up = nullptr, s_comp = nullptr, s_down = nullptr;
-  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
-  int out_pairs[2] = {0, 0};
-  int64_t done_blocks = 0;
-  double t_read = 0.0, t_write = 0.0;
-  const double t_begin = now_s();
-  bool ended = false;
-  int64_t it = 0;
-
-  for (int i = 0; i < 2; i++) {
-    HIP_TRYS(hipHostMalloc((void **)&hin[i], in_bytes, hipHostMallocDefault));
-    HIP_TRYS(hipHostMalloc((void **)&hout[i], out_bytes, hipHostMallocDefault));
-    HIP_TRYS(hipMalloc((void **)&din[i], in_bytes));
-    HIP_TRYS(hipMalloc((void **)&dout[i], out_bytes));
-    HIP_TRYS(hipEventCreateWithFlags(&ev_up[i], hipEventDisableTiming));
-    HIP_TRYS(hipEventCreateWithFlags(&ev_comp[i], hipEventDisableTiming));
-    HIP_TRYS(hipEventCreateWithFlags(&ev_down[i], hipEventDisableTiming));
-  }
-  HIP_TRYS(hipStreamCreateWithFlags(&s_up, hipStreamNonBlocking));
-  HIP_TRYS(hipStreamCreateWithFlags(&s_comp, hipStreamNonBlocking));
-  HIP_TRYS(hipStreamCreateWithFlags(&s_down, hipStreamNonBlocking));
-
-  for (; !ended; it++) {
-    const int slot = (int)(it & 1);
-    int want = blocks_per_call;
-    if (max_blocks > 0 && max_blocks - done_blocks < (int64_t)want) want = (int)(max_blocks - done_blocks);
-    want -= want % gran;
-    if (want <= 0) break;
-    if (it >= 2) HIP_TRYS(hipEventSynchronize(ev_up[slot])); /* the pinned input slot is free again */
-    double t0 = now_s();
-    int got = source(source_user, hin[slot], in_stride, want); /* Q_in_L/R.readBuffer(), CONV:236-244 */
-    t_read += now_s() - t0;
-    if (got < 0) {
-      rdsp_set_error("stream source failed (%d)", got);
-      rc = RDSP_ERR_INVALID;
-      goto done;
-    }
-    if (got < want) ended = true; /* the sketch would keep waiting for a full granule (CONV:231): stop */
-    got -= got % gran;
-    if (got > 0) {
-      /* upload: the compute of two batches ago has finished reading din[slot] */
-      if (it >= 2) HIP_TRYS(hipStreamWaitEvent(s_up, ev_comp[slot], 0));
-      if (got == blocks_per_call) {
-        HIP_TRYS(hipMemcpyAsync(din[slot], hin[slot], in_bytes, hipMemcpyHostToDevice, s_up));
-      } else {
-        HIP_TRYS(hipMemcpy2DAsync(din[slot], in_stride * 4, hin[slot], in_stride * 4, (size_t)got * RDSP_BLOCK_SAMPLES * 4,
-                                  (size_t)nch, hipMemcpyHostToDevice, s_up));
-      }
-      HIP_TRYS(hipEventRecord(ev_up[slot], s_up));
-      /* compute: needs the upload, and dout[slot] drained by the download of two batches ago */
-      HIP_TRYS(hipStreamWaitEvent(s_comp, ev_up[slot], 0));
-      if (it >= 2) HIP_TRYS(hipStreamWaitEvent(s_comp, ev_down[slot], 0));
-      rc = rdsp_chain_process(c, din[slot], in_stride, got, dout[slot], out_stride, nullptr, s_comp);
-      if (rc != RDSP_OK) goto done;
-      HIP_TRYS(hipEventRecord(ev_comp[slot], s_comp));
-      /* download: after the whole chain of this batch (pipelined mode: its tail stage) */
-      HIP_TRYS(hipStreamWaitEvent(s_down, ev_comp[slot], 0));
-      rc = rdsp_chain_flush(c, s_down);
-      if (rc != RDSP_OK) goto done;
-      out_pairs[slot] = got * RDSP_BLOCK_SAMPLES / decim;
-      if (got == blocks_per_call) {
-        HIP_TRYS(hipMemcpyAsync(hout[slot], dout[slot], out_bytes, hipMemcpyDeviceToHost, s_down));
-      } else {
-        HIP_TRYS(hipMemcpy2DAsync(hout[slot], out_stride * 4, dout[slot], out_stride * 4, (size_t)out_pairs[slot] * 4,
-                                  (size_t)nch, hipMemcpyDeviceToHost, s_down));
-      }
-      HIP_TRYS(hipEventRecord(ev_down[slot], s_down));
-      done_blocks += got;
-    } else {
-      out_pairs[slot] = 0;
-    }
-    /* hand the previous batch to the sink while this one is in flight */
-    if (it >= 1 && out_pairs[slot ^ 1] > 0) {
-      HIP_TRYS(hipEventSynchronize(ev_down[slot ^ 1]));
-      t0 = now_s();
-      const int w = sink(sink_user, hout[slot ^ 1], out_stride, out_pairs[slot ^ 1]); /* Q_out_L/R.playBuffer(), CONV:344-349 */
-      t_write += now_s() - t0;
-      out_pairs[slot ^ 1] = 0;
-      if (w < 0) {
-        rdsp_set_error("stream sink failed (%d)", w);
-        rc = RDSP_ERR_INVALID;
-        goto done;
-      }
-    }
-  }
-  { /* the last batch */
-    const int last = (int)((it - 1) & 1);
-    if (it >= 1 && out_pairs[last] > 0) {
-      HIP_TRYS(hipEventSynchronize(ev_down[last]));
-      const double t0 = now_s();
-      const int w = sink(sink_user, hout[last], out_stride, out_pairs[last]);
-      t_write += now_s() - t0;
-      if (w < 0) {
-        rdsp_set_error("stream sink failed (%d)", w);
-        rc = RDSP_ERR_INVALID;
-      }
-    }
-  }
-
-done:
-  if (s_up) (void)hipStreamSynchronize(s_up);
-  if (s_comp) (void)hipStreamSynchronize(s_comp);
-  if (s_down) (void)hipStreamSynchronize(s_down);
-  if (stats) {
-    stats->blocks = done_blocks;
-    stats->samples_in = done_blocks * RDSP_BLOCK_SAMPLES;
-    stats->samples_out = done_blocks * RDSP_BLOCK_SAMPLES / decim;
-    stats->seconds = now_s() - t_begin;
-    stats->read_seconds = t_read;
-    stats->write_seconds = t_write;
-  }
-  for (int i = 0; i < 2; i++) {
-    if (hin[i]) (void)hipHostFree(hin[i]);
-    if (hout[i]) (void)hipHostFree(hout[i]);
-    if (din[i]) (void)hipFree(din[i]);
-    if (dout[i]) (void)hipFree(dout[i]);
-    if (ev_up[i]) (void)hipEventDestroy(ev_up[i]);
-    if (ev_comp[i]) (void)hipEventDestroy(ev_comp[i]);
-    if (ev_down[i]) (void)hipEventDestroy(ev_down[i]);
-  }
-  if (s_up) (void)hipStreamDestroy(s_up);
-  if (s_comp) (void)hipStreamDestroy(s_comp);
-  if (s_down) (void)hipStreamDestroy(s_down);
+  RC_TRY(check_call_unit(c, blocks_per_call));
+  RC_TRY(use_chain_device(c));
+  Staged st;
+  st.sink = sink;
+  st.sink_user = sink_user;
+  Progress r;
+  const int rc = st.run(c, source, source_user, blocks_per_call, max_blocks, r);
+  st.p.drain();
+  fill_stats(stats, r, rdsp_chain_decim(c));
   return rc;
 }
 
@@ -267,79 +280,33 @@ static bool is_pinned_host(const void *p) {
   return a.type == hipMemoryTypeHost;
 }
 
-static int stream_pinned(rdsp_chain_t *c, const int16_t *host_iq, size_t in_stride, int64_t n_blocks, int16_t *host_out,
-                         size_t out_stride, int blocks_per_call, rdsp_stream_stats_t *stats) {
+static int pinned_batches(Pipeline &p, rdsp_chain_t *c, const int16_t *host_iq, size_t in_stride, int64_t n_blocks, int16_t *host_out,
+                          size_t out_stride, int blocks_per_call, Progress &r) {
   const int gran = rdsp_chain_call_unit_blocks(c);
-  if (blocks_per_call <= 0 || blocks_per_call % gran != 0) {
-    rdsp_set_error("blocks_per_call %d is not a multiple of the call unit %d", blocks_per_call, gran);
-    return RDSP_ERR_NOT_READY;
-  }
-  if (hipSetDevice(rdsp_chain_device(c)) != hipSuccess) {
-    rdsp_set_error("hipSetDevice(%d) failed", rdsp_chain_device(c));
-    return RDSP_ERR_HIP;
-  }
-  const int nch = rdsp_chain_channels(c), decim = rdsp_chain_decim(c);
-  const size_t d_in = (size_t)blocks_per_call * RDSP_BLOCK_SAMPLES, d_out = d_in / (size_t)decim;
-  int rc = RDSP_OK;
-  int16_t *din[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr};
-  hipStream_t s_up = nullptr, s_comp = nullptr, s_down = nullptr;
-  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
-  int64_t done = 0, it = 0;
-  const double t_begin = now_s();
-  for (int i = 0; i < 2; i++) {
-    HIP_TRYS(hipMalloc((void **)&din[i], d_in * 4 * (size_t)nch));
-    HIP_TRYS(hipMalloc((void **)&dout[i], d_out * 4 * (size_t)nch));
-    HIP_TRYS(hipEventCreateWithFlags(&ev_up[i], hipEventDisableTiming));
-    HIP_TRYS(hipEventCreateWithFlags(&ev_comp[i], hipEventDisableTiming));
-    HIP_TRYS(hipEventCreateWithFlags(&ev_down[i], hipEventDisableTiming));
-  }
-  HIP_TRYS(hipStreamCreateWithFlags(&s_up, hipStreamNonBlocking));
-  HIP_TRYS(hipStreamCreateWithFlags(&s_comp, hipStreamNonBlocking));
-  HIP_TRYS(hipStreamCreateWithFlags(&s_down, hipStreamNonBlocking));
-  for (; done < n_blocks; it++) {
+  const size_t decim = (size_t)rdsp_chain_decim(c);
+  RC_TRY(p.create(c, blocks_per_call));
+  for (int64_t it = 0; r.blocks < n_blocks; it++) {
     const int slot = (int)(it & 1);
-    int take = (int)((n_blocks - done) < (int64_t)blocks_per_call ? (n_blocks - done) : (int64_t)blocks_per_call);
+    int take = (int)((n_blocks - r.blocks) < (int64_t)blocks_per_call ? (n_blocks - r.blocks) : (int64_t)blocks_per_call);
     take -= take % gran;
     if (take <= 0) break;
-    const size_t pin = (size_t)take * RDSP_BLOCK_SAMPLES, pout = pin / (size_t)decim;
-    if (it >= 2) HIP_TRYS(hipStreamWaitEvent(s_up, ev_comp[slot], 0)); /* din[slot] consumed */
-    HIP_TRYS(hipMemcpy2DAsync(din[slot], d_in * 4, host_iq + (size_t)done * RDSP_BLOCK_SAMPLES * 2, in_stride * 4, pin * 4,
-                              (size_t)nch, hipMemcpyHostToDevice, s_up));
-    HIP_TRYS(hipEventRecord(ev_up[slot], s_up));
-    HIP_TRYS(hipStreamWaitEvent(s_comp, ev_up[slot], 0));
-    if (it >= 2) HIP_TRYS(hipStreamWaitEvent(s_comp, ev_down[slot], 0)); /* dout[slot] drained */
-    rc = rdsp_chain_process(c, din[slot], d_in, take, dout[slot], d_out, nullptr, s_comp);
-    if (rc != RDSP_OK) goto done;
-    HIP_TRYS(hipEventRecord(ev_comp[slot], s_comp));
-    HIP_TRYS(hipStreamWaitEvent(s_down, ev_comp[slot], 0));
-    rc = rdsp_chain_flush(c, s_down);
-    if (rc != RDSP_OK) goto done;
-    HIP_TRYS(hipMemcpy2DAsync(host_out + (size_t)done * RDSP_BLOCK_SAMPLES / (size_t)decim * 2, out_stride * 4, dout[slot],
-                              d_out * 4, pout * 4, (size_t)nch, hipMemcpyDeviceToHost, s_down));
-    HIP_TRYS(hipEventRecord(ev_down[slot], s_down));
-    done += take;
+    const size_t at = (size_t)r.blocks * RDSP_BLOCK_SAMPLES, pairs = (size_t)take * RDSP_BLOCK_SAMPLES;
+    RC_TRY(p.upload(slot, it, host_iq + at * 2, in_stride, pairs, false));
+    RC_TRY(p.compute(slot, it, take));
+    RC_TRY(p.download(slot, host_out + at / decim * 2, out_stride, pairs / decim, false));
+    r.blocks += take;
   }
-done:
-  if (s_up) (void)hipStreamSynchronize(s_up);
-  if (s_comp) (void)hipStreamSynchronize(s_comp);
-  if (s_down) (void)hipStreamSynchronize(s_down);
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-    stats->blocks = done;
-    stats->samples_in = done * RDSP_BLOCK_SAMPLES;
-    stats->samples_out = done * RDSP_BLOCK_SAMPLES / decim;
-    stats->seconds = now_s() - t_begin;
-  }
-  for (int i = 0; i < 2; i++) {
-    if (din[i]) (void)hipFree(din[i]);
-    if (dout[i]) (void)hipFree(dout[i]);
-    if (ev_up[i]) (void)hipEventDestroy(ev_up[i]);
-    if (ev_comp[i]) (void)hipEventDestroy(ev_comp[i]);
-    if (ev_down[i]) (void)hipEventDestroy(ev_down[i]);
-  }
-  if (s_up) (void)hipStreamDestroy(s_up);
-  if (s_comp) (void)hipStreamDestroy(s_comp);
-  if (s_down) (void)hipStreamDestroy(s_down);
+  return RDSP_OK;
+}
+static int stream_pinned(rdsp_chain_t *c, const int16_t *host_iq, size_t in_stride, int64_t n_blocks, int16_t *host_out,
+                         size_t out_stride, int blocks_per_call, rdsp_stream_stats_t *stats) {
+  RC_TRY(check_call_unit(c, blocks_per_call));
+  RC_TRY(use_chain_device(c));
+  Pipeline p;
+  Progress r;
+  const int rc = pinned_batches(p, c, host_iq, in_stride, n_blocks, host_out, out_stride, blocks_per_call, r);
+  p.drain();
+  fill_stats(stats, r, rdsp_chain_decim(c));
   return rc;
 }
 

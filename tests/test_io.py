@@ -191,6 +191,75 @@ def test_memory_runner_and_callbacks(rdsp, torch_cuda):
 
 
 @pytest.mark.gpu
+def test_runner_stops_cleanly_when_a_callback_refuses(rdsp, torch_cuda):
+    """rdsp_stream_run's failure path: a source or a sink that returns a negative number ends the run with
+    RDSP_ERR_INVALID; the batches already queued are drained (the chain's state stands at what was processed, the
+    statistics say so), nothing is left in flight, and the next run is a normal one."""
+    import ctypes as C
+    torch = torch_cuda
+    from radiodsp_sdr_rx_amd import _lib
+    from radiodsp_sdr_rx_amd.chain import Chain, synth_iq
+    from radiodsp_sdr_rx_amd.io import stream_callbacks
+    lib = _lib.load()
+    RDSP_ERR_INVALID = -1      # include/rdsp.h
+    nch, per, batches = 2, 8, 5
+    iq = synth_iq(nch, batches * per * 128)
+    batch = lambda k: np.ascontiguousarray(iq[:, k * per * 128:(k + 1) * per * 128])
+    resident = lambda chain, k: chain.process(torch.from_numpy(batch(k)).cuda()).cpu().numpy()
+    ref_chain = Chain(nch, max_blocks_per_call=per, **K1)
+    ref = [resident(ref_chain, k) for k in range(batches)]
+
+    def run(chain, source, sink):
+        calls = {"source": 0, "sink": 0}
+        got = []
+
+        def _src(_user, dst, stride, n_blocks):
+            k = calls["source"]
+            calls["source"] += 1
+            if source(k) < 0:
+                return -1
+            if k >= batches:
+                return 0
+            np.ctypeslib.as_array(dst, (nch, stride, 2))[:, :per * 128] = batch(k)
+            return per
+
+        def _snk(_user, src, stride, n_pairs):
+            k = calls["sink"]
+            calls["sink"] += 1
+            if sink(k) < 0:
+                return -1
+            got.append(np.ctypeslib.as_array(src, (nch, stride, 2))[:, :n_pairs].copy())
+            return n_pairs
+
+        st = _lib.StreamStats()
+        cs, ck = _lib.SOURCE_FN(_src), _lib.SINK_FN(_snk)
+        rc = lib.rdsp_stream_run(chain.h, cs, None, ck, None, per, 0, C.byref(st))
+        return rc, st, got
+
+    # (a) the source refuses on its third call: batches 0 and 1 are processed, the sink has seen batch 0 only
+    ch = Chain(nch, max_blocks_per_call=per, **K1)
+    rc, st, got = run(ch, lambda k: -1 if k == 2 else 0, lambda k: 0)
+    assert rc == RDSP_ERR_INVALID
+    assert len(got) == 1 and np.array_equal(got[0], ref[0])
+    assert st.blocks == 2 * per
+    assert np.array_equal(resident(ch, 2), ref[2])        # drained, and the chain's state stands at two batches
+    # (b) the sink refuses on its first call; a fresh run on a fresh chain is then complete and correct
+    rc, st, got = run(Chain(nch, max_blocks_per_call=per, **K1), lambda k: 0, lambda k: -1)
+    assert rc == RDSP_ERR_INVALID and not got
+    chunks, pos = [], {"k": 0}
+
+    def source(dst):
+        if pos["k"] >= batches:
+            return 0
+        dst[:, :per * 128] = batch(pos["k"])
+        pos["k"] += 1
+        return per
+
+    st = stream_callbacks(Chain(nch, max_blocks_per_call=per, **K1), source, chunks.append, per)
+    assert st["blocks"] == batches * per and np.array_equal(np.concatenate(chunks, 1), np.concatenate(ref, 1))
+
+
+@pytest.mark.gpu
 def test_runner_argument_errors(rdsp, torch_cuda):
     from radiodsp_sdr_rx_amd import RdspError
     from radiodsp_sdr_rx_amd.chain import Chain, synth_iq
