@@ -86,10 +86,9 @@ typedef struct rdsp_chain rdsp_chain_t;
 
 const char *rdsp_last_error(void);
 const char *rdsp_version(void);
-/* 1 if the library was built with EXPERIMENTAL=1 (csrc/Makefile): it then also carries the
- * kernel variants that were measured and not adopted (matrix-core FIR and tail reductions,
- * half-row / DPP-shift tail layouts); the product build has none of them and the variant
- * setters below return RDSP_ERR_UNSUPPORTED for anything but the defaults. */
+/* Always 0: there is one build of the library.  The kernel variants that were measured and not adopted (matrix-core
+ * FIR and tail reductions, half-row / DPP-shift tail layouts: docs/history.md) are not in it -- a build that carried
+ * them answered 1 -- and the variant setters below return RDSP_ERR_UNSUPPORTED for them. */
 int rdsp_experimental_build(void);
 int rdsp_device_count(void);
 
@@ -356,12 +355,13 @@ int rdsp_chain_set_priorities(rdsp_chain_t *c, int front_fir_prio, int tail_prio
  * frames per granule): split-invariant like the default and ~10 % faster than it for chains without a tail stage
  * (K2 0.727 against 0.808 ms per step), no gain beside a tail kernel; with the noise blanker on it runs the default
  * form.  All of them are the same exact linear convolution with the same taps (RDSP_ERR_UNSUPPORTED for 2 / 4 / 5
- * on decim-1 chains, which have no decimator).  EXPERIMENTAL=1 builds: 1 matrix-core GEMM slices, 3 the same unless
- * the tail stage shares the SIMDs, 6 the row form with 192 outputs per window. */
+ * on decim-1 chains, which have no decimator).  RDSP_ERR_UNSUPPORTED, measured and not adopted (docs/history.md):
+ * 1 matrix-core GEMM slices, 3 the same unless the tail stage shares the SIMDs, 6 the row form with 192 outputs
+ * per window. */
 int rdsp_chain_set_fir_variant(rdsp_chain_t *c, int variant);
-/* tail-kernel variant: (16, 2) is the product -- a channel per 16-lane DPP row, two
- * steps per DPP reduction, delay line fed from LDS.  EXPERIMENTAL=1 builds: (16, 4) weights one block
- * stale with a hand-interleaved issue order, (16, 3) one reduction per step, (8, 2) half a row per
+/* tail-kernel variant: (16, 2) is the kernel there is -- a channel per 16-lane DPP row, two steps per
+ * DPP reduction, delay line fed from LDS.  RDSP_ERR_UNSUPPORTED, measured and not adopted (docs/history.md): (16, 4)
+ * weights one block stale with a hand-interleaved issue order, (16, 3) one reduction per step, (8, 2) half a row per
  * channel, (16 | 8, 1) cross-lane sums on the matrix pipe, (16, 0) delay line shifted by DPP */
 int rdsp_chain_set_tail_variant(rdsp_chain_t *c, int lanes_per_channel, int matrix_reduce);
 

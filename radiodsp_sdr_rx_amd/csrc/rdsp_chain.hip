@@ -27,13 +27,8 @@ int chain_fail(int code, const char *fmt, ...) {
   return code;
 }
 extern "C" const char *rdsp_last_error(void) { return g_err; }
-#ifdef RDSP_EXPERIMENTAL
-extern "C" const char *rdsp_version(void) { return "rdsp-amd 0.2 (gfx950, experimental variants)"; }
-extern "C" int rdsp_experimental_build(void) { return 1; }
-#else
 extern "C" const char *rdsp_version(void) { return "rdsp-amd 0.2 (gfx950)"; }
-extern "C" int rdsp_experimental_build(void) { return 0; }
-#endif
+extern "C" int rdsp_experimental_build(void) { return 0; } /* there is one build (include/rdsp.h) */
 
 extern "C" int rdsp_device_count(void) {
   int n = 0;
@@ -145,14 +140,13 @@ extern "C" int rdsp_chain_decim(const rdsp_chain_t *c) { return c ? c->decim : 0
 extern "C" int rdsp_chain_device(const rdsp_chain_t *c) { return c ? c->device : -1; }
 
 /* RdspFrontParams::fir_fd of a chain: 0 direct form (and every decim-1 chain), 1 / 2 the wave-wide frequency-domain
- * forms (448-sample frames / one granule per frame), 3 / 4 the row forms (128 / 192 outputs per window) */
+ * forms (448-sample frames / one granule per frame), 3 the row form (128 outputs per window) */
 int chain_fir_fd(const rdsp_chain_t *c) {
   if (!c->d_fd_mask) return 0;
   switch (c->fir_mode) {
     case 2: return 1;
     case -1: case 4: return 2;
     case 5: return 3;
-    case 6: return 4;
     default: return 0;
   }
 }
@@ -170,8 +164,8 @@ extern "C" int rdsp_chain_call_unit_blocks(const rdsp_chain_t *c) {
 extern "C" int rdsp_chain_granule_blocks(const rdsp_chain_t *c) {
   if (!c) return 0;
   const int unit = rdsp_chain_call_unit_blocks(c);
-  if ((c->fir_mode != 2 && c->fir_mode != 6) || !c->d_fd_mask) return unit;
-  const int frame = c->fir_mode == 2 ? 14 : 6; /* 448 (192) outputs x 4 / 128 */
+  if (c->fir_mode != 2 || !c->d_fd_mask) return unit;
+  const int frame = 14; /* 448 outputs x 4 / 128 */
   int a = unit, b = frame;
   while (b) { const int t = a % b; a = b; b = t; }
   return unit / a * frame;
@@ -376,7 +370,7 @@ static void front_params(rdsp_chain_t *c, Call &k) {
    * its waves and a tail wave fit one SIMD, and the lean variant's twiddle chains only cost */
   fp.lean = (c->lean_mode < 0) ? 0 : c->lean_mode;
   fp.front_prio = k.piped ? c->front_fir_prio : 0;
-  fp.fir_matrix = (c->fir_mode == 3) ? (k.piped ? 0 : 1) : (c->fir_mode == 1);
+  fp.fir_matrix = 0;
   /* stage A3 (rdsp_chain_set_fir_variant).  Default (-1) and 4: in the frequency domain with frames of one granule
    * (256 outputs per 512-point window): every frame's input is a function of the absolute sample position, so the
    * bits do not depend on how the stream is cut into calls -- like the direct form (0), at about two thirds of

@@ -258,48 +258,36 @@ extern "C" int rdsp_chain_set_priorities(rdsp_chain_t *c, int front_fir_prio, in
  * granule): split-invariant like the default, ~10 % faster than it for chains without a tail stage (K2 0.727 against
  * 0.808 ms), no gain beside a tail kernel (250 registers); with the noise blanker on it runs the default form.
  * Same taps and the same exact linear convolution in all of them; the sums associate differently (~2e-7).
- * EXPERIMENTAL=1 builds: 1 = v_mfma GEMM slices, 3 = the same unless the tail stage runs concurrently, 6 = the row
- * form with 192 outputs per window (frames anchored at the call's first sample; measured, no gain over 2). */
+ * 1 and 3 (v_mfma GEMM slices; 3 unless the tail stage runs concurrently) and 6 (the row form with 192 outputs per
+ * window, frames anchored at the call's first sample) were measured and not adopted (docs/history.md): unsupported. */
 extern "C" int rdsp_chain_set_fir_variant(rdsp_chain_t *c, int variant) {
   NEED(c);
   if (variant < -1 || variant > 6) return RDSP_ERR_INVALID;
   if ((variant == 2 || variant >= 4) && !c->d_fd_mask)
     return chain_fail(RDSP_ERR_UNSUPPORTED, "the frequency-domain decimator needs decim = 4");
-#ifndef RDSP_EXPERIMENTAL
   if (variant == 1 || variant == 3)
-    return chain_fail(RDSP_ERR_UNSUPPORTED, "the matrix-core FIR is only in EXPERIMENTAL=1 builds of the library");
+    return chain_fail(RDSP_ERR_UNSUPPORTED, "the matrix-core FIR was measured and not adopted (docs/history.md)");
   if (variant == 6)
-    return chain_fail(RDSP_ERR_UNSUPPORTED, "the row form with 192 outputs per window is only in EXPERIMENTAL=1 builds of the library");
-#endif
+    return chain_fail(RDSP_ERR_UNSUPPORTED, "the row form with 192 outputs per window was measured and not adopted (docs/history.md)");
   c->fir_mode = variant;
   return RDSP_OK;
 }
-/* tail-kernel variant.  (16, 2) is the product (rdsp_tail.hip: a channel per 16-lane DPP row, two
- * steps per reduction).  EXPERIMENTAL=1 builds: (16, 4) weights one block stale with a hand-interleaved
- * issue order, (16, 5) four steps per reduction (both round 3), (16, 3) one reduction per step (round 1), (8, 2) half a row per channel,
- * (16 | 8, 1) the reduction on the matrix pipe, (16, 0) the delay line shifted by DPP.  All compute
- * the same recursion; the sums associate differently. */
+/* tail-kernel variant.  (16, 2) is the kernel there is (rdsp_tail.hip: a channel per 16-lane DPP row, two
+ * steps per reduction).  Measured and not adopted (docs/history.md), unsupported: (16, 4) weights one block stale
+ * with a hand-interleaved issue order, (16, 5) four steps per reduction (both round 3), (16, 3) one reduction per
+ * step (round 1), (8, 2) half a row per channel, (16 | 8, 1) the reduction on the matrix pipe, (16, 0) the delay
+ * line shifted by DPP. */
 extern "C" int rdsp_chain_set_tail_variant(rdsp_chain_t *c, int lanes_per_channel, int matrix_reduce) {
   NEED(c);
   if ((lanes_per_channel != 8 && lanes_per_channel != 16) || (lanes_per_channel == 8 && !matrix_reduce) ||
       matrix_reduce < 0 || matrix_reduce > 5 || (lanes_per_channel == 8 && matrix_reduce > 2))
     return RDSP_ERR_INVALID;
-  int v;
-  if (lanes_per_channel == 16 && matrix_reduce == 2) v = 100;
-  else {
-#ifndef RDSP_EXPERIMENTAL
-    rdsp_set_error("tail-kernel variants other than the product's are only in EXPERIMENTAL=1 builds of the library");
+  if (lanes_per_channel != 16 || matrix_reduce != 2) {
+    rdsp_set_error("tail-kernel variants other than (16, 2) were measured and not adopted (docs/history.md)");
     return RDSP_ERR_UNSUPPORTED;
-#else
-    if (matrix_reduce == 5) v = 105;
-    else if (matrix_reduce == 4) v = 104;
-    else if (matrix_reduce == 3) v = 102;
-    else if (matrix_reduce == 2) v = 101;
-    else v = lanes_per_channel + (matrix_reduce ? 100 : 0);
-#endif
   }
   RC_TRY(chain_drain_tail(c));
-  c->tail_lpc = v;
+  c->tail_lpc = 100;
   return RDSP_OK;
 }
 /* `stream` waits for every call issued so far (outputs complete after it) */

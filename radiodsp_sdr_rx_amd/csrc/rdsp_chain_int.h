@@ -142,8 +142,8 @@ struct rdsp_chain {
   int fir_mode = -1;  /* stage A3 (rdsp_chain_set_fir_variant): 4 frequency domain, one granule per frame (split-
                          invariant bits); -1 (default) that or 5, by what follows the front kernel; 0 direct form; 2
                          frequency domain, 448-sample frames;
-                         5 / 6 frequency domain on 16-lane rows, 128 (split-invariant) / 192 outputs per 256-point window;
-                         EXPERIMENTAL builds: 1 matrix-core FIR, 3 matrix unless the tail stage shares the SIMDs */
+                         5 frequency domain on 16-lane rows, 128 outputs per 256-point window (split-invariant);
+                         1, 3 and 6 (measured and not adopted, docs/history.md) are never stored */
   /* wave priorities while both kernels share the SIMDs: the direct-form front kernel raises its
    * own to front_fir_prio during the FIR, the frequency-domain one never does; the tail kernel runs
    * at tail_prio throughout.  Round 2, frequency-domain front kernel, tail priority 0 / 1 / 2 / 3:
@@ -155,8 +155,7 @@ struct rdsp_chain {
    * the profiler and 1.83 against 1.50 as a leg of the default bench run -- no consistent gain, so the priority stays 2
    * in every form (tests/micro/prio_default.sh, default_form_trace.sh) */
   int front_fir_prio = 2, tail_prio = 2;
-  /* tail kernel: 100 = the product's (rdsp_tail.hip: a channel per 16-lane DPP row, two steps per reduction);
-   * other values select the EXPERIMENTAL=1 variants (rdsp_launch_tail) */
+  /* tail kernel (rdsp_launch_tail): 100, rdsp_tail.hip's -- a channel per 16-lane DPP row, two steps per reduction */
   int tail_lpc = 100;
   int saved_agc_mode = RDSP_AGC_MEDIUM, saved_als_mode = RDSP_ALS_NOTCH;
   /* the engine's IIR audio filter bank (RDSP_AUDIO_KIND_IIR): coefficient sets per group, DF1

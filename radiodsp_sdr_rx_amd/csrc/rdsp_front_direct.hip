@@ -1,6 +1,6 @@
 /*
  * rdsp_front_direct.hip -- the front kernel with the decimator in direct form (or none), hand-written for CDNA4
- * (gfx950).  No MFMA in the product build: the path is streaming FIR/FFT work in fp32.
+ * (gfx950).  No MFMA: the path is streaming FIR/FFT work in fp32.
  *
  *   rdsp_front_kernel<N,P,DECIM>  one channel per workgroup of NT = N/P threads
  *       A1  int16 IQ unpack           RDSP_convolutional.h:241-242
@@ -30,18 +30,16 @@ namespace {
 
 /* ---- front kernel -------------------------------------------------------- */
 /* LDS plan of the front kernel (float2 units), shared with the launch code */
-/* FMX: the decimating FIR as a GEMM with v_mfma (fir_matrix, rdsp_front.h) instead of packed FMAs */
-template <int N, int P, int DECIM, bool FMX>
+template <int N, int P, int DECIM>
 struct FrontLds {
   static constexpr int NT = N / P;
   static constexpr int H = N / 2;
-  static constexpr bool FM = FMX && (DECIM == 4);
-  static constexpr int XS_N = (DECIM == 4) ? (FM ? RDSP_XL_N : 16 * RDSP_XP) : 0;
+  static constexpr int XS_N = (DECIM == 4) ? 16 * RDSP_XP : 0;
   static constexpr int HB_N = (H > 256) ? H : 256; /* new samples of one chunk / one hop */
   /* one-wave kernels with a work buffer that fits behind the FIR history reuse the planes */
   static constexpr bool ALIAS = (DECIM == 4) && (NT == 64) && (N <= 512);
   static constexpr int WB_N = ALIAS ? 0 : FftPlan<N, P>::WB;
-  static constexpr int TAPS_N = (DECIM == 4) ? (FM ? RDSP_HZ_N / 2 : 128) : 0;
+  static constexpr int TAPS_N = (DECIM == 4) ? 128 : 0;
   static constexpr size_t BYTES = (size_t)(XS_N + HB_N + WB_N + TAPS_N) * sizeof(float2) + 64 * sizeof(float);
 };
 
@@ -51,13 +49,12 @@ struct FrontLds {
  * file of a SIMD in pipelined mode; since the butterflies and the FIR were written out by
  * hand the full-register kernel needs 185 VGPRs, fits as well (2 x 192 + 112) and is the
  * default in both modes (the lean one stays selectable, rdsp_chain_set_front_variant).
- * FMX = true (opt-in, rdsp_chain_set_fir_variant) runs the decimating FIR as
- * v_mfma_f32_16x16x4_f32 GEMM slices.  fp32 MFMA and fp32 VALU work do not overlap on a gfx950
- * SIMD (tests/micro/mfma_valu_overlap.hip: one wave of each takes the sum of both times), so
- * this is not a second pipe; it wins 10 % at K2, 6 % on the K3 front kernel and 2 % at K4
- * through fewer LDS reads and instructions and 40-60 fewer VGPRs -- and its 32-cycle
- * instructions starve a co-resident tail wave (pipelined K3: 2.21 -> 2.58 ms). */
-template <int N, int P, int DECIM, bool LEAN, bool PRE, bool FMX>
+ * The decimating FIR as v_mfma_f32_16x16x4_f32 GEMM slices was built and measured (docs/history.md, DESIGN.md
+ * section 4.1c): fp32 MFMA and fp32 VALU work do not overlap on a gfx950 SIMD (tests/micro/mfma_valu_overlap.hip:
+ * one wave of each takes the sum of both times), so it is not a second pipe; it won 10 % at K2, 6 % on the K3
+ * front kernel and 2 % at K4 through fewer LDS reads and instructions and 40-60 fewer VGPRs -- and its 32-cycle
+ * instructions starved a co-resident tail wave (pipelined K3: 2.21 -> 2.58 ms).  Not adopted. */
+template <int N, int P, int DECIM, bool LEAN, bool PRE>
 __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p) {
   using PL = FftPlan<N, P>;
   constexpr int NT = PL::NT;
@@ -68,12 +65,8 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
   constexpr int CH_IN = CH_OUT * DECIM;
   constexpr int FPC = (H >= CH_OUT) ? 1 : CH_OUT / H; /* frames per chunk */
   constexpr int CPF = (H >= CH_OUT) ? H / CH_OUT : 1; /* chunks per frame */
-  using LY = FrontLds<N, P, DECIM, FMX>;
+  using LY = FrontLds<N, P, DECIM>;
   constexpr bool ALIAS = LY::ALIAS;
-  constexpr bool FM = LY::FM;
-  /* matrix FIR: the input is one padded line; after the FIR only its first 256 samples (the
-   * history) are live, so the work buffer sits right behind them with the plain map */
-  constexpr bool WALIAS = ALIAS && !FM;
   constexpr int LP = (CH_IN / 4 + NT - 1) / NT; /* uint4 loads per thread per chunk */
   static_assert(DECIM == 1 || DECIM == 4, "decimation 1 or 4");
   static_assert(NT == 64 || NT == 256, "one or four waves per channel");
@@ -86,10 +79,8 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float2 *xs = reinterpret_cast<float2 *>(smem_raw);
   float2 *hb = xs + LY::XS_N;
-  float2 *wb = ALIAS ? (FM ? xs + xl_pos(0) : xs) : hb + LY::HB_N;
-  static_assert(!FM || !ALIAS || xl_pos(0) + PL::WB <= RDSP_XL_N, "work buffer fits behind the history");
+  float2 *wb = ALIAS ? xs : hb + LY::HB_N;
   float4 *taps_lds = reinterpret_cast<float4 *>(hb + LY::HB_N + (ALIAS ? 0 : PL::WB));
-  float *hz = reinterpret_cast<float *>(taps_lds);
   float *red = reinterpret_cast<float *>(reinterpret_cast<float2 *>(taps_lds) + LY::TAPS_N);
 
   /* PRE: the pre-processor's IQ swap and the noise blanker are compiled in (their
@@ -124,8 +115,8 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
    * (digit-reversed, /N), its VAD-bin membership bits and its four taps */
   Twiddles<N, P, LEAN> tw;
   tw.init(tid);
-  LdsBases<N, P, WALIAS> lb;
-  make_lds_bases<N, P, WALIAS>(tid, lb);
+  LdsBases<N, P, ALIAS> lb;
+  make_lds_bases<N, P, ALIAS>(tid, lb);
   uint32_t vadbits = 0; /* (twins: the VAD bits of rdsp_front_fd_kernel, rdsp_front_fd.hip, and rdsp_front_rd_kernel, rdsp_front_rd.hip) */
 #pragma unroll
   for (int e = 0; e < P; e++) {
@@ -133,14 +124,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
     if (k >= p.vad_lo && k <= p.vad_hi) vadbits |= 1u << e;
   }
   if constexpr (DECIM == 4) {
-    if constexpr (FM) { /* tap line hz[t + 64] = h[t] = hc[t % 4][t / 4], zero outside 0..255 */
-      for (int t = tid; t < RDSP_HZ_N; t += NT) {
-        const int tt = t - 64;
-        hz[t] = (tt >= 0 && tt < 256) ? p.fir_hc[(tt & 3) * 64 + (tt >> 2)] : 0.f;
-      }
-    } else {
-      if (tid < 64) taps_lds[tid] = reinterpret_cast<const float4 *>(p.fir_hc)[tid];
-    }
+    if (tid < 64) taps_lds[tid] = reinterpret_cast<const float4 *>(p.fir_hc)[tid];
   }
 
   float nfloor = p.st_scal[ch * 4 + 0];
@@ -181,7 +165,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
           float2 ph = (k == 0) ? ph0 : cmul_pinned_u(ph0, k == 1 ? G.roth1 : (k == 2 ? G.roth2 : G.roth3));
           x = cmul_pinned(x, ph);
         }
-        xs[FM ? xl_pos(-256 + 4 * i + k) : xs_pos(-256 + 4 * i + k)] = x;
+        xs[xs_pos(-256 + 4 * i + k)] = x;
       }
     }
   }
@@ -249,7 +233,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           if constexpr (DECIM == 4) {
-            xs[FM ? xl_pos(4 * idx + j) : xs_pos(4 * idx + j)] = x[j];
+            xs[xs_pos(4 * idx + j)] = x[j];
           } else {
             int m = 4 * idx + j; /* no decimator: the sample is the "output" */
             hb[(chunk % CPF) * CH_OUT + m] = x[j];
@@ -286,38 +270,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
     wg_sync<NW>();
 
     /* ---- A3: polyphase decimating FIR ------------------------------------ */
-    if constexpr (DECIM == 4 && FM) {
-      /* on the matrix pipe (rdsp_front.h): lane 16 kq + i gets outputs m = 64 kq + 16 r + i */
-      rdsp_v4f dre = {0.f, 0.f, 0.f, 0.f}, dim = {0.f, 0.f, 0.f, 0.f};
-      const int mi = lane & 15, mk = lane >> 4;
-      if constexpr (NW == 1) {
-        if (p.front_prio == 1) __builtin_amdgcn_s_setprio(1);
-        else if (p.front_prio == 2) __builtin_amdgcn_s_setprio(2);
-        else if (p.front_prio == 3) __builtin_amdgcn_s_setprio(3);
-        fir_matrix<0, 80>(lane, xs, hz, dre, dim);
-        if (p.front_prio > 0) __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-        for (int r = 0; r < 4; r++) hb[(chunk % CPF) * CH_OUT + 64 * mk + 16 * r + mi] = make_float2(dre[r], dim[r]);
-        wg_sync<NW>();
-      } else {
-        /* four waves: wave w takes a quarter of the K-slices; partials summed via LDS */
-        if (wave == 0) fir_matrix<0, 20>(lane, xs, hz, dre, dim);
-        else if (wave == 1) fir_matrix<20, 40>(lane, xs, hz, dre, dim);
-        else if (wave == 2) fir_matrix<40, 60>(lane, xs, hz, dre, dim);
-        else fir_matrix<60, 80>(lane, xs, hz, dre, dim);
-#pragma unroll
-        for (int r = 0; r < 4; r++) wb[wave * CH_OUT + 64 * mk + 16 * r + mi] = make_float2(dre[r], dim[r]);
-        wg_sync<NW>();
-        {
-          float2 s0 = wb[tid], s1 = wb[CH_OUT + tid], s2 = wb[2 * CH_OUT + tid], s3 = wb[3 * CH_OUT + tid];
-          float2 s = cadd(cadd(s0, s1), cadd(s2, s3));
-          hb[(chunk % CPF) * CH_OUT + tid] = s;
-        }
-      }
-      /* the last 256 samples of the chunk are the next chunk's history */
-      for (int t = tid; t < 256; t += NT) xs[xl_pos(t - 256)] = xs[xl_pos(768 + t)];
-      wg_sync<NW>();
-    } else if constexpr (DECIM == 4) {
+    if constexpr (DECIM == 4) {
       float2 acc[4];
 #pragma unroll
       for (int r = 0; r < 4; r++) acc[r] = make_float2(0.f, 0.f);
@@ -362,7 +315,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
 #pragma unroll 1
     for (int f = 0; f < FPC; f++) {
       const float2 *hnew = hb + f * H;
-      front_frame<N, P, WALIAS>(p, G, tw, lb, wb, red, mreg, vadbits, vad_inv, vprev, nfloor, agc_g, am_dc, frame_idx,
+      front_frame<N, P, ALIAS>(p, G, tw, lb, wb, red, mreg, vadbits, vad_inv, vprev, nfloor, agc_g, am_dc, frame_idx,
                                 ch, tid, [&](int i) { return hnew[i]; }); /* advances frame_idx */
     }
   }
@@ -391,34 +344,26 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_kernel(RdspFrontParams p)
   }
 }
 
-template <int N, int P, int DECIM, bool LEAN, bool PRE, bool FMX>
+template <int N, int P, int DECIM, bool LEAN, bool PRE>
 int launch_direct(const RdspFrontParams *p, int n_channels, hipStream_t stream) {
-  constexpr size_t lds = FrontLds<N, P, DECIM, FMX>::BYTES;
-  int e = ensure_lds_limit<&rdsp_front_kernel<N, P, DECIM, LEAN, PRE, FMX>>(lds);
+  constexpr size_t lds = FrontLds<N, P, DECIM>::BYTES;
+  int e = ensure_lds_limit<&rdsp_front_kernel<N, P, DECIM, LEAN, PRE>>(lds);
   if (e != 0) return e;
-  hipLaunchKernelGGL((rdsp_front_kernel<N, P, DECIM, LEAN, PRE, FMX>), dim3(n_channels), dim3(N / P), lds, stream, *p);
+  hipLaunchKernelGGL((rdsp_front_kernel<N, P, DECIM, LEAN, PRE>), dim3(n_channels), dim3(N / P), lds, stream, *p);
   return (int)hipGetLastError();
 }
 
-#ifdef RDSP_EXPERIMENTAL
-constexpr bool FMX_BUILT = true;
-#else
-constexpr bool FMX_BUILT = false; /* matrix-core FIR: EXPERIMENTAL=1 builds only */
-#endif
-
-/* the instances that exist: no full-register one at radix 16, the matrix-core FIR where there is a decimator */
-template <int P, int DECIM, bool LEAN, bool FMX>
-constexpr bool direct_instance = (LEAN || P != 16) && (!FMX || (FMX_BUILT && DECIM == 4));
+/* the instances that exist: no full-register one at radix 16 */
+template <int P, bool LEAN>
+constexpr bool direct_instance = LEAN || P != 16;
 
 template <int N, int P, int DECIM>
 int launch_direct_flags(const RdspFrontPick &k, const RdspFrontParams *p, int n_channels, hipStream_t stream) {
   return with_flag(k.lean, [&](auto lean) {
     return with_flag(k.pre, [&](auto pre) {
-      return with_flag(k.fmx, [&](auto fmx) {
-        constexpr bool LEAN = decltype(lean)::value, PRE = decltype(pre)::value, FMX = decltype(fmx)::value;
-        if constexpr (direct_instance<P, DECIM, LEAN, FMX>) return launch_direct<N, P, DECIM, LEAN, PRE, FMX>(p, n_channels, stream);
-        else return (int)hipErrorInvalidValue;
-      });
+      constexpr bool LEAN = decltype(lean)::value, PRE = decltype(pre)::value;
+      if constexpr (direct_instance<P, LEAN>) return launch_direct<N, P, DECIM, LEAN, PRE>(p, n_channels, stream);
+      else return (int)hipErrorInvalidValue;
     });
   });
 }
@@ -437,6 +382,6 @@ int rdsp::front_direct_launch(int fft_l, int decim, const RdspFrontPick &k, cons
 extern "C" size_t rdsp_front_lds_bytes(int fft_l, int decim) {
   return with_front_plan(fft_l, (size_t)0, [&](auto plan) {
     constexpr int N = decltype(plan)::N, P = decltype(plan)::P;
-    return decim == 4 ? FrontLds<N, P, 4, false>::BYTES : FrontLds<N, P, 1, false>::BYTES;
+    return decim == 4 ? FrontLds<N, P, 4>::BYTES : FrontLds<N, P, 1>::BYTES;
   });
 }

@@ -16,19 +16,18 @@ namespace {
  * mixed input, branch spectra, one inverse -- on 256-point windows, one window per 16-lane DPP row: 16 points per
  * lane, two radix-16 passes, ONE LDS exchange each way (the plan of front_frame_quad), a wave taking four
  * consecutive windows at once.  A window is the 64 quads in front of its frame (the 256 raw samples of the FIR
- * history; rows and passes re-read them, an L2 hit) and RV new ones:
- *   RV = 128 (fir_variant 5): two frames per granule of 256 outputs, the window's last quarter zeros.  Every call
- *     boundary is a frame boundary and a frame's arithmetic does not depend on the row or pass it lands in: the
- *     same bits for any call split, like the one-granule form of rdsp_front_fd_kernel;
- *   RV = 192 (EXPERIMENTAL=1 builds, fir_variant 6): the whole window is data; frames anchored at the call's first
- *     sample, the last one partial.
+ * history; rows and passes re-read them, an L2 hit) and RV = 128 new ones (fir_variant 5): two frames per granule
+ * of 256 outputs, the window's last quarter zeros.  Every call boundary is a frame boundary and a frame's arithmetic
+ * does not depend on the row or pass it lands in: the same bits for any call split, like the one-granule form of
+ * rdsp_front_fd_kernel.
  * Mixer: one phasor per lane and pass (its first new column), every (column, branch) by one product with an entry
  * of a 64-entry table in LDS, exp(-j theta (64 (j - 4) + r)), made at the start of the launch.
  * What it costs, from the ISA: a row's transform is 184 packed instructions for 16 points (2 x 77 + 15 twiddle
  * products), the wave-wide 512-point radix-8 one 113 for 8: 19 % less per point, which the shorter window gives
  * back -- 1330 packed instructions per pass of 768 (512) outputs against 759 per frame of 448 (256).  Measured at
  * K2 / K4 (PMC and same-box A/B, tests/micro/rows_ab.sh, rows_pmc.sh): RV 128 0.727 / 2.04 ms per step where the
- * one-granule form takes 0.808 / 2.10 and 448-sample frames 0.598 / 1.74; RV 192 0.742 / 2.05 (as many vector
+ * one-granule form takes 0.808 / 2.10 and 448-sample frames 0.598 / 1.74; RV 192 (the whole window data, frames
+ * anchored at the call's first sample; measured and not adopted) 0.742 / 2.05 (as many vector
  * instructions as the 448-sample form, 2.19e8 against 2.16e8 per K2 launch, and 38 spilled registers).  So: an
  * opt-in for chains that want split-invariant bits and whose audio does not go on to a tail kernel on the same
  * SIMDs (238-256 VGPRs where the wave-wide forms fit 176; K3 pipelined: 1.39-1.43 ms against 1.38-1.46).
@@ -36,13 +35,14 @@ namespace {
  * the launch code falls back to the form with the same split behaviour. */
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 constexpr int RD_WB = 4 * FftPlan<256, 16>::WB; /* a wave's four row exchange buffers */
+constexpr int RV = 128;                         /* new outputs per window: a frame is a hop of FFT_L 256 */
 
 /* LDS plan of rdsp_front_rd_kernel, shared with the launch code: sizes in elements, offsets in bytes */
-template <int N, int P, bool Q4, int RV>
+template <int N, int P, bool Q4>
 struct FrontRdLds {
   static constexpr int NW = N / P / 64;
-  /* Q4 ring: the overlap hop, what a pass leaves unconsumed (< 4 hops, whole hops: 0 or 2 at RV 192) and a pass */
-  static constexpr int HOPS = RV == 128 ? QUAD_HOPS : 9;
+  /* Q4 ring: the overlap hop, what a pass leaves unconsumed (< 4 hops) and a pass */
+  static constexpr int HOPS = QUAD_HOPS;
   static constexpr int RING_N = Q4 ? HOPS * QUAD_PITCH : (NW == 1 ? 1024 : 4096); /* float2: decimated samples */
   /* float2: the filter's work buffer, every wave's four row exchange buffers, front_frame_quad's four */
   static constexpr int WB_N0 = FftPlan<N, P>::WB > NW * RD_WB ? FftPlan<N, P>::WB : NW * RD_WB;
@@ -56,7 +56,7 @@ struct FrontRdLds {
   static constexpr size_t BYTES = UTAB + UTAB_N * sizeof(float2);
 };
 
-template <int N, int P, bool LEAN, bool PRE, bool Q4, int RV>
+template <int N, int P, bool LEAN, bool PRE, bool Q4>
 __global__ void __launch_bounds__(N / P, 2) rdsp_front_rd_kernel(RdspFrontParams p) {
   using PL = FftPlan<N, P>;
   using PR = FftPlan<256, 16>;
@@ -64,14 +64,13 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_rd_kernel(RdspFrontParams
   constexpr int NW = NT / 64;
   constexpr int H = N / 2;
   constexpr int PH = P / 2;
-  static_assert(RV == 128 || RV == 192, "two frames per granule, or the whole window");
   constexpr int NJ = 4 + RV / 16; /* data points of a lane: four history columns and RV / 16 new ones */
   constexpr int PASS = 4 * RV;    /* outputs of one wave's pass */
   constexpr bool QUAD = Q4;
   static_assert(!Q4 || N == 256, "the four-frame form exists for FFT_L 256");
-  using LY = FrontRdLds<N, P, Q4, RV>;
+  using LY = FrontRdLds<N, P, Q4>;
   constexpr int HOPS = LY::HOPS;
-  static_assert(!QUAD || 1 + (RV == 128 ? 0 : 2) + PASS / 128 <= HOPS, "ring hops");
+  static_assert(!QUAD || 1 + PASS / 128 <= HOPS, "ring hops");
   constexpr int RING = LY::RING_N;
   /* what a round leaves unconsumed is a multiple of gcd(H, NW PASS) below H */
   static_assert(QUAD || (H - cgcd(H, NW * PASS)) + NW * PASS <= RING, "ring holds a round's outputs behind an unfinished hop");
@@ -272,29 +271,12 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_rd_kernel(RdspFrontParams
     }
     /* acc[j] = y at window index li + 16 j; index 64 (j = 4) is output fr * RV of the call */
     if constexpr (QUAD) {
-      if constexpr (RV == 128) { /* a frame is a hop */
-        int h = whop + wave * 4 + row;
-        h = h >= HOPS ? h - HOPS : h;
-        float2 *dst = ring + h * QUAD_PITCH + li;
+      int h = whop + wave * 4 + row; /* a frame is a hop */
+      h = h >= HOPS ? h - HOPS : h;
+      float2 *dst = ring + h * QUAD_PITCH + li;
 #pragma unroll
-        for (int c = 0; c < 8; c++) dst[16 * c] = acc[4 + c];
-        whop = (whop + 4 * NW) % HOPS;
-      } else { /* a frame is a hop and a half: even rows start a hop, odd ones in the middle of one */
-        const int odd = row & 1;
-        int a = whop + ((3 * row) >> 1);
-        a = a >= HOPS ? a - HOPS : a;
-        const int a1 = a + 1 >= HOPS ? a + 1 - HOPS : a + 1;
-        float2 *dA = ring + a * QUAD_PITCH + (odd ? 64 : 0) + li;
-        float2 *dB = odd ? ring + a1 * QUAD_PITCH + li : ring + a * QUAD_PITCH + 64 + li;
-        float2 *dC = ring + a1 * QUAD_PITCH + (odd ? 64 : 0) + li;
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-          dA[16 * c] = acc[4 + c];
-          dB[16 * c] = acc[8 + c];
-          dC[16 * c] = acc[12 + c];
-        }
-        whop = (whop + 6) % HOPS;
-      }
+      for (int c = 0; c < 8; c++) dst[16 * c] = acc[4 + c];
+      whop = (whop + 4 * NW) % HOPS;
     } else {
       const int mb = fr * RV; /* of the call; a multiple of 64 like the ring's length */
 #pragma unroll
@@ -359,23 +341,17 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_rd_kernel(RdspFrontParams
   }
 }
 
-template <int N, int P, bool LEAN, bool PRE, bool Q4, int RV>
+template <int N, int P, bool LEAN, bool PRE, bool Q4>
 int launch_rd(const RdspFrontParams *p, int n_channels, hipStream_t stream) {
-  constexpr size_t lds = FrontRdLds<N, P, Q4, RV>::BYTES;
+  constexpr size_t lds = FrontRdLds<N, P, Q4>::BYTES;
   static_assert(!Q4 || lds <= 48 * 1024, "no raised dynamic-LDS limit needed");
   if constexpr (lds > 48 * 1024) {
-    int e = ensure_lds_limit<&rdsp_front_rd_kernel<N, P, LEAN, PRE, Q4, RV>>(lds);
+    int e = ensure_lds_limit<&rdsp_front_rd_kernel<N, P, LEAN, PRE, Q4>>(lds);
     if (e != 0) return e;
   }
-  hipLaunchKernelGGL((rdsp_front_rd_kernel<N, P, LEAN, PRE, Q4, RV>), dim3(n_channels), dim3(N / P), lds, stream, *p);
+  hipLaunchKernelGGL((rdsp_front_rd_kernel<N, P, LEAN, PRE, Q4>), dim3(n_channels), dim3(N / P), lds, stream, *p);
   return (int)hipGetLastError();
 }
-
-#ifdef RDSP_EXPERIMENTAL
-constexpr bool RV192_BUILT = true;
-#else
-constexpr bool RV192_BUILT = false; /* 192 outputs per window: EXPERIMENTAL=1 builds (measured, no gain) */
-#endif
 
 /* the instances that exist: the plan's radix decides LEAN (the filter's twiddles by product chains from radix 8 up: the
  * rows need the registers), four frames per pass at FFT_L 256 only */
@@ -385,21 +361,15 @@ constexpr bool rd_instance = LEAN == (P >= 8) && (!Q4 || N == 256);
 }  // namespace
 
 int rdsp::front_rd_launch(int fft_l, const RdspFrontPick &k, const RdspFrontParams *p, int n_channels, hipStream_t stream) {
-  if (k.frame != 128 && !(RV192_BUILT && k.frame == 192)) return (int)hipErrorInvalidValue;
+  if (k.frame != RV) return (int)hipErrorInvalidValue;
   return with_front_plan(fft_l, (int)hipErrorInvalidValue, [&](auto plan) {
     return with_flag(k.lean, [&](auto lean) {
       return with_flag(k.pre, [&](auto pre) {
         return with_flag(k.q4, [&](auto q4) {
           constexpr int N = decltype(plan)::N, P = decltype(plan)::P;
           constexpr bool LEAN = decltype(lean)::value, PRE = decltype(pre)::value, Q4 = decltype(q4)::value;
-          if constexpr (rd_instance<N, P, LEAN, Q4>) {
-            if constexpr (RV192_BUILT) {
-              if (k.frame == 192) return launch_rd<N, P, LEAN, PRE, Q4, 192>(p, n_channels, stream);
-            }
-            return launch_rd<N, P, LEAN, PRE, Q4, 128>(p, n_channels, stream);
-          } else {
-            return (int)hipErrorInvalidValue;
-          }
+          if constexpr (rd_instance<N, P, LEAN, Q4>) return launch_rd<N, P, LEAN, PRE, Q4>(p, n_channels, stream);
+          else return (int)hipErrorInvalidValue;
         });
       });
     });

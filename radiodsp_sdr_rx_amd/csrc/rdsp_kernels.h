@@ -65,14 +65,14 @@ struct RdspFrontParams {
   int vad_lo, vad_hi;      /* inclusive natural bin range                    */
   int to_mid;              /* 1: write mono float audio for the tail kernel  */
   int lean;                /* 1: register-lean variant (FFT twiddles rebuilt per pass)     */
-  int fir_matrix;          /* 1: decimating FIR as v_mfma GEMM slices (EXPERIMENTAL builds)    */
+  int fir_matrix;          /* must be 0 (the matrix-core FIR was not adopted; the word keeps the later fields in place) */
   int fir_fd;              /* decimator in the frequency domain (rdsp_front_fd_kernel): 1 = 448-sample frames anchored at
                               the call's first sample, 2 = frames of one granule (split-invariant); 0 = direct form;
                               on 16-lane rows (rdsp_front_rd_kernel): 3 = 128 outputs per 256-point window (two frames per
-                              granule: split-invariant), 4 = 192 outputs per window, anchored at the call's first sample */
+                              granule: split-invariant); 4 (192 outputs per window) is not supported */
   const float2 *fd_mask;   /* [4][RDSP_FD_N] spectra of the polyphase branches g_r[k] = h[4k - r],
                               /RDSP_FD_N, digit-reversed thread-major like the filter masks    */
-  const float2 *rd_mask;   /* [4][256] the same spectra for 256-point windows, natural bin order, /256 (fir_fd 3, 4) */
+  const float2 *rd_mask;   /* [4][256] the same spectra for 256-point windows, natural bin order, /256 (fir_fd 3) */
   int front_prio;          /* 1: raise wave priority (tail kernel shares the SIMDs) */
   int agc_on;
   float agc_attack, agc_decay;
@@ -100,9 +100,8 @@ struct RdspFrontPick {
   int radix;   /* P of the overlap-save filter's transform: 4, 8 or 16 points per thread */
   int lean;    /* LEAN: FFT twiddles rebuilt per pass */
   int pre;     /* PRE: IQ swap, noise blanker, two input gains and a history from other settings compiled in */
-  int fmx;     /* FMX: decimating FIR on the matrix cores (direct family, EXPERIMENTAL=1 builds) */
   int q4;      /* Q4: FFT_L 256, four overlap-save frames per pass (front_frame_quad) */
-  int frame;   /* fd: VC, new quad columns per decimator frame (4 or 7); rd: RV, outputs per window (128 or 192);
+  int frame;   /* fd: VC, new quad columns per decimator frame (4 or 7); rd: RV, outputs per window (128);
                   direct: 0 */
 };
 

@@ -1,7 +1,7 @@
 /*
  * rdsp_kernels.hip -- the launch layer of the front kernels and the chain's small kernels (gfx950).
  *
- *   rdsp_front_pick      which front-kernel instance a call runs: family, LEAN, PRE, FMX, Q4, frame length.  The one
+ *   rdsp_front_pick      which front-kernel instance a call runs: family, LEAN, PRE, Q4, frame length.  The one
  *                        statement of that choice -- the chain's timing records take the kernel's name from it too
  *   rdsp_launch_front    launches what it names, through the family's entry (rdsp_front_launch.h)
  *   rdsp_group_store_kernel, rdsp_iq_slip_kernel, rdsp_q15_to_float_kernel, rdsp_float_to_q15_kernel
@@ -74,18 +74,14 @@ __global__ void rdsp_float_to_q15_kernel(const float *src, int16_t *dst, size_t 
  * the registers, the `lean` switch is for the wave-wide forms.
  * PRE: blanker, swap, a FIR history that came in under another swap flag / other input gains, or different gains on I
  * and Q (iq_balance) -- the kernels without PRE fold the one gain into the mixer.
- * fir_fd 1: 448-sample frames (throughput form, fir_variant 2); 2: one granule per frame (split-invariant); 3 / 4: the
- * row forms with 128 / 192 outputs per window -- with the noise blanker on, the wave-wide form with the same split
- * behaviour (2 / 1): its decisions travel with the raw words from frame to frame.
+ * fir_fd 1: 448-sample frames (throughput form, fir_variant 2); 2: one granule per frame (split-invariant); 3: the
+ * row form, 128 outputs per window -- with the noise blanker on, the wave-wide form with the same split behaviour (2):
+ * its decisions travel with the raw words from frame to frame.  fir_fd 4 (192 outputs per window) and fir_matrix (the
+ * decimating FIR on the matrix cores) were measured and not adopted (docs/history.md): not supported.
  * Q4, FFT_L 256: four overlap-save frames per pass (front_frame_quad) unless the audio goes on to the tail kernel, which
  * may share the SIMDs (pipelined mode) and leaves no room for that form's registers and LDS.  Measurement switch
  * RDSP_NO_QUAD=1: the one-frame form behind the wave-wide decimator too (tests/micro/k2_occupancy.sh). */
 extern "C" int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, RdspFrontPick *pick) {
-#ifdef RDSP_EXPERIMENTAL
-  const bool experimental = true;
-#else
-  const bool experimental = false;
-#endif
   if (decim != 1 && decim != 4) return (int)hipErrorInvalidValue;
   RdspFrontPick k = {};
   k.radix = with_front_plan(fft_l, 0, [](auto plan) { return decltype(plan)::P; });
@@ -97,10 +93,10 @@ extern "C" int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, R
   if (decim == 4 && p->fir_fd) {
     if (p->fir_fd >= 3 && !p->nb_on) {
       if (!p->rd_mask) return (int)hipErrorInvalidValue;
-      if (p->fir_fd == 4 && !experimental) return (int)hipErrorNotSupported; /* 192 outputs per window: EXPERIMENTAL=1 builds */
+      if (p->fir_fd == 4) return (int)hipErrorNotSupported;
       k.family = RDSP_FRONT_RD;
       k.lean = k.radix >= 8;
-      k.frame = p->fir_fd == 4 ? 192 : 128;
+      k.frame = 128;
       k.q4 = one_hop_frames;
     } else {
       static const bool no_quad = getenv("RDSP_NO_QUAD") && atoi(getenv("RDSP_NO_QUAD")) != 0;
@@ -109,9 +105,8 @@ extern "C" int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, R
       k.q4 = one_hop_frames && !no_quad;
     }
   } else {
-    if (p->fir_matrix && !experimental) return (int)hipErrorNotSupported; /* matrix-core FIR: EXPERIMENTAL=1 builds only */
+    if (p->fir_matrix) return (int)hipErrorNotSupported;
     k.family = RDSP_FRONT_DIRECT;
-    k.fmx = decim == 4 && p->fir_matrix;
   }
   *pick = k;
   return 0;

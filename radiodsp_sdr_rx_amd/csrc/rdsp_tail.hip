@@ -14,7 +14,7 @@
  * steps per 16-lane reduction with the energy E and the lag-1 correlation B, which depend on the
  * input only, in two DPP prefix scans per 64 steps: ~19 issue slots per step (103 cycles) against a
  * chain of ~98; measured 123 cycles per step.  Taking the chain away (weights one block stale,
- * hand-interleaved issue order: tests/micro/not_adopted/rdsp_tail_lookahead.h) was built and measured in round 3
+ * hand-interleaved issue order: docs/history.md) was built and measured in round 3
  * and loses: its two extra scans cost more issue slots than the chain it removes.
  * Input blocks are fetched from HBM a whole block ahead (round 3: 0.967 -> 0.912 ms alone).
  * In pipelined K3 the lone wave shares its CU's LDS with eight front workgroups and issues more LDS instructions
@@ -115,8 +115,6 @@ __device__ __forceinline__ float reduce_halves(float a0, float a1) {
 struct NlmsB {
   /* 64 steps per group of scalars: the two prefix scans (8 DPP operations) serve four steps per lane */
   static constexpr int TPL = 6, GS = 64;
-  static constexpr int LDS_SCR = 0;            /* the scalars of a group stay in the registers of the lane that made them */
-  static constexpr bool OUT_IN_SCR = false;    /* block() writes its 128 outputs to `out` */
   v2f w2[TPL / 2];
   v2f P[8];
   float energy;
@@ -185,10 +183,10 @@ struct NlmsB {
     return r;
   }
 
-  /* one 128-sample block.  ring is [previous block | current block], 256 floats, so every sample a
+  /* one 128-sample block, its 128 outputs written to `out`.  ring is [previous block | current block], 256 floats, so every sample a
    * step looks back at is at a fixed distance below it (no wrap) */
   template <bool OUT_E>
-  __device__ __forceinline__ void block(const float *ring, bool first, float mu, float *out, float *, int sub, bool running) {
+  __device__ __forceinline__ void block(const float *ring, bool first, float mu, float *out, int sub, bool running) {
     const float *cur = ring + RDSP_BLOCK;
     const float *dsrc = first ? cur : ring; /* NR:69-79 */
     const float *mine = cur - TPL * sub;
@@ -273,23 +271,18 @@ struct NlmsB {
     energy = e_base;
   }
   /* output sample i of the block just processed */
-  static __device__ __forceinline__ float4 out4(const float *out, const float *, int i) {
+  static __device__ __forceinline__ float4 out4(const float *out, int i) {
     return *reinterpret_cast<const float4 *>(out + i);
   }
 };
 
-#ifdef RDSP_EXPERIMENTAL
-#include "rdsp_tail_lookahead.h" /* tests/micro/not_adopted/, on the include path of EXPERIMENTAL=1 builds */
-#endif
-
 /* health word of one NLMS instance at the end of a launch (kernel params, st_status): bit 0 when some
  * lane of the channel divided by energy + eps <= 0, bit 1 when a weight or the energy is not finite
  * (0 * x is NaN exactly for those; the row sum carries it to every lane) */
-template <typename NL>
-__device__ __forceinline__ uint32_t nlms_health(const NL &f) {
+__device__ __forceinline__ uint32_t nlms_health(const NlmsB &f) {
   float z = f.energy * 0.f;
 #pragma unroll
-  for (int k = 0; k < NL::TPL / 2; k++) z = fmaf(f.w2[k][0], 0.f, fmaf(f.w2[k][1], 0.f, z));
+  for (int k = 0; k < NlmsB::TPL / 2; k++) z = fmaf(f.w2[k][0], 0.f, fmaf(f.w2[k][1], 0.f, z));
   const float bad_e = row_allsum(f.emin <= 0.f ? 1.f : 0.f);
   const float nf = row_allsum(z);
   return (bad_e > 0.f ? 1u : 0u) | (nf == 0.f ? 0u : 2u);
@@ -303,25 +296,24 @@ __device__ __forceinline__ uint32_t nlms_health(const NL &f) {
 
 /* One wave per workgroup throughout: wg_sync<1>() (rdsp_wave.h) orders the lanes' LDS traffic without the
  * `s_waitcnt lgkmcnt(0)` a __syncthreads() leaves behind. */
-template <bool DUAL, typename NL>
+template <bool DUAL>
 __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
 #ifdef RDSP_TAIL_PROFILE
   long long tp_acc[4] = {0, 0, 0, 0}, tp_last = __builtin_readcyclecounter();
 #endif
   constexpr int CPW = 4, SPL = RDSP_BLOCK / 16; /* channels per wave, samples per lane per block */
   constexpr int RINGS = DUAL ? 2 : 1;
-  constexpr int FIN = NL::OUT_IN_SCR ? 0 : RDSP_BLOCK;
+  constexpr int FIN = RDSP_BLOCK; /* the 128 outputs of the last NLMS instance, handed to the AGC */
   /* consecutive channels start 32 dwords apart mod 64: the even sample pairs of the two channels of a
    * 32-lane group (float2 index -3 sub each) then fall on disjoint halves of the 64 banks */
   /* A ring is four block slots, [M | S0 | S1 | S2].  Block b lives in S(b mod 3) and M mirrors S2, so the block in
-   * front of the current one always lies right below it -- [previous | current], which is what NL::block() takes --
+   * front of the current one always lies right below it -- [previous | current], which is what NlmsB::block() takes --
    * and no block is ever moved: the slot of the block after next is simply written over.  Keeping M costs two
    * stores per lane every third block (the block that lands in S2 is stored twice). */
   constexpr int SLOTS = 4;
-  constexpr int PER_CH0 = SLOTS * RINGS * RDSP_BLOCK + FIN + NL::LDS_SCR;
+  constexpr int PER_CH0 = SLOTS * RINGS * RDSP_BLOCK + FIN;
   constexpr int PER_CH = PER_CH0 + (96 - PER_CH0 % 64) % 64;
   static_assert(PER_CH % 64 == 32 && PER_CH % 4 == 0, "channel pitch in LDS");
-  static_assert(!(DUAL && NL::OUT_IN_SCR), "the two-instance kernel hands a block on through `out`");
   __shared__ __attribute__((aligned(16))) float lds[CPW][PER_CH];
   if (p.prio == 1) __builtin_amdgcn_s_setprio(1);
   else if (p.prio == 2) __builtin_amdgcn_s_setprio(2);
@@ -335,7 +327,6 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
   float *ringA = &lds[cw][0];
   float *ringB = DUAL ? &lds[cw][SLOTS * RDSP_BLOCK] : ringA;
   float *fin = &lds[cw][SLOTS * RINGS * RDSP_BLOCK];
-  float *scr = &lds[cw][SLOTS * RINGS * RDSP_BLOCK + FIN]; /* NL::LDS_SCR floats (none for NlmsB) */
 
   const bool has_inst = DUAL || p.nr_on || p.als_mode;
   const bool one_is_nr = !DUAL && p.nr_on;
@@ -346,7 +337,7 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
   const int o_first = one_is_nr ? p.nr_first : p.als_first;
   const int o_mode = one_is_nr ? p.nr_mode : p.als_mode; /* 0: 1.1*y, 1: e, 2: y */
 
-  NL nr, als; /* !DUAL: `als` is the one instance */
+  NlmsB nr, als; /* !DUAL: `als` is the one instance */
   if constexpr (DUAL) {
     nr.load(p.nr_w, p.nr_energy, ch, sub);
     als.load(p.als_w, p.als_energy, ch, sub);
@@ -396,7 +387,7 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
     if constexpr (DUAL) { /* CONV:326-337, then the ALS filter */
       float *rB = ringB + slot * RDSP_BLOCK;
       float *o = rB + RDSP_BLOCK;
-      nr.template block<false>(rA, p.nr_first && b == 0, p.nr_mu, o, scr, sub, p.energy_running != 0);
+      nr.template block<false>(rA, p.nr_first && b == 0, p.nr_mu, o, sub, p.energy_running != 0);
       wg_sync<1>();
       if (p.nr_mode == 0) { /* CONV:334 */
 #pragma unroll
@@ -409,11 +400,11 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
 #pragma unroll
         for (int k = 0; k < SPL / 4; k++) m4[k] = o4[k];
       }
-      if (p.als_mode == 1) als.template block<true>(rB, p.als_first && b == 0, p.als_mu, fin, scr, sub, p.energy_running != 0);
-      else als.template block<false>(rB, p.als_first && b == 0, p.als_mu, fin, scr, sub, p.energy_running != 0);
+      if (p.als_mode == 1) als.template block<true>(rB, p.als_first && b == 0, p.als_mu, fin, sub, p.energy_running != 0);
+      else als.template block<false>(rB, p.als_first && b == 0, p.als_mu, fin, sub, p.energy_running != 0);
     } else if (has_inst) {
-      if (o_mode == 1) als.template block<true>(rA, o_first && b == 0, o_mu, fin, scr, sub, p.energy_running != 0);
-      else als.template block<false>(rA, o_first && b == 0, o_mu, fin, scr, sub, p.energy_running != 0);
+      if (o_mode == 1) als.template block<true>(rA, o_first && b == 0, o_mu, fin, sub, p.energy_running != 0);
+      else als.template block<false>(rA, o_first && b == 0, o_mu, fin, sub, p.energy_running != 0);
     }
     wg_sync<1>();
     RDSP_TP(1);
@@ -421,7 +412,7 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
     float L[SPL];
 #pragma unroll
     for (int k = 0; k < SPL / 4; k++) {
-      const float4 a = has_inst ? NL::out4(fin, scr, sub * SPL + 4 * k)
+      const float4 a = has_inst ? NlmsB::out4(fin, sub * SPL + 4 * k)
                                 : *reinterpret_cast<const float4 *>(rA + RDSP_BLOCK + sub * SPL + 4 * k);
       L[4 * k] = a.x; L[4 * k + 1] = a.y; L[4 * k + 2] = a.z; L[4 * k + 3] = a.w;
     }
@@ -534,36 +525,20 @@ __device__ __forceinline__ void tail_body(const RdspTailParams &p) {
 }
 
 /* two NLMS instances (DSP-NR feeding the ALS filter; the sketch's menu never enables both, CTL:240-296) */
-__global__ void __launch_bounds__(64) rdsp_tail_dual_kernel(RdspTailParams p) { tail_body<true, NlmsB>(p); }
+__global__ void __launch_bounds__(64) rdsp_tail_dual_kernel(RdspTailParams p) { tail_body<true>(p); }
 
 /* The default (one NLMS instance).  116 VGPRs, 128 allocated: in pipelined mode it shares a SIMD's 512 with
  * two waves of the frequency-domain front kernel (176 allocated each: 480 in all); a tail wave that does
  * not fit waits for a front wave to retire (measured in round 1: 1.8 -> 2.4 ms per K3 step).  The CPU suite
  * reads both counts out of the built code object (test_generated_code_keeps_...). */
 __global__ void __launch_bounds__(64) rdsp_tail_kernel(RdspTailParams p) {
-  tail_body<false, NlmsB>(p);
+  tail_body<false>(p);
 }
-#ifdef RDSP_EXPERIMENTAL
-/* weights one block stale / four steps per reduction (tests/micro/not_adopted/rdsp_tail_lookahead.h): measured, not adopted */
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) rdsp_tail_lookahead_kernel(RdspTailParams p) {
-  tail_body<false, NlmsL>(p);
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) rdsp_tail_four_kernel(RdspTailParams p) {
-  tail_body<false, NlmsQ>(p);
-}
-#endif
 
 }  // namespace
 
-#ifdef RDSP_EXPERIMENTAL
-extern "C" int rdsp_launch_tail_shift(const RdspTailParams *p, hipStream_t stream);            /* tests/micro/not_adopted/rdsp_tail_shift.hip */
-extern "C" int rdsp_launch_tail_layouts(const RdspTailParams *p, int variant, hipStream_t stream); /* tests/micro/not_adopted/rdsp_tail_layouts.hip */
-#endif
-
-/* variant 100: the product's kernel.  EXPERIMENTAL=1 builds also know 104 (weights one block stale), 105 (four
- * steps per reduction),
- * 16 (delay line shifted by DPP), 102 (one reduction per step), 101 (half a row per channel),
- * 116 / 108 (16 / 8 lanes with the reduction on the matrix pipe). */
+/* variant 100 is the kernel there is; the numbers of the variants that were measured and not adopted
+ * (docs/history.md) are not supported */
 extern "C" int rdsp_launch_tail(const RdspTailParams *p, int variant, hipStream_t stream) {
   const int grid = (p->n_channels - p->ch_base + 3) / 4;
   const bool dual = p->nr_on && p->als_mode;
@@ -572,15 +547,5 @@ extern "C" int rdsp_launch_tail(const RdspTailParams *p, int variant, hipStream_
     else hipLaunchKernelGGL(rdsp_tail_kernel, dim3(grid), dim3(64), 0, stream, *p);
     return (int)hipGetLastError();
   }
-#ifdef RDSP_EXPERIMENTAL
-  if (variant == 104 || variant == 105) {
-    if (dual) hipLaunchKernelGGL(rdsp_tail_dual_kernel, dim3(grid), dim3(64), 0, stream, *p);
-    else if (variant == 104) hipLaunchKernelGGL(rdsp_tail_lookahead_kernel, dim3(grid), dim3(64), 0, stream, *p);
-    else hipLaunchKernelGGL(rdsp_tail_four_kernel, dim3(grid), dim3(64), 0, stream, *p);
-    return (int)hipGetLastError();
-  }
-  if (variant == 16) return rdsp_launch_tail_shift(p, stream);
-  if (variant == 101 || variant == 102 || variant == 116 || variant == 108) return rdsp_launch_tail_layouts(p, variant, stream);
-#endif
   return (int)hipErrorNotSupported;
 }

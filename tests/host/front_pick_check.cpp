@@ -1,6 +1,6 @@
 // rdsp_front_pick (csrc/rdsp_kernels.h) over the whole grid of tests/test_front_pick.py: one line per point,
-//   error family radix lean pre fmx q4 frame      (the record's fields are printed as zeros behind an error)
-// in the order of the loops below; the first line says whether the library is an EXPERIMENTAL=1 build.
+//   error family radix lean pre q4 frame      (the record's fields are printed as zeros behind an error)
+// in the order of the loops below; the first line is what rdsp_experimental_build() answers (0: there is one build).
 // Host code only: nothing here touches a device.
 #include <cstdio>
 
@@ -35,17 +35,17 @@ int main() {
                     if (trigger == 3) p.scale_i_hist = 0.25f;           // scale_i_hist != scale_i
                     if (trigger == 4) p.scale_q_hist = 0.25f;           // scale_q_hist != scale_q
                     if (trigger == 5) p.scale_i = p.scale_i_hist = 1.f; // scale_i != scale_q
-                    RdspFrontPick k = {-1, -1, -1, -1, -1, -1, -1};
+                    RdspFrontPick k = {-1, -1, -1, -1, -1, -1};
                     const int e = rdsp_front_pick(fft_l, decim, &p, &k);
                     if (e != 0) {
                       // a refusal leaves the record alone
-                      if (k.family != -1 || k.radix != -1 || k.lean != -1 || k.pre != -1 || k.fmx != -1 || k.q4 != -1 || k.frame != -1) {
+                      if (k.family != -1 || k.radix != -1 || k.lean != -1 || k.pre != -1 || k.q4 != -1 || k.frame != -1) {
                         printf("record written behind error %d\n", e);
                         return 1;
                       }
                       k = RdspFrontPick{};
                     }
-                    printf("%d %d %d %d %d %d %d %d\n", e, k.family, k.radix, k.lean, k.pre, k.fmx, k.q4, k.frame);
+                    printf("%d %d %d %d %d %d %d\n", e, k.family, k.radix, k.lean, k.pre, k.q4, k.frame);
                   }
   return 0;
 }

@@ -1,7 +1,7 @@
 // Times the tail kernel alone (ALS notch instance, 4096 channels by default).
 // hipcc -O3 --offload-arch=gfx950 -std=c++17 -I radiodsp_sdr_rx_amd/csrc tests/micro/tail_bench.hip \
 //       -L radiodsp_sdr_rx_amd -lrdsp_hip -Wl,-rpath,$PWD/radiodsp_sdr_rx_amd -o tests/micro/tail_bench
-// usage: tail_bench [channels] [variant] [iterations]   variant 100 the product kernel (default; others: EXPERIMENTAL=1 builds)
+// usage: tail_bench [channels] [variant] [iterations]   variant 100, the tail kernel (default; every other number is refused: docs/history.md)
 #include "rdsp_kernels.h"
 #include <cstdio>
 #include <cstring>
@@ -10,7 +10,7 @@
 #include <vector>
 int main(int argc, char **argv) {
   int nch = argc > 1 ? atoi(argv[1]) : 4096, nb = 128;
-  const int variant = argc > 2 ? atoi(argv[2]) : 100;  // 100 row layout (default), 16 rdsp_tail.hip, 116 / 108 matrix pipe
+  const int variant = argc > 2 ? atoi(argv[2]) : 100;  // 100 row layout (default); the variants that were not adopted had numbers of their own (docs/history.md)
   size_t stride = (size_t)nb * 128;
   float *mid, *w, *prev, *en, *scal; uint32_t *out;
   hipMalloc(&mid, nch * stride * 4); hipMalloc(&w, nch * 96 * 4); hipMalloc(&prev, nch * 128 * 4); hipMalloc(&en, nch * 4);

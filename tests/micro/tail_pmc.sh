@@ -1,6 +1,6 @@
 #!/bin/bash
-# PMC passes of the tail kernel alone (tests/micro/tail_bench): the product (variant 100); with an EXPERIMENTAL=1
-# build of the library also 104 (weights one block stale) and 105 (four steps per reduction).
+# PMC passes of the tail kernel alone (tests/micro/tail_bench, variant 100).  Round 3 also ran them over 104 (weights
+# one block stale) and 105 (four steps per reduction), which the library no longer carries (docs/history.md).
 # usage (GPU box, repository root): bash tests/micro/tail_pmc.sh [variants...]
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/r3/tailpmc; mkdir -p $OUT; export TMPDIR=/tmp
 for V in ${@:-100}; do

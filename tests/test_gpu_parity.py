@@ -34,17 +34,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("front_form")]   # every 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _experimental():
-    """the library under test was built with EXPERIMENTAL=1 (not the product build)"""
-    try:
-        import radiodsp_sdr_rx_amd as R
-        return bool(R.load().rdsp_experimental_build())
-    except Exception:
-        return False
-
-
-EXPERIMENTAL = _experimental()
-TAILS = ["16r"] + (["16", "8r", "16m", "8m", "16l", "16q"] if EXPERIMENTAL else [])
+TAILS = ["16r"]
 
 
 @pytest.fixture(scope="module")
@@ -55,20 +45,11 @@ def torch_cuda():
 
 
 def gpu_run(torch, iq, cfg, calls=1, tail=None, setup=None, fir=None):
-    """tail: None or "16r" (the product's tail kernel); "16", "8r", "16m", "8m": experimental layouts"""
+    """tail: None or "16r" (the tail kernel: a channel per 16-lane row, two steps per reduction)"""
     from radiodsp_sdr_rx_amd.chain import Chain
     nch, n = iq.shape[0], iq.shape[1]
     ch = Chain(nch, max_blocks_per_call=n // 128 // calls, **cfg)
-    if tail == "16r":
-        pass
-    elif tail == "8r":  # half-row layout (EXPERIMENTAL builds)
-        ch.set_tail_variant(8, 2)
-    elif tail == "16l":  # weights one block stale, hand-interleaved issue order (EXPERIMENTAL builds)
-        ch.set_tail_variant(16, 4)
-    elif tail == "16q":  # four steps per reduction (EXPERIMENTAL builds)
-        ch.set_tail_variant(16, 5)
-    elif tail:          # "16": rdsp_tail.hip; "16m" / "8m": matrix-pipe reduction
-        ch.set_tail_variant(int(tail.rstrip("m")), int(tail.endswith("m")))
+    assert tail in (None, "16r")
     apply_setup(ch, setup)
     if fir is not None:   # stage A3: 0 direct form, 2 frequency domain with 448-sample frames, -1 / 4 granule frames (None: the module's `front_form`)
         ch.set_fir_variant(fir)
@@ -203,22 +184,6 @@ def test_spectral_stage_as_written_matches_the_oracle_as_written(rdsp, oracle, t
     assert e_lt <= max(2e-6, 0.5 * bound)                          # the two evaluations of the as-written form: one result
     assert np.allclose(s_lit[:, 0], s_eq[:, 0], rtol=1e-5)         # NFloor: the threshold logic does not depend on the form
     assert 5e-6 <= cross <= 5e-5                                    # the table's interpolation error separates the forms
-
-
-@pytest.mark.skipif(not EXPERIMENTAL, reason="matrix-core FIR: EXPERIMENTAL=1 builds only")
-@pytest.mark.parametrize("name", ["k2_usb_256", "usb_1024", "lsb_2048", "k4_cw_4096_agc", "spectral_512"])
-def test_matrix_fir_variant_matches_oracle(rdsp, oracle, torch_cuda, name):
-    """rdsp_chain_set_fir_variant(1): the decimating FIR as v_mfma GEMM slices (opt-in)"""
-    torch = torch_cuda
-    from radiodsp_sdr_rx_amd.chain import Chain, synth_iq
-    cfg, nch, nblk, cw = FF_CASES[name]
-    iq = synth_iq(nch, nblk * 128, cw=cw)
-    ch = Chain(nch, max_blocks_per_call=nblk // 2, **cfg)
-    ch.set_fir_variant(1)
-    got = np.concatenate([ch.process(torch.from_numpy(np.ascontiguousarray(iq[:, k * (nblk // 2) * 128:(k + 1) * (nblk // 2) * 128])).cuda(),
-                                     want_f32=True)[1].cpu().numpy() for k in range(2)], 1)
-    _, r32 = oracle_run(oracle, iq, cfg)
-    assert normwise(got, r32) <= TOL
 
 
 @pytest.mark.parametrize("name", ["k1_one_channel", "k2_usb_256", "usb_512", "usb_1024", "lsb_2048", "k4_cw_4096_agc", "spectral_512",
@@ -515,12 +480,11 @@ NLMS_CASES = {
 @pytest.mark.parametrize("tail", TAILS)
 @pytest.mark.parametrize("name", sorted(NLMS_CASES))
 def test_chain_with_nlms_is_as_close_to_float64_truth_as_the_oracle(rdsp, oracle, torch_cuda, name, tail):
-    """tail "16r": the product's tail kernel (row layout, two steps per reduction).  The experimental
-    layouts ("16": delay line shifted by DPP; "8r": half a row; "16m", "8m": reduction on the
-    matrix pipe) are only in the library when it is built with EXPERIMENTAL=1."""
+    """tail "16r": the tail kernel (row layout, two steps per reduction).  The layouts that were measured and not
+    adopted (delay line shifted by DPP, half a row, reduction on the matrix pipe) are in docs/history.md."""
     from radiodsp_sdr_rx_amd.chain import synth_iq
     cfg = NLMS_CASES[name]
-    nch, nblk = 11 if tail == "8m" else 5, 64          # partly filled last waves (8 / 4 channels per wave)
+    nch, nblk = 5, 64          # a partly filled last wave (4 channels per wave)
     iq = synth_iq(nch, nblk * 128)
     o16, o32, _ = gpu_run(torch_cuda, iq, cfg, calls=2, tail=tail)
     r16, r32 = oracle_run(oracle, iq, cfg)
@@ -795,8 +759,8 @@ def test_front_kernel_variants_agree(rdsp, oracle, torch_cuda):
     cfg = dict(fft_l=512, demod="USB", spectral_nr=1, spectral_level=2.0, agc_mode="medium")
     iq = synth_iq(4, 32 * 128)
     _, r32 = oracle_run(oracle, iq, cfg)
-    # register-lean x stage A3 (0 direct form, 2 frequency domain, 1 matrix cores)
-    for lean, fir in ((0, 0), (1, 0), (0, 2), (1, 2)) + (((0, 1), (1, 1)) if EXPERIMENTAL else ()):
+    # register-lean x stage A3 (0 direct form, 2 frequency domain)
+    for lean, fir in ((0, 0), (1, 0), (0, 2), (1, 2)):
         ch = Chain(4, max_blocks_per_call=32, **cfg)
         ch.set_front_variant(lean)
         ch.set_fir_variant(fir)
