@@ -774,10 +774,56 @@ const float *rdsp_engine_tune_table(void);
  *   128 x D pairs (src_stride at least that); d_lr, out_stride and max_blocks count 44 100 Hz samples as before.
  * - Refused with nothing changed (RDSP_ERR_INVALID): D outside 1 ... 64, gain not above 0 or not finite, a channel already
  *   tuned to |f| >= D x 22 050.
- * - Out of scope: rational rate changes (the 48 kHz family) and decimation in several stages. */
+ * - Out of scope: decimation in several stages. */
 int rdsp_engine_set_source_decimation(rdsp_engine_t *e, int D, float gain);
 int rdsp_engine_source_decimation(const rdsp_engine_t *e);
 int rdsp_engine_ddc_taps(int D, float gain, float *out /* [16 D] */);
+/* Sources at any rational multiple of 44 100 Hz: rows at 44 100 P / Q Hz (48 k = 160 / 147, 96 k = 320 / 147, 192 k = 640 / 147,
+ * 2.4 M = 8000 / 147, 250 k = 2500 / 441, 1.024 M = 10240 / 441, 2.048 M = 20480 / 441; Q is 147 or 441 for every integer-Hz rate
+ * on the 1 kHz or 2 kHz grid).  The pass becomes a polyphase rational resampler: it tunes, low-passes and changes the rate by
+ * Q / P in one pass per receiver (csrc/rdsp_engine_rate.hip, arithmetic in csrc/rdsp_tune.h).
+ * - rdsp_engine_set_source_rate(e, P, Q, gain), after rdsp_engine_set_sources (RDSP_ERR_NOT_READY before).  P, Q are divided
+ *   by their gcd first; after that 1 <= Q <= 441, Q <= P <= 64 Q, gain finite and above 0.  Q = 1 after reduction IS
+ *   rdsp_engine_set_source_decimation(e, P, gain): the same code path, the same bits.  rdsp_engine_set_source_decimation
+ *   called later replaces a rational rate.  Dc = ceil(P / Q); a branch of the filter has Tb = 16 Dc taps.
+ * - The prototype (rdsp_engine_rate_taps, host only, Tp = Tb Q floats): the low-pass of rdsp_engine_ddc_taps at the rate
+ *   44 100 P -- a sinc with its cutoff at 22 050 Hz under a Kaiser window, beta = 9, by the same libm-free series, with
+ *   q = |2 i - (Tp - 1)|, u = pi q / (2 P), rho = q / (Tp - 1), summed in tap order, out[i] = (float)((h[i] / sum) (Q gain)).
+ *   For Q = 1 it is rdsp_engine_ddc_taps(P, gain) bit for bit.  Branch r is hb[r][j] = out[j Q + r], j = 0 ... Tb - 1: the tap
+ *   for a delay of j + r / Q source samples.  Over the rates of tests/test_engine_rate.py: ripple <= 0.001 dB on |f| <=
+ *   12 000 Hz, >= 89 dB down from 32 100 Hz to the prototype's Nyquist frequency (the images of the source spectrum
+ *   included), sum_j |hb[r][j]| <= 2.5 (a branch of a ratio near 1 spans up to 32 output periods).
+ * - Schedule: one integer for all sources, frac = (M P) mod Q, M the outputs since the last reset: zero at create, after
+ *   rdsp_engine_reset and when the rate or n_sources changes (the source histories are zeroed on the same occasions).  A call
+ *   of n_out = n_blocks x 128 outputs consumes pairs = (frac + n_out P) div Q pairs of every source row, then frac <- (frac +
+ *   n_out P) mod Q.  rdsp_engine_source_pairs(e, n_blocks) returns pairs for the NEXT call (it varies by one between calls;
+ *   for an integer rate it is n_blocks x 128 x D).  Output i of a call has its newest source pair at local index n(i) =
+ *   (frac + (i + 1) P) div Q - 1 and uses branch r(i) = (frac + (i + 1) P) mod Q (64-bit products).
+ * - Arithmetic, x the source row with the pairs of earlier calls before it:
+ *     dphi = llround((TuningOffset - station) 2^32 / ((P 44100.0) / Q))  (uint32)
+ *     e_j  = table phasor at 0 - j dphi;  u_j = (hb[r(i)][j] xI[n(i) - j], hb[r(i)][j] xQ[n(i) - j]), two rounded products;
+ *     one chain over j ascending from re = im = 0, four fmaf a tap: re += e.x u.x; re += -e.y u.y; im += e.x u.y; im += e.y u.x;
+ *     y[i] = the tuning pass's rotation, rounding and saturation at the phase ph0 + (n(i) + 1 - Dc) dphi;
+ *     the phase after the call is ph0 + pairs dphi.
+ *   The order has no tile, register block or call size in it, so neither has the result; tests/test_engine_rate.py restates
+ *   it in numpy bit for bit, and the audio is bit for bit rdsp_engine_update on the tuned rows.
+ * - State: per channel the one phase, with all its rules (continuous through calls, retunes, mode changes and regroupings,
+ *   zeroed by reset, in the blob behind the header flag).  Per SOURCE the last Tb pairs; they are in no blob and blob sizes
+ *   are unchanged: a moved receiver continues bit for bit when both engines heard the same source stream since the same
+ *   reset.
+ * - With a rational rate set: |station_hz| < 22 050 P / Q in rdsp_engine_tune; rdsp_engine_update_sources reads
+ *   rdsp_engine_source_pairs(e, n_blocks) pairs per row, src_stride at least that, rows and stride int16-PAIR (4-byte)
+ *   aligned only, so a host can walk a pointer through a long recording (the 16-byte rule stays for Q = 1);
+ *   rdsp_engine_source_decimation returns 0; rdsp_engine_source_rate gives P, Q (D, 1 for an integer rate).
+ * - rdsp_engine_rate_of_hz(fs_hz, &P, &Q): for an integer-Hz rate fs / g, 44100 / g, g their gcd; refused when fs is not an
+ *   integer or the ratio is outside the limits above (44 101 Hz: Q = 44 100; 32 000 Hz: P < Q; 3.2 MHz: above 64).
+ * - Refused with nothing changed (RDSP_ERR_INVALID): P or Q below 1, Q above 441 or P outside Q ... 64 Q after reduction, gain
+ *   not above 0 or not finite, a channel already tuned to |f| >= 22 050 P / Q, a src_stride below rdsp_engine_source_pairs. */
+int rdsp_engine_set_source_rate(rdsp_engine_t *e, int P, int Q, float gain);
+int rdsp_engine_source_rate(const rdsp_engine_t *e, int *P, int *Q);
+size_t rdsp_engine_source_pairs(const rdsp_engine_t *e, int n_blocks);
+int rdsp_engine_rate_of_hz(double fs_hz, int *P, int *Q);
+int rdsp_engine_rate_taps(int P, int Q, float gain, float *out /* [16 ceil(P / Q) Q], P / Q in lowest terms */);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -289,6 +289,11 @@ SYMBOLS = [
     ("rdsp_engine_set_source_decimation", _i, [_vp, _i, C.c_float]),
     ("rdsp_engine_source_decimation", _i, [_vp]),
     ("rdsp_engine_ddc_taps", _i, [_i, C.c_float, _f32p]),
+    ("rdsp_engine_set_source_rate", _i, [_vp, _i, _i, C.c_float]),
+    ("rdsp_engine_source_rate", _i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("rdsp_engine_source_pairs", C.c_size_t, [_vp, _i]),
+    ("rdsp_engine_rate_of_hz", _i, [_d, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("rdsp_engine_rate_taps", _i, [_i, _i, C.c_float, _f32p]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

@@ -32,11 +32,14 @@ enum { PL_ST, PL_RING_I, PL_RING_Q, PL_NB, PL_ALS, N_PLANES };
 struct EngSources {
   DevBuf<uint32_t> phase, dphi, tuned;
   DevBuf<int> source_of, order, wg_first, wg_count;
+  DevBuf<int> rate_wg_first, rate_wg_count; /* the polyphase pass's workgroups: runs of at most RATE_RPW receivers */
   DevBuf<float4> tune_tab;
   rdsp_dev::Event dphi_ev; /* the last upload of dphi has left dphi_stage */
 };
 /* sources at D > 1: the prototype's taps, every receiver's translated taps, and per SOURCE the last 15 D pairs */
 struct EngDdc { DevBuf<float> h; DevBuf<float2> g; DevBuf<uint32_t> hist; };
+/* sources at 44 100 P / Q Hz, Q > 1: the prototype by branches hb[r][j], per SOURCE the last Tb pairs, the call's schedule */
+struct EngRate { DevBuf<float> hb; DevBuf<uint32_t> hist; DevBuf<rdsp_tune::RateStep> sched; };
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -60,6 +63,10 @@ struct rdsp_engine {
   int n_sources = 0, ddc_D = 1, n_wg = 0;
   float ddc_gain = 1.0f;
   std::unique_ptr<EngDdc> ddc; /* while ddc_D > 1 */
+  /* sources at 44 100 rate_P / rate_Q Hz (rdsp_engine_set_source_rate), in lowest terms; while `rate` exists rate_Q > 1 and ddc_D is 1 */
+  int rate_P = 1, rate_Q = 1, n_rate_wg = 0;
+  uint32_t frac = 0; /* (outputs since the last reset x rate_P) mod rate_Q */
+  std::unique_ptr<EngRate> rate;
 };
 
 namespace {
@@ -81,6 +88,10 @@ P source_pass(const rdsp_engine_t *e, const int16_t *d_src, size_t src_stride) {
   p.order = e->src->order; p.source_of = e->src->source_of;
   p.phase = e->src->phase; p.dphi = e->src->dphi; p.tab = e->src->tune_tab; p.n_channels = e->n_channels;
   return p;
+}
+/* |station| must stay below it: half the source rate */
+double source_band_hz(const rdsp_engine_t *e) {
+  return e->rate ? (rdsp_tune::TUNE_MAX_HZ * (double)e->rate_P) / (double)e->rate_Q : (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ;
 }
 /* the setters address the selected group, or all of them */
 template <typename F>
@@ -273,6 +284,8 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
                           : hipMemcpyAsync(e->plane[k], fill[k].data(), fill[k].size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess && e->src) err = hipMemsetAsync(e->src->phase, 0, n * 4, s); /* the stations are settings: kept */
   if (err == hipSuccess && e->ddc) err = hipMemsetAsync(e->ddc->hist, 0, (size_t)e->n_sources * rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D * 4, s);
+  if (err == hipSuccess && e->rate) err = hipMemsetAsync(e->rate->hist, 0, (size_t)e->n_sources * (size_t)rdsp_tune::rate_tb(e->rate_P, e->rate_Q) * 4, s);
+  e->frac = 0;
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -396,7 +409,8 @@ hipError_t upload_dphi(rdsp_engine_t *e, hipStream_t s) {
   e->tune_to.resize(e->grp.size());
   for (size_t g = 0; g < e->grp.size(); g++) {
     const int c1 = range_end(e->first, g, e->n_channels);
-    for (int c = e->first[g]; c < c1; c++) e->dphi_stage[(size_t)c] = rdsp_tune::ddc_dphi(e->grp[g].tuning_offset, e->station[(size_t)c], e->ddc_D);
+    for (int c = e->first[g]; c < c1; c++) e->dphi_stage[(size_t)c] = e->rate ? rdsp_tune::rate_dphi(e->grp[g].tuning_offset, e->station[(size_t)c], e->rate_P, e->rate_Q)
+                                                                      : rdsp_tune::ddc_dphi(e->grp[g].tuning_offset, e->station[(size_t)c], e->ddc_D);
     e->tune_to[g] = e->grp[g].tuning_offset;
   }
   if (err == hipSuccess) err = hipMemcpyAsync(e->src->dphi, e->dphi_stage.data(), e->dphi_stage.size() * 4, hipMemcpyHostToDevice, s);
@@ -408,6 +422,12 @@ hipError_t upload_dphi(rdsp_engine_t *e, hipStream_t s) {
  * The caller has waited for queued work. */
 hipError_t ddc_setup(rdsp_engine_t *e, int D, float gain, int n_sources) {
   hipError_t err = hipSuccess;
+  if (e->rate) { /* an integer rate replaces a rational one: its histories and its schedule go */
+    e->rate.reset();
+    e->rate_P = e->rate_Q = 1;
+    e->frac = 0;
+    e->n_sources = -1; /* what follows is new */
+  }
   if (D != e->ddc_D || n_sources != e->n_sources) {
     e->ddc.reset();
     e->ddc_D = 1; /* until everything below exists */
@@ -430,6 +450,33 @@ hipError_t ddc_setup(rdsp_engine_t *e, int D, float gain, int n_sources) {
     if (err != hipSuccess) return err;
   }
   e->ddc_D = D;
+  e->ddc_gain = gain;
+  e->dphi_stale = true; /* the step is per source sample */
+  return hipSuccess;
+}
+/* the device side of a rate P / Q (lowest terms, Q > 1) on n_sources rows: histories and schedule are new (zero) when the
+ * rate or the number of rows changed, the taps always.  The caller has waited for queued work. */
+hipError_t rate_setup(rdsp_engine_t *e, int P, int Q, float gain, int n_sources) {
+  const size_t Tb = (size_t)rdsp_tune::rate_tb(P, Q), keep = (size_t)n_sources * Tb;
+  std::vector<float> h(Tb * (size_t)Q), hb(Tb * (size_t)Q);
+  rdsp_tune::rate_taps(P, Q, (double)gain, h.data());
+  for (size_t r = 0; r < (size_t)Q; r++)
+    for (size_t j = 0; j < Tb; j++) hb[r * Tb + j] = h[j * (size_t)Q + r];
+  if (!e->rate || P != e->rate_P || Q != e->rate_Q || n_sources != e->n_sources) {
+    auto d = std::make_unique<EngRate>();
+    hipError_t err = d->hb.alloc(hb.size());
+    if (err == hipSuccess) err = d->hist.alloc(keep);
+    if (err == hipSuccess) err = d->sched.alloc((size_t)e->max_blocks * BS);
+    if (err == hipSuccess) err = hipMemset(d->hist, 0, keep * 4);
+    if (err != hipSuccess) return err;
+    e->rate = std::move(d);
+    e->ddc.reset(); /* a rational rate replaces an integer one */
+    e->ddc_D = 1;
+    e->rate_P = P; e->rate_Q = Q; e->n_sources = n_sources;
+    e->frac = 0;
+  }
+  const hipError_t err = hipMemcpy(e->rate->hb, hb.data(), hb.size() * 4, hipMemcpyHostToDevice);
+  if (err != hipSuccess) return err;
   e->ddc_gain = gain;
   e->dphi_stale = true; /* the step is per source sample */
   return hipSuccess;
@@ -468,6 +515,15 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
     wg_count.push_back((int)(j - i));
     i = j;
   }
+  /* the polyphase pass's: runs of at most RATE_RPW */
+  std::vector<int> rate_wg_first, rate_wg_count;
+  for (size_t i = 0; i < n;) {
+    size_t j = i + 1;
+    while (j < n && j - i < (size_t)rdsp_tune::RATE_RPW && source_of_channel[order[j]] == source_of_channel[order[i]]) j++;
+    rate_wg_first.push_back((int)i);
+    rate_wg_count.push_back((int)(j - i));
+    i = j;
+  }
   hipError_t err = hipSetDevice(e->device);
   if (err == hipSuccess && e->src) err = hipDeviceSynchronize(); /* queued passes may still read the old map */
   if (err == hipSuccess && !e->src) {
@@ -478,6 +534,8 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
     if (err == hipSuccess) err = q->order.alloc(n);
     if (err == hipSuccess) err = q->wg_first.alloc(n);
     if (err == hipSuccess) err = q->wg_count.alloc(n);
+    if (err == hipSuccess) err = q->rate_wg_first.alloc(n);
+    if (err == hipSuccess) err = q->rate_wg_count.alloc(n);
     if (err == hipSuccess) err = q->tune_tab.alloc(rdsp_tune::TUNE_N);
     if (err == hipSuccess) err = q->tuned.alloc(n * (size_t)e->max_blocks * BS);
     if (err == hipSuccess) err = q->dphi_ev.create(hipEventDisableTiming);
@@ -496,9 +554,13 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
   if (err == hipSuccess) err = hipMemcpy(e->src->order, order.data(), n * sizeof(int), hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(e->src->wg_first, wg_first.data(), wg_first.size() * sizeof(int), hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(e->src->wg_count, wg_count.data(), wg_count.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = ddc_setup(e, e->ddc_D, e->ddc_gain, n_sources); /* another number of rows: their histories start at zero */
+  if (err == hipSuccess) err = hipMemcpy(e->src->rate_wg_first, rate_wg_first.data(), rate_wg_first.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(e->src->rate_wg_count, rate_wg_count.data(), rate_wg_count.size() * sizeof(int), hipMemcpyHostToDevice);
+  /* another number of rows: their histories start at zero */
+  if (err == hipSuccess) err = e->rate ? rate_setup(e, e->rate_P, e->rate_Q, e->ddc_gain, n_sources) : ddc_setup(e, e->ddc_D, e->ddc_gain, n_sources);
   if (err != hipSuccess) return engine_fail("rdsp_engine_set_sources", err);
   e->n_wg = (int)wg_first.size();
+  e->n_rate_wg = (int)rate_wg_first.size();
   e->dphi_stale = true;
   return RDSP_OK;
 }
@@ -526,7 +588,64 @@ int rdsp_engine_set_source_decimation(rdsp_engine_t *e, int D, float gain) {
   if (err == hipSuccess) err = ddc_setup(e, D, gain, e->n_sources);
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_set_source_decimation", err);
 }
-int rdsp_engine_source_decimation(const rdsp_engine_t *e) { return e ? e->ddc_D : 0; }
+int rdsp_engine_source_decimation(const rdsp_engine_t *e) { return e && !e->rate ? e->ddc_D : 0; }
+
+int rdsp_engine_set_source_rate(rdsp_engine_t *e, int P, int Q, float gain) {
+  if (!e || !rdsp_tune::rate_reduce(P, Q) || !(gain > 0.0f) || !std::isfinite(gain)) {
+    rdsp_set_error("rdsp_engine_set_source_rate: bad argument (in lowest terms 1 <= Q <= %d and Q <= P <= %d Q: P %d, Q %d; gain %g must be "
+                   "finite and above 0)", rdsp_tune::RATE_MAX_Q, rdsp_tune::RATE_MAX_RATIO, P, Q, (double)gain);
+    return RDSP_ERR_INVALID;
+  }
+  if (!e->src) {
+    rdsp_set_error("rdsp_engine_set_source_rate: no sources; call rdsp_engine_set_sources first");
+    return RDSP_ERR_NOT_READY;
+  }
+  if (Q == 1) return rdsp_engine_set_source_decimation(e, P, gain); /* an integer multiple: the decimating pass itself */
+  const double band = (rdsp_tune::TUNE_MAX_HZ * (double)P) / (double)Q;
+  for (size_t c = 0; c < e->station.size(); c++)
+    if (!(fabs(e->station[c]) < band)) {
+      rdsp_set_error("rdsp_engine_set_source_rate: channel %zu is tuned to %g Hz, outside a source at 44100 x %d / %d Hz", c, e->station[c], P, Q);
+      return RDSP_ERR_INVALID;
+    }
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = hipDeviceSynchronize(); /* queued passes read the taps and the histories */
+  if (err == hipSuccess) err = rate_setup(e, P, Q, gain, e->n_sources);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_set_source_rate", err);
+}
+int rdsp_engine_source_rate(const rdsp_engine_t *e, int *P, int *Q) {
+  if (!e || !P || !Q) return RDSP_ERR_INVALID;
+  *P = e->rate ? e->rate_P : e->ddc_D;
+  *Q = e->rate ? e->rate_Q : 1;
+  return RDSP_OK;
+}
+size_t rdsp_engine_source_pairs(const rdsp_engine_t *e, int n_blocks) {
+  if (!e || n_blocks < 0) return 0;
+  const uint32_t n_out = (uint32_t)n_blocks * BS;
+  return e->rate ? (size_t)rdsp_tune::rate_pairs(e->frac, e->rate_P, e->rate_Q, n_out) : (size_t)n_out * (size_t)e->ddc_D;
+}
+int rdsp_engine_rate_of_hz(double fs_hz, int *P, int *Q) {
+  const double top = (double)rdsp_tune::RATE_MAX_RATIO * rdsp_tune::TUNE_FS;
+  if (!P || !Q || !(fs_hz >= rdsp_tune::TUNE_FS) || !(fs_hz <= top) || fs_hz != floor(fs_hz)) {
+    rdsp_set_error("rdsp_engine_rate_of_hz: %g Hz is not an integer rate in 44100 ... %g Hz", fs_hz, top);
+    return RDSP_ERR_INVALID;
+  }
+  int p = (int)fs_hz, q = 44100;
+  if (!rdsp_tune::rate_reduce(p, q)) {
+    rdsp_set_error("rdsp_engine_rate_of_hz: %g Hz is 44100 x %d / %d, outside Q <= %d", fs_hz, p, q, rdsp_tune::RATE_MAX_Q);
+    return RDSP_ERR_INVALID;
+  }
+  *P = p; *Q = q;
+  return RDSP_OK;
+}
+int rdsp_engine_rate_taps(int P, int Q, float gain, float *out) {
+  if (!rdsp_tune::rate_reduce(P, Q) || !(gain > 0.0f) || !std::isfinite(gain) || !out) {
+    rdsp_set_error("rdsp_engine_rate_taps: bad argument (in lowest terms 1 <= Q <= %d and Q <= P <= %d Q: P %d, Q %d; gain %g)",
+                   rdsp_tune::RATE_MAX_Q, rdsp_tune::RATE_MAX_RATIO, P, Q, (double)gain);
+    return RDSP_ERR_INVALID;
+  }
+  rdsp_tune::rate_taps(P, Q, (double)gain, out);
+  return RDSP_OK;
+}
 int rdsp_engine_ddc_taps(int D, float gain, float *out) {
   if (D < 1 || D > rdsp_tune::DDC_MAX_D || !(gain > 0.0f) || !std::isfinite(gain) || !out) {
     rdsp_set_error("rdsp_engine_ddc_taps: bad argument (D %d of 1 .. %d, gain %g)", D, rdsp_tune::DDC_MAX_D, (double)gain);
@@ -542,8 +661,8 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
     return RDSP_ERR_INVALID;
   }
   for (int k = 0; k < n_channels; k++)
-    if (!(fabs(station_hz[k]) < (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ)) {
-      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ);
+    if (!(fabs(station_hz[k]) < source_band_hz(e))) {
+      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], source_band_hz(e));
       return RDSP_ERR_INVALID;
     }
   if (e->station.empty()) e->station.assign((size_t)e->n_channels, 0.0);
@@ -553,7 +672,14 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
 }
 
 int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
-  if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS * (size_t)e->ddc_D || src_stride % 4 != 0 ||
+  if (e && e->rate) { /* a rational rate: rows of rdsp_engine_source_pairs pairs, int16-pair aligned */
+    if (!d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < rdsp_engine_source_pairs(e, n_blocks) || ((uintptr_t)d_src & 3) != 0 ||
+        out_stride < (size_t)n_blocks * BS) {
+      rdsp_set_error("rdsp_engine_update_sources: bad argument (n_blocks %d of at most %d; source rows 4-byte aligned and at least "
+                     "rdsp_engine_source_pairs = %zu pairs long at 44100 x %d / %d Hz)", n_blocks, e->max_blocks, rdsp_engine_source_pairs(e, std::max(n_blocks, 0)), e->rate_P, e->rate_Q);
+      return RDSP_ERR_INVALID;
+    }
+  } else if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS * (size_t)e->ddc_D || src_stride % 4 != 0 ||
       ((uintptr_t)d_src & 15) != 0 || out_stride < (size_t)n_blocks * BS) {
     rdsp_set_error("rdsp_engine_update_sources: bad argument (n_blocks %d of at most %d; source rows 16-byte aligned, a multiple of 4 "
                    "pairs apart and at least n_blocks * 128 * D long, D = %d)", n_blocks, e ? e->max_blocks : 0, e ? e->ddc_D : 0);
@@ -572,7 +698,14 @@ int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t sr
   hipError_t err = hipSetDevice(e->device);
   if (err == hipSuccess) err = upload_dphi(e, s);
   if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources", err);
-  if (e->ddc_D > 1) { /* tune, low-pass and decimate: rdsp_engine_ddc.hip */
+  if (e->rate) { /* tune, low-pass and resample by Q / P: rdsp_engine_rate.hip */
+    auto q = source_pass<rdsp_tune::RateParams>(e, d_src, src_stride);
+    q.hist = e->rate->hist; q.hb = e->rate->hb; q.sched = e->rate->sched; q.wg_first = e->src->rate_wg_first; q.wg_count = e->src->rate_wg_count;
+    q.n_sources = e->n_sources; q.n_wg = e->n_rate_wg; q.P = e->rate_P; q.Q = e->rate_Q;
+    q.frac = e->frac; q.n_out = (uint32_t)n_blocks * BS; q.pairs = (uint32_t)rdsp_engine_source_pairs(e, n_blocks);
+    err = rdsp_engine_rate_launch(q, s);
+    if (err == hipSuccess) e->frac = rdsp_tune::rate_frac_after(e->frac, e->rate_P, e->rate_Q, q.n_out);
+  } else if (e->ddc_D > 1) { /* tune, low-pass and decimate: rdsp_engine_ddc.hip */
     auto q = source_pass<rdsp_tune::DdcParams>(e, d_src, src_stride);
     q.hist = e->ddc->hist; q.h = e->ddc->h; q.g = e->ddc->g; q.wg_first = e->src->wg_first; q.wg_count = e->src->wg_count;
     q.n_sources = e->n_sources; q.n_wg = e->n_wg; q.D = e->ddc_D; q.n_out = (uint32_t)n_blocks * BS;

@@ -193,9 +193,108 @@ struct DdcParams {
   uint32_t n_out;                           /* a multiple of 128 */
 };
 
+/* ---- sources at 44 100 P / Q Hz: tune, low-pass and change the rate by Q / P in one polyphase pass (rdsp_engine_set_source_rate) --
+ * P / Q in lowest terms, 1 <= Q <= 441, Q <= P <= 64 Q; Q = 1 IS the decimating pass above (the engine routes it there).
+ * Dc = ceil(P / Q); a branch has Tb = 16 Dc taps; the prototype has Tp = Tb Q taps at the rate 44 100 P.
+ * Schedule: with M outputs since the last reset, frac = (M P) mod Q.  Output i of a call has its newest source pair at
+ * local index n(i) = (frac + (i + 1) P) div Q - 1 (>= 0, as P >= Q) and uses branch r(i) = (frac + (i + 1) P) mod Q; a call
+ * of n_out outputs consumes (frac + n_out P) div Q pairs and leaves frac = (frac + n_out P) mod Q.  The products are taken
+ * in 64 bits (n_out P reaches 1.9e9).
+ * Arithmetic of output i, x the row with the pairs of earlier calls before it, hb[r][j] = h[j Q + r]:
+ *   e_j = tune_phasor(0 - j dphi);  u_j = (hb[r][j] xI[n - j], hb[r][j] xQ[n - j]), two rounded products (rate_u);
+ *   ONE chain over j = 0 ... Tb - 1 per component from 0: ddc_mac(re, im, e_j, u_j.x, u_j.y);
+ *   y[i] = ddc_rot(re, im, tune_phasor(ph0 + (n + 1 - Dc) dphi));  the phase after the call is ph0 + pairs dphi.
+ * The tap multiplies the SAMPLE, not the phasor: u_j does not depend on the receiver, so a workgroup computes it once for
+ * all its receivers (rdsp_engine_rate.hip).  For Q = 1 the window and the phases are the decimating pass's. */
+constexpr int RATE_MAX_Q = 441;
+constexpr int RATE_MAX_RATIO = DDC_MAX_D; /* P <= 64 Q */
+
+RDSP_HD int rate_dc(int P, int Q) { return (P + Q - 1) / Q; }
+RDSP_HD int rate_tb(int P, int Q) { return DDC_TAPS_PER_PHASE * rate_dc(P, Q); }
+struct RateStep { int n, r; }; /* newest pair's local index, branch */
+RDSP_HD RateStep rate_step(uint32_t frac, int P, int Q, uint32_t i) {
+  const uint64_t t = (uint64_t)frac + ((uint64_t)i + 1u) * (uint64_t)P;
+  RateStep s;
+  s.n = (int)(t / (uint64_t)Q) - 1;
+  s.r = (int)(t % (uint64_t)Q);
+  return s;
+}
+/* pairs a call of n_out outputs consumes, and frac after it */
+RDSP_HD uint64_t rate_pairs(uint32_t frac, int P, int Q, uint32_t n_out) { return ((uint64_t)frac + (uint64_t)n_out * (uint64_t)P) / (uint64_t)Q; }
+RDSP_HD uint32_t rate_frac_after(uint32_t frac, int P, int Q, uint32_t n_out) { return (uint32_t)(((uint64_t)frac + (uint64_t)n_out * (uint64_t)P) % (uint64_t)Q); }
+
+/* host only: P / Q in lowest terms and inside the limits? (reduces in place) */
+inline bool rate_reduce(int &P, int &Q) {
+  if (P < 1 || Q < 1) return false;
+  int a = P, b = Q;
+  while (b) { const int t = a % b; a = b; b = t; }
+  P /= a; Q /= a;
+  return Q <= RATE_MAX_Q && P >= Q && (long long)P <= (long long)RATE_MAX_RATIO * Q;
+}
+/* host only: the step per source sample of a source at 44 100 P / Q Hz; Q = 1 gives ddc_dphi(..., P) */
+inline uint32_t rate_dphi(float tuning_offset, double station_hz, int P, int Q) {
+  return (uint32_t)(unsigned long long)llround(((double)tuning_offset - station_hz) * 4294967296.0 / (((double)P * TUNE_FS) / (double)Q));
+}
+/* host only, libm-free: the prototype, ddc_taps at the rate 44 100 P with Tp = Tb Q taps (cutoff 22 050 Hz, Kaiser beta 9),
+ * normalised to sum 1 (summed in tap order), times Q gain: every branch then sums to about gain.  Q = 1 gives ddc_taps(P)
+ * bit for bit.  Up to 451 584 taps: the doubles are taken from the heap. */
+inline void rate_taps(int P, int Q, double gain, float *out) {
+  const int Tp = rate_tb(P, Q) * Q;
+  double *h = new double[(size_t)Tp], sum = 0.0;
+  const double i0b = ddc_i0(DDC_KAISER_BETA);
+  for (int i = 0; i < Tp; i++) {
+    const int q = 2 * i - (Tp - 1) < 0 ? (Tp - 1) - 2 * i : 2 * i - (Tp - 1);
+    const double u = (3.141592653589793 * (double)q) / (2.0 * (double)P);
+    const double rho = (double)q / (double)(Tp - 1);
+    h[i] = (ddc_sin_halfpi(q, P) / u) * (ddc_i0(DDC_KAISER_BETA * sqrt(1.0 - rho * rho)) / i0b);
+  }
+  for (int i = 0; i < Tp; i++) sum += h[i];
+  const double scale = (double)Q * gain;
+  for (int i = 0; i < Tp; i++) out[i] = (float)((h[i] / sum) * scale);
+  delete[] h;
+}
+/* the tap on the sample: two rounded products */
+RDSP_HD float2 rate_u(float h, uint32_t w) {
+  return make_float2(h * (float)(int16_t)(uint16_t)(w & 0xffffu), h * (float)(int16_t)(uint16_t)(w >> 16));
+}
+/* one output: hb points at its branch's Tb taps, newest at x[n(i)] (the Tb - 1 words before it are read) */
+RDSP_HD uint32_t rate_output(const float4 *tab, const float *hb, int Tb, uint32_t dphi, const uint32_t *newest, float2 cs) {
+  float re = 0.0f, im = 0.0f;
+  uint32_t ph = 0u;
+  for (int j = 0; j < Tb; j++, ph -= dphi) { /* ph = 0 - j dphi */
+    const float2 u = rate_u(hb[j], newest[-j]);
+    ddc_mac(re, im, tune_phasor(tab, ph), u.x, u.y);
+  }
+  return ddc_rot(re, im, cs);
+}
+/* the phase of output i's rotation */
+RDSP_HD uint32_t rate_phase(uint32_t ph0, uint32_t dphi, int n, int Dc) { return ph0 + (uint32_t)(n + 1 - Dc) * dphi; }
+
+/* the polyphase pass's arguments.  Workgroup w takes the RATE_RPW-or-fewer receivers order[wg_first[w]] ... of ONE source. */
+constexpr int RATE_THREADS = 256;
+constexpr int RATE_C = 2;                 /* receivers per lane */
+constexpr int RATE_O = 16;                /* outputs per wave; two waves of a workgroup split a tile of 32 */
+constexpr int RATE_TILE = 2 * RATE_O;
+constexpr int RATE_RPW = 64 * RATE_C * 2; /* receivers per workgroup: two waves split them */
+constexpr int RATE_CHUNK = 128;           /* taps staged in LDS at a time */
+struct RateParams {
+  const uint32_t *src; size_t src_stride;   /* [source][t] words I | Q << 16, `pairs` per row, rows 4-byte aligned */
+  uint32_t *hist;                           /* [source][Tb]: the pairs before the call; rewritten after the pass */
+  uint32_t *dst; size_t dst_stride;         /* [ch][i] */
+  const int *order, *source_of;             /* [n_channels] */
+  const int *wg_first, *wg_count;           /* [n_wg] */
+  uint32_t *phase; const uint32_t *dphi;    /* [n_channels] */
+  const float4 *tab;                        /* [TUNE_N] */
+  const float *hb;                          /* [Q][Tb] */
+  RateStep *sched;                          /* [n_out], written by the pass's first kernel */
+  int n_channels, n_sources, n_wg, P, Q;
+  uint32_t frac, n_out, pairs;              /* n_out a multiple of 128 */
+};
+
 }  // namespace rdsp_tune
 
 hipError_t rdsp_engine_tune_launch(const rdsp_tune::TuneParams &p, hipStream_t s);
 hipError_t rdsp_engine_ddc_launch(const rdsp_tune::DdcParams &p, hipStream_t s);
+hipError_t rdsp_engine_rate_launch(const rdsp_tune::RateParams &p, hipStream_t s);
 
 #endif

@@ -72,18 +72,49 @@ class Engine:
     def source_decimation(self):
         return int(self.lib.rdsp_engine_source_decimation(self.h))
 
+    def set_source_rate(self, P, Q, gain=1.0):
+        """the source rows are at 44100 P / Q Hz (P / Q reduced first; then 1 <= Q <= 441, Q <= P <= 64 Q): update_sources()
+        tunes, low-passes and resamples by Q / P.  Q = 1 after reduction is set_source_decimation(P, gain).  After
+        set_sources()."""
+        check(self.lib.rdsp_engine_set_source_rate(self.h, int(P), int(Q), float(gain)))
+        self.D = self.source_decimation()                    # 0 while the rate is rational
+
+    def source_rate(self):
+        """(P, Q) in lowest terms; (D, 1) for an integer rate"""
+        p, q = C.c_int(), C.c_int()
+        check(self.lib.rdsp_engine_source_rate(self.h, C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    def source_pairs(self, n_blocks):
+        """pairs of every source row the NEXT update_sources(..., n_blocks=n_blocks) consumes"""
+        return int(self.lib.rdsp_engine_source_pairs(self.h, int(n_blocks)))
+
     def tune(self, first_channel, station_hz):
         """receivers first_channel ... get the stations station_hz (Hz from their source stream's centre, |f| < D x 22050)"""
         st = np.ascontiguousarray(np.atleast_1d(station_hz), np.float64)
         check(self.lib.rdsp_engine_tune(self.h, int(first_channel), st.size, st.ctypes.data_as(C.POINTER(C.c_double))))
 
-    def update_sources(self, d_src, out=None, stream=None):
+    def update_sources(self, d_src, out=None, stream=None, n_blocks=None):
         """d_src: torch int16 [n_sources, n D, 2] on the engine's device, n a multiple of 128, D the source decimation ->
         int16 [n_channels, n, 2]: every receiver tuned to its station in its source row (and for D > 1 low-passed and
-        decimated), then update()"""
+        decimated), then update().  With n_blocks: n = n_blocks x 128 outputs from the first source_pairs(n_blocks) pairs of
+        every row of d_src, which may be a view into a longer buffer (rows any even number of int16 apart); required with a
+        rational rate (set_source_rate)."""
         import torch
         nsrc, n_in, two = d_src.shape
         D = getattr(self, "D", 1)
+        if n_blocks is not None:
+            n, need = int(n_blocks) * 128, self.source_pairs(n_blocks)
+            assert two == 2 and d_src.dtype == torch.int16 and n_in >= need, "d_src holds fewer pairs than source_pairs(n_blocks)"
+            assert d_src.stride(2) == 1 and d_src.stride(1) == 2 and d_src.stride(0) % 2 == 0
+            assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
+            if out is None:
+                out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
+            s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+            stride = d_src.stride(0) // 2 if nsrc > 1 else max(n_in, need)
+            check(self.lib.rdsp_engine_update_sources(self.h, d_src.data_ptr(), stride, int(n_blocks), out.data_ptr(), n, C.c_void_p(s)))
+            return out
+        assert D >= 1, "a rational source rate is set: pass n_blocks"
         n = n_in // D
         assert two == 2 and n_in == n * D and n % 128 == 0 and d_src.dtype == torch.int16 and d_src.is_contiguous()
         assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
@@ -136,6 +167,24 @@ def ddc_taps(D, gain=1.0):
     o = np.zeros(16 * int(D), np.float32)
     check(load().rdsp_engine_ddc_taps(int(D), float(gain), o.ctypes.data_as(_F32P)))
     return o
+
+
+def rate_taps(P, Q, gain=1.0):
+    """the prototype low-pass of set_source_rate(P, Q, gain): 16 ceil(P / Q) Q float32 taps, P / Q in lowest terms (host only,
+    no GPU); branch r is taps[r::Q]"""
+    import math
+    g = math.gcd(int(P), int(Q)) if int(P) > 0 and int(Q) > 0 else 1
+    p, q = int(P) // g, int(Q) // g
+    o = np.zeros(16 * (-(-p // q)) * q if 0 < q <= 441 and q <= p <= 64 * q else 1, np.float32)
+    check(load().rdsp_engine_rate_taps(int(P), int(Q), float(gain), o.ctypes.data_as(_F32P)))
+    return o
+
+
+def rate_of_hz(fs_hz):
+    """(P, Q) with fs_hz = 44100 P / Q for an integer-Hz rate inside the limits of set_source_rate; RdspError otherwise"""
+    p, q = C.c_int(), C.c_int()
+    check(load().rdsp_engine_rate_of_hz(float(fs_hz), C.byref(p), C.byref(q)))
+    return p.value, q.value
 
 
 def _setter(name):
