@@ -436,6 +436,14 @@ double rdsp_iq_reader_sample_rate(const rdsp_iq_reader_t *r); /* 0: the containe
 int64_t rdsp_iq_reader_frames(const rdsp_iq_reader_t *r);     /* IQ pairs, -1 unknown */
 int rdsp_iq_reader_format(const rdsp_iq_reader_t *r);
 size_t rdsp_iq_reader_read(rdsp_iq_reader_t *r, int16_t *dst, size_t n_pairs);
+/* Recordings in the engine's other source formats (RDSP_SRC_* below): RAW takes the format it is told (.cu8, .cs8, .cf32);
+ * WAV accepts PCM 8-bit stereo as U8, PCM 16-bit as S16 and IEEE float (tag 3, also through the extensible header) 32-bit as
+ * F32, sample_format -1 for "what the header says" (any other value must match the header or the open is refused).  frames
+ * counts pairs in every format; read_samples delivers elements in the file's own format.  rdsp_iq_reader_open / _read keep
+ * their behaviour (int16); _read on a reader that is not S16 returns 0 and sets the error text. */
+int rdsp_iq_reader_open_samples(const char *path, int container, int sample_format, rdsp_iq_reader_t **out);
+int rdsp_iq_reader_sample_format(const rdsp_iq_reader_t *r);
+size_t rdsp_iq_reader_read_samples(rdsp_iq_reader_t *r, void *dst, size_t n_pairs);
 void rdsp_iq_reader_close(rdsp_iq_reader_t *r);
 int rdsp_audio_writer_open(const char *path, int format, double sample_rate, rdsp_audio_writer_t **out);
 size_t rdsp_audio_writer_write(rdsp_audio_writer_t *w, const int16_t *lr, size_t n_pairs);
@@ -824,6 +832,32 @@ int rdsp_engine_source_rate(const rdsp_engine_t *e, int *P, int *Q);
 size_t rdsp_engine_source_pairs(const rdsp_engine_t *e, int n_blocks);
 int rdsp_engine_rate_of_hz(double fs_hz, int *P, int *Q);
 int rdsp_engine_rate_taps(int P, int Q, float gain, float *out /* [16 ceil(P / Q) Q], P / Q in lowest terms */);
+/* Source sample formats: what the source rows of every rate above hold.  One format per engine.
+ *   RDSP_SRC_S16 (default)  int16                          value (float)x
+ *   RDSP_SRC_U8             uint8, offset binary (.cu8)    value (float)(2 u - 255) x 128: exact, +-32 640, symmetric about 127.5
+ *   RDSP_SRC_S8             int8 (.cs8)                    value (float)s x 256: exact
+ *   RDSP_SRC_F32            float, full scale +-1.0 (cf32) NaN -> 0; otherwise clamp(x, -256, 256) x 32768: +-inf and wild values
+ *                                                          stay finite at +-2^23 counts; the output saturates as always
+ *   Pairs are I then Q, interleaved.  The value, in counts on the int16 scale, enters the arithmetic of the three passes where
+ *   the int16 sample does (csrc/rdsp_tune.h, src_value); everything after it is the same, operation for operation.  So an 8-bit
+ *   row gives the bits of the int16 pass on the row widened by the table, and a float row of values k / 32768 the bits of the
+ *   int16 row k.  The passes read the rows in place in their own format: no widened copy, no conversion pass.
+ * - rdsp_engine_set_source_format(e, format), after rdsp_engine_set_sources (RDSP_ERR_NOT_READY before); an unknown format is
+ *   RDSP_ERR_INVALID.  A setting: kept by rdsp_engine_reset, rdsp_engine_set_sources and the rate setters, in no state blob (blob
+ *   sizes are unchanged).  Setting the format the engine has changes nothing; another one begins another stream: the source
+ *   histories and frac go to zero as with a change of rate, the phases stay with their channels.  It takes no stream and
+ *   waits for everything queued on the engine's device.  The histories of the three new formats are kept as float2 VALUES
+ *   (a fresh history is exactly 0 in every format; no uint8 byte has the value 0), those of S16 as the packed words.
+ * - rdsp_engine_update_source_samples is rdsp_engine_update_sources for any format (with S16 the same code path, the same
+ *   bits).  src_stride and rdsp_engine_source_pairs count PAIRS whatever the format.  Alignment in bytes: the integer rates
+ *   need rows 16-byte aligned and src_stride x bytes-per-pair (4 / 2 / 2 / 8) a multiple of 16; a rational rate needs rows
+ *   and stride aligned to one pair.  rdsp_engine_update_sources stays for S16 and is RDSP_ERR_INVALID under another format.
+ *   Every refusal changes nothing in the object. */
+enum { RDSP_SRC_S16 = 0, RDSP_SRC_U8 = 1, RDSP_SRC_S8 = 2, RDSP_SRC_F32 = 3 };
+int rdsp_engine_set_source_format(rdsp_engine_t *e, int format);
+int rdsp_engine_source_format(const rdsp_engine_t *e);
+int rdsp_engine_update_source_samples(rdsp_engine_t *e, const void *d_src, size_t src_stride /* pairs */, int n_blocks,
+                                      int16_t *d_lr, size_t out_stride, void *stream);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -150,6 +150,9 @@ SYMBOLS = [
     ("rdsp_iq_reader_frames", C.c_int64, [_vp]),
     ("rdsp_iq_reader_format", _i, [_vp]),
     ("rdsp_iq_reader_read", _sz, [_vp, _i16p, _sz]),
+    ("rdsp_iq_reader_open_samples", _i, [C.c_char_p, _i, _i, C.POINTER(_vp)]),
+    ("rdsp_iq_reader_sample_format", _i, [_vp]),
+    ("rdsp_iq_reader_read_samples", _sz, [_vp, _vp, _sz]),
     ("rdsp_iq_reader_close", None, [_vp]),
     ("rdsp_audio_writer_open", _i, [C.c_char_p, _i, _d, C.POINTER(_vp)]),
     ("rdsp_audio_writer_write", _sz, [_vp, _i16p, _sz]),
@@ -292,6 +295,9 @@ SYMBOLS = [
     ("rdsp_engine_set_source_rate", _i, [_vp, _i, _i, C.c_float]),
     ("rdsp_engine_source_rate", _i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("rdsp_engine_source_pairs", C.c_size_t, [_vp, _i]),
+    ("rdsp_engine_set_source_format", _i, [_vp, _i]),
+    ("rdsp_engine_source_format", _i, [_vp]),
+    ("rdsp_engine_update_source_samples", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     ("rdsp_engine_rate_of_hz", _i, [_d, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("rdsp_engine_rate_taps", _i, [_i, _i, C.c_float, _f32p]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),

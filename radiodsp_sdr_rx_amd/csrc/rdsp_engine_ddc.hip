@@ -13,7 +13,10 @@
  * 64 O outputs, O = 4, 2 or 1 by D (rdsp_engine_ddc_launch).  It stages the (64 O + 15) D pairs the tile needs in LDS once
  * for all of them, as floats, in polyphase order xs[r][n] = x[(m0 - 15 + n) D + r]: tap k = j D + p of output m0 + 64 o + lane
  * reads xs[D - 1 - p][64 o + lane + 15 - j], consecutive lanes consecutive 8-byte words whatever D is.  The pairs before the
- * call's first sample come from the history buffer.  A lane is O outputs and a wave's DDC_C receivers are a register block
+ * call's first sample come from the history buffer.  The rows are read in the source's own format (a template parameter;
+ * rdsp_tune.h's src_value is the one conversion, int16 pairs load as words, 8-bit pairs as 2-byte and float pairs as 8-byte
+ * elements, coalesced along the source index all the same); the history holds packed words for int16 and float2 values for
+ * the other formats, and the finish kernel writes whichever applies.  A lane is O outputs and a wave's DDC_C receivers are a register block
  * of DDC_C x O accumulator pairs: O ds_read_b64 and DDC_C taps feed 4 DDC_C O fmaf.  The taps are wave-uniform -- the
  * channel index goes through readfirstlane -- so they arrive by scalar loads from g, eight taps a load; with O > 1 the
  * compiler pairs two outputs of one tap into a v_pk_fma_f32, with O = 1 two receivers, which costs scalar moves to pair
@@ -40,7 +43,7 @@ __global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_taps_kernel(DdcPa
   p.g[i] = ddc_tap(p.tab, p.h[k], p.dphi[ch], k);
 }
 
-template <int O> /* outputs per lane: a tile is 64 O outputs */
+template <int F, int O> /* the format of the source rows; outputs per lane: a tile is 64 O outputs */
 __global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_kernel(DdcParams p) {
   constexpr int TILE = 64 * O, ROW = TILE + DDC_HIST_PER_PHASE;
   extern __shared__ float2 xs[]; /* [D][ROW] */
@@ -54,14 +57,13 @@ __global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_kernel(DdcParams 
 
   /* stage: element e of the tile is x[(m0 - 15) D + e]; negative indices are the history's tail */
   {
-    const uint32_t *row = p.src + (size_t)p.source_of[p.order[first]] * p.src_stride;
-    const uint32_t *hist = p.hist + (size_t)p.source_of[p.order[first]] * (size_t)(DDC_HIST_PER_PHASE * D);
+    const int source = p.source_of[p.order[first]], keep = DDC_HIST_PER_PHASE * D;
+    const void *row = src_at<F>(p.src, (size_t)source * p.src_stride);
+    const uint32_t *hist = (const uint32_t *)p.hist + (size_t)source * (size_t)(keep * src_hist_words(F));
     const long long i0 = ((long long)m0 - DDC_HIST_PER_PHASE) * D;
     for (int e = tid; e < ROW * D; e += DDC_THREADS) {
-      const long long i = i0 + e;
-      const uint32_t w = i >= 0 ? row[i] : hist[i + DDC_HIST_PER_PHASE * D];
       const int n = e / D, r = e - n * D;
-      xs[r * ROW + n] = make_float2((float)(int16_t)(uint16_t)(w & 0xffffu), (float)(int16_t)(uint16_t)(w >> 16));
+      xs[r * ROW + n] = src_or_hist<F>(row, hist, i0 + e, keep);
     }
   }
   __syncthreads();
@@ -109,21 +111,33 @@ __global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_kernel(DdcParams 
   }
 }
 
+template <int F>
 __global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_finish_kernel(DdcParams p) {
   const uint32_t keep = (uint32_t)(DDC_HIST_PER_PHASE * p.D), n_in = p.n_out * (uint32_t)p.D; /* n_in >= 128 D > keep */
   const uint32_t i = blockIdx.x * DDC_THREADS + threadIdx.x;
   if (i < (uint32_t)p.n_sources * keep) {
     const uint32_t s = i / keep, t = i - s * keep;
-    p.hist[i] = p.src[(size_t)s * p.src_stride + (n_in - keep) + t];
+    const void *row = src_at<F>(p.src, (size_t)s * p.src_stride);
+    if constexpr (F == SRC_S16) ((uint32_t *)p.hist)[i] = ((const uint32_t *)row)[(n_in - keep) + t];
+    else ((float2 *)p.hist)[i] = src_pair<F>(row, (long long)(n_in - keep) + t);
   }
   if (i < (uint32_t)p.n_channels) p.phase[i] = tune_phase(p.phase[i], (uint32_t)p.D * p.dphi[i], p.n_out);
 }
 
 constexpr size_t DDC_LDS_BUDGET = 163840 / 3;
 size_t ddc_lds_bytes(int D, int O) { return (size_t)D * (size_t)(64 * O + DDC_HIST_PER_PHASE) * sizeof(float2); } /* at most 40 448 at O = 1 */
+
+template <int F>
+void ddc_launch(const DdcParams &p, int O, size_t grid, size_t lds, size_t n_fin, hipStream_t s) {
+  if (O == 4) hipLaunchKernelGGL((rdsp_engine_ddc_kernel<F, 4>), dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
+  else if (O == 2) hipLaunchKernelGGL((rdsp_engine_ddc_kernel<F, 2>), dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
+  else hipLaunchKernelGGL((rdsp_engine_ddc_kernel<F, 1>), dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
+  hipLaunchKernelGGL(rdsp_engine_ddc_finish_kernel<F>, dim3((unsigned)((n_fin + DDC_THREADS - 1) / DDC_THREADS)), dim3(DDC_THREADS), 0, s, p);
+}
 }  // namespace
 
 hipError_t rdsp_engine_ddc_launch(const DdcParams &p, hipStream_t s) {
+  if (p.format < 0 || p.format >= SRC_FORMATS) return hipErrorInvalidValue;
   const size_t T = (size_t)(DDC_TAPS_PER_PHASE * p.D);
   const size_t n_g = (size_t)p.n_channels * T;
   hipLaunchKernelGGL(rdsp_engine_ddc_taps_kernel, dim3((unsigned)((n_g + DDC_THREADS - 1) / DDC_THREADS)), dim3(DDC_THREADS), 0, s, p);
@@ -134,10 +148,12 @@ hipError_t rdsp_engine_ddc_launch(const DdcParams &p, hipStream_t s) {
   const size_t lds = ddc_lds_bytes(p.D, O);
   const size_t grid = (size_t)p.n_wg * (p.n_out / (64u * O));
   if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  if (O == 4) hipLaunchKernelGGL(rdsp_engine_ddc_kernel<4>, dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
-  else if (O == 2) hipLaunchKernelGGL(rdsp_engine_ddc_kernel<2>, dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
-  else hipLaunchKernelGGL(rdsp_engine_ddc_kernel<1>, dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
   const size_t n_fin = std::max((size_t)p.n_sources * (size_t)(DDC_HIST_PER_PHASE * p.D), (size_t)p.n_channels);
-  hipLaunchKernelGGL(rdsp_engine_ddc_finish_kernel, dim3((unsigned)((n_fin + DDC_THREADS - 1) / DDC_THREADS)), dim3(DDC_THREADS), 0, s, p);
+  switch (p.format) {
+    case SRC_S16: ddc_launch<SRC_S16>(p, O, grid, lds, n_fin, s); break;
+    case SRC_U8: ddc_launch<SRC_U8>(p, O, grid, lds, n_fin, s); break;
+    case SRC_S8: ddc_launch<SRC_S8>(p, O, grid, lds, n_fin, s); break;
+    default: ddc_launch<SRC_F32>(p, O, grid, lds, n_fin, s); break;
+  }
   return hipGetLastError();
 }

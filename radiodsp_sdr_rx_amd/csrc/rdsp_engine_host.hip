@@ -37,7 +37,7 @@ struct EngSources {
   rdsp_dev::Event dphi_ev; /* the last upload of dphi has left dphi_stage */
 };
 /* sources at D > 1: the prototype's taps, every receiver's translated taps, and per SOURCE the last 15 D pairs */
-struct EngDdc { DevBuf<float> h; DevBuf<float2> g; DevBuf<uint32_t> hist; };
+struct EngDdc { DevBuf<float> h; DevBuf<float2> g; DevBuf<uint32_t> hist; }; /* hist: src_hist_words(format) words a pair */
 /* sources at 44 100 P / Q Hz, Q > 1: the prototype by branches hb[r][j], per SOURCE the last Tb pairs, the call's schedule */
 struct EngRate { DevBuf<float> hb; DevBuf<uint32_t> hist; DevBuf<rdsp_tune::RateStep> sched; };
 struct rdsp_engine {
@@ -67,6 +67,8 @@ struct rdsp_engine {
   int rate_P = 1, rate_Q = 1, n_rate_wg = 0;
   uint32_t frac = 0; /* (outputs since the last reset x rate_P) mod rate_Q */
   std::unique_ptr<EngRate> rate;
+  /* the format of the source rows (rdsp_engine_set_source_format): a setting; the histories hold words for S16, float2 values otherwise */
+  int src_format = rdsp_tune::SRC_S16;
 };
 
 namespace {
@@ -81,14 +83,16 @@ void engine_sam_constants(rdsp_engine_t *e) { /* 0xed34 with the constructor's l
 }
 /* what the arguments of the tuning and the decimating pass share (rdsp_engine_update_sources) */
 template <typename P>
-P source_pass(const rdsp_engine_t *e, const int16_t *d_src, size_t src_stride) {
+P source_pass(const rdsp_engine_t *e, const void *d_src, size_t src_stride) {
   P p;
-  p.src = (const uint32_t *)d_src; p.src_stride = src_stride;
+  p.src = d_src; p.src_stride = src_stride; p.format = e->src_format;
   p.dst = e->src->tuned; p.dst_stride = (size_t)e->max_blocks * BS;
   p.order = e->src->order; p.source_of = e->src->source_of;
   p.phase = e->src->phase; p.dphi = e->src->dphi; p.tab = e->src->tune_tab; p.n_channels = e->n_channels;
   return p;
 }
+/* words of the source histories: keep pairs of every source, in the engine's format */
+size_t hist_words(const rdsp_engine_t *e, size_t keep) { return (size_t)e->n_sources * keep * (size_t)rdsp_tune::src_hist_words(e->src_format); }
 /* |station| must stay below it: half the source rate */
 double source_band_hz(const rdsp_engine_t *e) {
   return e->rate ? (rdsp_tune::TUNE_MAX_HZ * (double)e->rate_P) / (double)e->rate_Q : (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ;
@@ -283,8 +287,8 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
     err = fill[k].empty() ? hipMemsetAsync(e->plane[k], 0, n * e->plane_words[k] * 4, s)
                           : hipMemcpyAsync(e->plane[k], fill[k].data(), fill[k].size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess && e->src) err = hipMemsetAsync(e->src->phase, 0, n * 4, s); /* the stations are settings: kept */
-  if (err == hipSuccess && e->ddc) err = hipMemsetAsync(e->ddc->hist, 0, (size_t)e->n_sources * rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D * 4, s);
-  if (err == hipSuccess && e->rate) err = hipMemsetAsync(e->rate->hist, 0, (size_t)e->n_sources * (size_t)rdsp_tune::rate_tb(e->rate_P, e->rate_Q) * 4, s);
+  if (err == hipSuccess && e->ddc) err = hipMemsetAsync(e->ddc->hist, 0, hist_words(e, (size_t)rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D) * 4, s);
+  if (err == hipSuccess && e->rate) err = hipMemsetAsync(e->rate->hist, 0, hist_words(e, (size_t)rdsp_tune::rate_tb(e->rate_P, e->rate_Q)) * 4, s);
   e->frac = 0;
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
@@ -433,7 +437,7 @@ hipError_t ddc_setup(rdsp_engine_t *e, int D, float gain, int n_sources) {
     e->ddc_D = 1; /* until everything below exists */
     e->n_sources = n_sources;
     if (D > 1) {
-      const size_t T = (size_t)rdsp_tune::DDC_TAPS_PER_PHASE * D, keep = (size_t)n_sources * rdsp_tune::DDC_HIST_PER_PHASE * D;
+      const size_t T = (size_t)rdsp_tune::DDC_TAPS_PER_PHASE * D, keep = hist_words(e, (size_t)rdsp_tune::DDC_HIST_PER_PHASE * D);
       auto d = std::make_unique<EngDdc>();
       err = d->h.alloc(T);
       if (err == hipSuccess) err = d->g.alloc((size_t)e->n_channels * T);
@@ -457,7 +461,7 @@ hipError_t ddc_setup(rdsp_engine_t *e, int D, float gain, int n_sources) {
 /* the device side of a rate P / Q (lowest terms, Q > 1) on n_sources rows: histories and schedule are new (zero) when the
  * rate or the number of rows changed, the taps always.  The caller has waited for queued work. */
 hipError_t rate_setup(rdsp_engine_t *e, int P, int Q, float gain, int n_sources) {
-  const size_t Tb = (size_t)rdsp_tune::rate_tb(P, Q), keep = (size_t)n_sources * Tb;
+  const size_t Tb = (size_t)rdsp_tune::rate_tb(P, Q), keep = (size_t)n_sources * Tb * (size_t)rdsp_tune::src_hist_words(e->src_format);
   std::vector<float> h(Tb * (size_t)Q), hb(Tb * (size_t)Q);
   rdsp_tune::rate_taps(P, Q, (double)gain, h.data());
   for (size_t r = 0; r < (size_t)Q; r++)
@@ -671,33 +675,67 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
   return RDSP_OK;
 }
 
-int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
-  if (e && e->rate) { /* a rational rate: rows of rdsp_engine_source_pairs pairs, int16-pair aligned */
-    if (!d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < rdsp_engine_source_pairs(e, n_blocks) || ((uintptr_t)d_src & 3) != 0 ||
-        out_stride < (size_t)n_blocks * BS) {
-      rdsp_set_error("rdsp_engine_update_sources: bad argument (n_blocks %d of at most %d; source rows 4-byte aligned and at least "
-                     "rdsp_engine_source_pairs = %zu pairs long at 44100 x %d / %d Hz)", n_blocks, e->max_blocks, rdsp_engine_source_pairs(e, std::max(n_blocks, 0)), e->rate_P, e->rate_Q);
-      return RDSP_ERR_INVALID;
-    }
-  } else if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS * (size_t)e->ddc_D || src_stride % 4 != 0 ||
-      ((uintptr_t)d_src & 15) != 0 || out_stride < (size_t)n_blocks * BS) {
-    rdsp_set_error("rdsp_engine_update_sources: bad argument (n_blocks %d of at most %d; source rows 16-byte aligned, a multiple of 4 "
-                   "pairs apart and at least n_blocks * 128 * D long, D = %d)", n_blocks, e ? e->max_blocks : 0, e ? e->ddc_D : 0);
+/* The format of the source rows.  A setting: kept by reset, set_sources and the rate setters, in no blob.  Another format
+ * begins another stream: the source histories (reallocated: words for S16, float2 values otherwise) and frac go to zero as
+ * with a change of rate; the phases stay with their channels. */
+int rdsp_engine_set_source_format(rdsp_engine_t *e, int format) {
+  if (!e || format < 0 || format >= rdsp_tune::SRC_FORMATS) {
+    rdsp_set_error("rdsp_engine_set_source_format: bad argument (format %d of RDSP_SRC_S16 = 0, U8 = 1, S8 = 2, F32 = 3)", format);
     return RDSP_ERR_INVALID;
   }
   if (!e->src) {
-    rdsp_set_error("rdsp_engine_update_sources: no sources; call rdsp_engine_set_sources first");
+    rdsp_set_error("rdsp_engine_set_source_format: no sources; call rdsp_engine_set_sources first");
+    return RDSP_ERR_NOT_READY;
+  }
+  if (format == e->src_format) return RDSP_OK;
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = hipDeviceSynchronize(); /* queued passes read the histories */
+  DevBuf<uint32_t> *hist = e->rate ? &e->rate->hist : e->ddc ? &e->ddc->hist : nullptr;
+  DevBuf<uint32_t> fresh; /* the object keeps its format unless the new histories exist */
+  if (err == hipSuccess && hist) {
+    const size_t keep = e->rate ? (size_t)rdsp_tune::rate_tb(e->rate_P, e->rate_Q) : (size_t)rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D;
+    const size_t words = (size_t)e->n_sources * keep * (size_t)rdsp_tune::src_hist_words(format);
+    err = fresh.alloc(words);
+    if (err == hipSuccess) err = hipMemset(fresh, 0, words * 4);
+  }
+  if (err != hipSuccess) return engine_fail("rdsp_engine_set_source_format", err);
+  if (hist) std::swap(hist->p, fresh.p);
+  e->src_format = format;
+  e->frac = 0;
+  return RDSP_OK;
+}
+int rdsp_engine_source_format(const rdsp_engine_t *e) { return e ? e->src_format : RDSP_ERR_INVALID; }
+
+namespace {
+/* both entry points; who: the one that was called, for the error text */
+int update_source_rows(const char *who, rdsp_engine_t *e, const void *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
+  const size_t pair = e ? (size_t)rdsp_tune::src_pair_bytes(e->src_format) : 4;
+  if (e && e->rate) { /* a rational rate: rows of rdsp_engine_source_pairs pairs, aligned to a pair */
+    if (!d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < rdsp_engine_source_pairs(e, n_blocks) || (uintptr_t)d_src % pair != 0 ||
+        out_stride < (size_t)n_blocks * BS) {
+      rdsp_set_error("%s: bad argument (n_blocks %d of at most %d; source rows %zu-byte aligned and at least "
+                     "rdsp_engine_source_pairs = %zu pairs long at 44100 x %d / %d Hz)", who, n_blocks, e->max_blocks, pair, rdsp_engine_source_pairs(e, std::max(n_blocks, 0)), e->rate_P, e->rate_Q);
+      return RDSP_ERR_INVALID;
+    }
+  } else if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS * (size_t)e->ddc_D || (src_stride * pair) % 16 != 0 ||
+      ((uintptr_t)d_src & 15) != 0 || out_stride < (size_t)n_blocks * BS) {
+    rdsp_set_error("%s: bad argument (n_blocks %d of at most %d; source rows 16-byte aligned, a multiple of 16 "
+                   "bytes apart and at least n_blocks * 128 * D pairs long, D = %d)", who, n_blocks, e ? e->max_blocks : 0, e ? e->ddc_D : 0);
+    return RDSP_ERR_INVALID;
+  }
+  if (!e->src) {
+    rdsp_set_error("%s: no sources; call rdsp_engine_set_sources first", who);
     return RDSP_ERR_NOT_READY;
   }
   if (!e->tables) {
-    rdsp_set_error("rdsp_engine_update_sources: the engine's coefficient tables are not loaded (rdsp_engine_load_tables)");
+    rdsp_set_error("%s: the engine's coefficient tables are not loaded (rdsp_engine_load_tables)", who);
     return RDSP_ERR_NOT_READY;
   }
   if (n_blocks == 0) return RDSP_OK;
   hipStream_t s = (hipStream_t)stream;
   hipError_t err = hipSetDevice(e->device);
   if (err == hipSuccess) err = upload_dphi(e, s);
-  if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources", err);
+  if (err != hipSuccess) return engine_fail(who, err);
   if (e->rate) { /* tune, low-pass and resample by Q / P: rdsp_engine_rate.hip */
     auto q = source_pass<rdsp_tune::RateParams>(e, d_src, src_stride);
     q.hist = e->rate->hist; q.hb = e->rate->hb; q.sched = e->rate->sched; q.wg_first = e->src->rate_wg_first; q.wg_count = e->src->rate_wg_count;
@@ -716,8 +754,22 @@ int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t sr
     p.n_samples = (uint32_t)n_blocks * BS;
     err = rdsp_engine_tune_launch(p, s);
   }
-  if (err != hipSuccess) return engine_fail("rdsp_engine_update_sources launch", err);
+  if (err != hipSuccess) return engine_fail(who, err);
   return rdsp_engine_update(e, (const int16_t *)e->src->tuned.p, (size_t)e->max_blocks * BS, n_blocks, d_lr, out_stride, stream);
+}
+
+}  // namespace
+
+int rdsp_engine_update_source_samples(rdsp_engine_t *e, const void *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
+  return update_source_rows("rdsp_engine_update_source_samples", e, d_src, src_stride, n_blocks, d_lr, out_stride, stream);
+}
+
+int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
+  if (e && e->src_format != rdsp_tune::SRC_S16) {
+    rdsp_set_error("rdsp_engine_update_sources: the engine's source format is %d, not int16; call rdsp_engine_update_source_samples", e->src_format);
+    return RDSP_ERR_INVALID;
+  }
+  return update_source_rows("rdsp_engine_update_sources", e, d_src, src_stride, n_blocks, d_lr, out_stride, stream);
 }
 
 /* ---- the signal state of a channel range as data: resume, or move receivers between objects / GPUs ---------------------

@@ -16,7 +16,8 @@
  * receivers of ONE source that are neighbours in `order` and a tile of 32 outputs: wave w has the receivers of half w & 1
  * and the 16 outputs of half w >> 1, 2 x 16 accumulator pairs a lane.  The taps go through LDS RATE_CHUNK = 128 at a time
  * (so its use does not grow with Dc: 34 816 bytes of products and the 16 384-byte phasor table, three workgroups a CU):
- * all threads stage the chunk's products as floats, us[j][half][I / Q][16], coalesced along j in global memory, rows 68
+ * all threads stage the chunk's products as floats (the rows are read in the source's own format, a template parameter:
+ * rdsp_tune.h's src_value; the history holds words for int16, float2 values otherwise), us[j][half][I / Q][16], coalesced along j in global memory, rows 68
  * words apart so that the writes of consecutive j spread over the banks; then per tap a wave reads its 32 floats by eight
  * 16-byte reads at ONE address for all lanes (a broadcast, no bank conflicts), each lane looks up its two receivers' phasors
  * at 0 - j dphi in the table in LDS (tune_phasor), and 128 fmaf follow.  The accumulators stay in registers through the
@@ -42,6 +43,7 @@ __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_sched_kernel(Ra
   if (i < p.n_out) p.sched[i] = rate_step(p.frac, p.P, p.Q, i);
 }
 
+template <int F> /* the format of the source rows (rdsp_tune.h, src_value) */
 __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_kernel(RateParams p) {
   __shared__ float4 tabs[TUNE_N];
   __shared__ __attribute__((aligned(16))) float us[RATE_CHUNK * RATE_PITCH];
@@ -55,8 +57,8 @@ __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_kernel(RatePara
   const int first = p.wg_first[wg], count = p.wg_count[wg];
   const uint32_t i0 = tile * RATE_TILE;
   const int source = p.source_of[p.order[first]];
-  const uint32_t *row = p.src + (size_t)source * p.src_stride;
-  const uint32_t *hist = p.hist + (size_t)source * (size_t)Tb;
+  const void *row = src_at<F>(p.src, (size_t)source * p.src_stride);
+  const uint32_t *hist = (const uint32_t *)p.hist + (size_t)source * (size_t)(Tb * src_hist_words(F));
 
   for (int k = tid; k < TUNE_N; k += RATE_THREADS) tabs[k] = p.tab[k];
   if (tid < RATE_TILE) steps[tid] = p.sched[i0 + tid];
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_kernel(RatePara
       const int o = e / len, jj = e - o * len, j = j0 + jj;
       const RateStep s = steps[o];
       const int at = s.n - j; /* >= -(Tb - 1) */
-      const float2 u = rate_u(p.hb[(size_t)s.r * (size_t)Tb + (size_t)j], at >= 0 ? row[at] : hist[at + Tb]);
+      const float2 u = rate_u(p.hb[(size_t)s.r * (size_t)Tb + (size_t)j], src_or_hist<F>(row, hist, at, Tb));
       float *d = us + jj * RATE_PITCH + (o / RATE_O) * (2 * RATE_O) + (o % RATE_O);
       d[0] = u.x;
       d[RATE_O] = u.y;
@@ -133,25 +135,39 @@ __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_kernel(RatePara
   }
 }
 
+template <int F>
 __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_finish_kernel(RateParams p) {
   const uint32_t keep = (uint32_t)rate_tb(p.P, p.Q); /* pairs >= 128 P / Q - 1 > 16 Dc: the row alone holds them */
   const uint32_t i = blockIdx.x * RATE_THREADS + threadIdx.x;
   if (i < (uint32_t)p.n_sources * keep) {
     const uint32_t s = i / keep, t = i - s * keep;
-    p.hist[i] = p.src[(size_t)s * p.src_stride + (p.pairs - keep) + t];
+    const void *row = src_at<F>(p.src, (size_t)s * p.src_stride);
+    if constexpr (F == SRC_S16) ((uint32_t *)p.hist)[i] = ((const uint32_t *)row)[(p.pairs - keep) + t];
+    else ((float2 *)p.hist)[i] = src_pair<F>(row, (long long)(p.pairs - keep) + t);
   }
   if (i < (uint32_t)p.n_channels) p.phase[i] = tune_phase(p.phase[i], p.dphi[i], p.pairs);
+}
+
+template <int F>
+void rate_launch(const RateParams &p, size_t grid, size_t n_fin, hipStream_t s) {
+  hipLaunchKernelGGL(rdsp_engine_rate_kernel<F>, dim3((unsigned)grid), dim3(RATE_THREADS), 0, s, p);
+  hipLaunchKernelGGL(rdsp_engine_rate_finish_kernel<F>, dim3((unsigned)((n_fin + RATE_THREADS - 1) / RATE_THREADS)), dim3(RATE_THREADS), 0, s, p);
 }
 }  // namespace
 
 hipError_t rdsp_engine_rate_launch(const RateParams &p, hipStream_t s) {
   /* the bank's vector stores: 16 outputs of a receiver are 64 bytes, whole in its row */
   if (p.n_out % RATE_TILE != 0 || p.dst_stride % 4 != 0 || ((uintptr_t)p.dst & 15) != 0 || p.pairs < (uint32_t)rate_tb(p.P, p.Q)) return hipErrorInvalidValue;
+  if (p.format < 0 || p.format >= SRC_FORMATS) return hipErrorInvalidValue;
   const size_t grid = (size_t)p.n_wg * (p.n_out / RATE_TILE);
   if (grid > 0x7fffffffull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rdsp_engine_rate_sched_kernel, dim3((p.n_out + RATE_THREADS - 1) / RATE_THREADS), dim3(RATE_THREADS), 0, s, p);
-  hipLaunchKernelGGL(rdsp_engine_rate_kernel, dim3((unsigned)grid), dim3(RATE_THREADS), 0, s, p);
   const size_t n_fin = std::max((size_t)p.n_sources * (size_t)rate_tb(p.P, p.Q), (size_t)p.n_channels);
-  hipLaunchKernelGGL(rdsp_engine_rate_finish_kernel, dim3((unsigned)((n_fin + RATE_THREADS - 1) / RATE_THREADS)), dim3(RATE_THREADS), 0, s, p);
+  switch (p.format) {
+    case SRC_S16: rate_launch<SRC_S16>(p, grid, n_fin, s); break;
+    case SRC_U8: rate_launch<SRC_U8>(p, grid, n_fin, s); break;
+    case SRC_S8: rate_launch<SRC_S8>(p, grid, n_fin, s); break;
+    default: rate_launch<SRC_F32>(p, grid, n_fin, s); break;
+  }
   return hipGetLastError();
 }

@@ -5,7 +5,8 @@
  *
  * A workgroup takes cpw receivers that are neighbours in `order` (receivers sorted by source, so a source row is read by
  * workgroups dispatched together and comes from the caches, not HBM), reads their phases and steps into LDS with the
- * phasor table, and streams each row in 16-byte words: four pairs a lane, phases in closed form ph0 + t dphi.  The phase
+ * phasor table, and streams each row in 16-byte words: four int16 pairs a lane (eight of 8-bit, two of float: the format of the
+ * source rows is a template parameter, rdsp_tune.h's src_value the one conversion), phases in closed form ph0 + t dphi.  The phase
  * words are read before the one barrier and written after the last row, by the lanes that read them.
  *
  * Compiled with -ffp-contract=off: every fused operation is an fmaf.
@@ -18,10 +19,12 @@ using namespace rdsp_tune;
 
 namespace {
 
+template <int F> /* the format of the source rows (rdsp_tune.h, src_value) */
 __global__ __launch_bounds__(TUNE_THREADS) void rdsp_engine_tune_kernel(TuneParams p) {
   __shared__ float4 tab[TUNE_N];
   __shared__ int ch_of[TUNE_MAX_CPW], src_of[TUNE_MAX_CPW];
   __shared__ uint32_t ph0_of[TUNE_MAX_CPW], dphi_of[TUNE_MAX_CPW];
+  constexpr uint32_t NP = 16 / (F == SRC_F32 ? 8 : F == SRC_S16 ? 4 : 2); /* pairs in a lane's 16 bytes */
   const int tid = threadIdx.x;
   for (int k = tid; k < TUNE_N; k += TUNE_THREADS) tab[k] = p.tab[k];
   const int i0 = blockIdx.x * p.cpw;
@@ -35,20 +38,37 @@ __global__ __launch_bounds__(TUNE_THREADS) void rdsp_engine_tune_kernel(TunePara
   for (int k = 0; k < p.cpw; k++) {
     const int ch = ch_of[k];
     if (ch < 0) break;
-    const uint4 *in = (const uint4 *)(p.src + (size_t)src_of[k] * p.src_stride);
-    uint4 *out = (uint4 *)(p.dst + (size_t)ch * p.dst_stride);
+    const uint4 *in = (const uint4 *)src_at<F>(p.src, (size_t)src_of[k] * p.src_stride);
+    uint32_t *out = p.dst + (size_t)ch * p.dst_stride;
     const uint32_t ph0 = ph0_of[k], dphi = dphi_of[k];
-    const uint32_t n4 = p.n_samples >> 2;
+    const uint32_t nv = p.n_samples / NP;
 #pragma unroll 2
-    for (uint32_t v = (uint32_t)tid; v < n4; v += TUNE_THREADS) {
+    for (uint32_t v = (uint32_t)tid; v < nv; v += TUNE_THREADS) {
       const uint4 w = in[v];
-      const uint32_t ph = tune_phase(ph0, dphi, 4u * v);
-      uint4 r;
-      r.x = tune_pair(w.x, tune_phasor(tab, ph));
-      r.y = tune_pair(w.y, tune_phasor(tab, ph + dphi));
-      r.z = tune_pair(w.z, tune_phasor(tab, ph + 2u * dphi));
-      r.w = tune_pair(w.w, tune_phasor(tab, ph + 3u * dphi));
-      out[v] = r;
+      const uint32_t ph = tune_phase(ph0, dphi, NP * v);
+      if constexpr (F == SRC_S16) {
+        uint4 r;
+        r.x = tune_pair(w.x, tune_phasor(tab, ph));
+        r.y = tune_pair(w.y, tune_phasor(tab, ph + dphi));
+        r.z = tune_pair(w.z, tune_phasor(tab, ph + 2u * dphi));
+        r.w = tune_pair(w.w, tune_phasor(tab, ph + 3u * dphi));
+        ((uint4 *)out)[v] = r;
+      } else if constexpr (F == SRC_F32) { /* two pairs: an 8-byte store */
+        uint2 r;
+        r.x = tune_pair(make_float2(src_value(F, w.x), src_value(F, w.y)), tune_phasor(tab, ph));
+        r.y = tune_pair(make_float2(src_value(F, w.z), src_value(F, w.w)), tune_phasor(tab, ph + dphi));
+        ((uint2 *)out)[v] = r;
+      } else { /* eight pairs, two a word: two 16-byte stores */
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+        uint32_t r[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) {
+          const uint32_t b = ws[j >> 1] >> (16u * (j & 1u));
+          r[j] = tune_pair(make_float2(src_value(F, b & 0xffu), src_value(F, (b >> 8) & 0xffu)), tune_phasor(tab, ph + j * dphi));
+        }
+        ((uint4 *)out)[2u * v] = make_uint4(r[0], r[1], r[2], r[3]);
+        ((uint4 *)out)[2u * v + 1u] = make_uint4(r[4], r[5], r[6], r[7]);
+      }
     }
   }
   if (tid < p.cpw && ch_of[tid] >= 0) p.phase[ch_of[tid]] = tune_phase(ph0_of[tid], dphi_of[tid], p.n_samples);
@@ -58,6 +78,12 @@ __global__ __launch_bounds__(TUNE_THREADS) void rdsp_engine_tune_kernel(TunePara
 
 hipError_t rdsp_engine_tune_launch(const TuneParams &p, hipStream_t s) {
   const unsigned grid = (unsigned)((p.n_channels + p.cpw - 1) / p.cpw);
-  hipLaunchKernelGGL(rdsp_engine_tune_kernel, dim3(grid), dim3(TUNE_THREADS), 0, s, p);
+  switch (p.format) {
+    case SRC_S16: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_S16>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
+    case SRC_U8: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_U8>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
+    case SRC_S8: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_S8>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
+    case SRC_F32: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_F32>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }

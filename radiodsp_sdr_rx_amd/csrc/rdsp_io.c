@@ -9,6 +9,8 @@
  *   WAV  RIFF/WAVE, PCM (format tag 1 or WAVE_FORMAT_EXTENSIBLE with the PCM
  *        sub-format), 16 bit, 2 channels: left = I, right = Q -- the wiring of
  *        the sketch, codec left/right -> IQinput ports 0/1 (.ino:71-72)
+ * rdsp_iq_reader_open_samples also opens the engine's other source formats (RDSP_SRC_*): RAW uint8 (.cu8), int8 (.cs8) and
+ * float32 (.cf32) pairs as told, WAV PCM 8-bit stereo as U8 and IEEE float 32-bit stereo as F32.
  * Audio out: int16 L,R pairs (what Q_out_L / Q_out_R carry to audio_out,
  * RDSP_convolutional.h:344-349), RAW or WAV at the decimated rate.
  */
@@ -26,6 +28,7 @@ struct rdsp_iq_reader {
   int64_t frames;      /* IQ pairs in the data chunk, -1 unknown */
   int64_t pos;         /* pairs delivered so far */
   int owns;            /* close f on close */
+  int sample_format;   /* RDSP_SRC_*: what the file's elements are */
 };
 
 struct rdsp_audio_writer {
@@ -44,13 +47,16 @@ static void put32(unsigned char *p, uint32_t v) {
 }
 static void put16(unsigned char *p, uint16_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); }
 
+static size_t pair_bytes(int sample_format) { return sample_format == RDSP_SRC_F32 ? 8u : sample_format == RDSP_SRC_S16 ? 4u : 2u; }
+
 static int host_is_little_endian(void) {
   const uint16_t one = 1;
   return *(const unsigned char *)&one == 1;
 }
 
-/* walk the RIFF chunks up to "data"; leaves the file positioned on the samples */
-static int parse_wav(rdsp_iq_reader_t *r) {
+/* walk the RIFF chunks up to "data"; leaves the file positioned on the samples.  want: the sample format the header must
+ * state, -1 for whichever of the supported ones it states */
+static int parse_wav(rdsp_iq_reader_t *r, int want) {
   unsigned char h[12];
   if (fread(h, 1, 12, r->f) != 12 || memcmp(h, "RIFF", 4) != 0 || memcmp(h + 8, "WAVE", 4) != 0) {
     rdsp_set_error("not a RIFF/WAVE file");
@@ -74,10 +80,14 @@ static int parse_wav(rdsp_iq_reader_t *r) {
       uint16_t tag = le16(f);
       const uint16_t nch = le16(f + 2), bits = le16(f + 14);
       if (tag == 0xFFFE && take >= 26) tag = le16(f + 24); /* extensible: sub-format GUID starts with the tag */
-      if (tag != 1 || nch != 2 || bits != 16) {
-        rdsp_set_error("WAV: need PCM 16-bit stereo (I left, Q right); got tag %u, %u channels, %u bits", tag, nch, bits);
+      const int fmt = (tag == 1 && bits == 16) ? RDSP_SRC_S16 : (tag == 1 && bits == 8) ? RDSP_SRC_U8 : (tag == 3 && bits == 32) ? RDSP_SRC_F32 : -1;
+      if (nch != 2 || fmt < 0 || (want >= 0 && fmt != want)) {
+        if (want == RDSP_SRC_S16) rdsp_set_error("WAV: need PCM 16-bit stereo (I left, Q right); got tag %u, %u channels, %u bits", tag, nch, bits);
+        else rdsp_set_error("WAV: need stereo (I left, Q right) PCM 8- or 16-bit or IEEE float 32-bit%s; got tag %u, %u channels, %u bits",
+                            want >= 0 ? ", as the sample format asked for" : "", tag, nch, bits);
         return RDSP_ERR_UNSUPPORTED;
       }
+      r->sample_format = fmt;
       r->sample_rate = (double)le32(f + 4);
       have_fmt = 1;
       const long rest = (long)(size - take) + (long)(size & 1u);
@@ -88,7 +98,7 @@ static int parse_wav(rdsp_iq_reader_t *r) {
         return RDSP_ERR_INVALID;
       }
       /* 0 and 0xFFFFFFFF are what recorders leave in streams they never finalised */
-      r->frames = (size == 0u || size == 0xFFFFFFFFu) ? -1 : (int64_t)(size / 4u);
+      r->frames = (size == 0u || size == 0xFFFFFFFFu) ? -1 : (int64_t)(size / (uint32_t)pair_bytes(r->sample_format));
       return RDSP_OK;
     } else {
       if (fseek(r->f, (long)size + (long)(size & 1u), SEEK_CUR) != 0) {
@@ -99,9 +109,11 @@ static int parse_wav(rdsp_iq_reader_t *r) {
   }
 }
 
-int rdsp_iq_reader_open(const char *path, int format, rdsp_iq_reader_t **out) {
-  if (!path || !out || format < RDSP_IO_AUTO || format > RDSP_IO_WAV) {
-    rdsp_set_error("rdsp_iq_reader_open: bad argument");
+/* sample_format: RDSP_SRC_*, or -1 for what a WAV header says (RAW then is int16) */
+int rdsp_iq_reader_open_samples(const char *path, int format, int sample_format, rdsp_iq_reader_t **out) {
+  if (!path || !out || format < RDSP_IO_AUTO || format > RDSP_IO_WAV || sample_format < -1 || sample_format > RDSP_SRC_F32) {
+    rdsp_set_error("rdsp_iq_reader_open / rdsp_iq_reader_open_samples: bad argument (container %d of RDSP_IO_AUTO .. RDSP_IO_WAV, sample format %d of -1 .. RDSP_SRC_F32)",
+                   format, sample_format);
     return RDSP_ERR_INVALID;
   }
   if (!host_is_little_endian()) {
@@ -125,29 +137,45 @@ int rdsp_iq_reader_open(const char *path, int format, rdsp_iq_reader_t **out) {
     format = (got == 4 && memcmp(m, "RIFF", 4) == 0) ? RDSP_IO_WAV : RDSP_IO_RAW;
   }
   r->format = format;
+  r->sample_format = sample_format < 0 ? RDSP_SRC_S16 : sample_format;
   if (format == RDSP_IO_WAV) {
-    const int rc = parse_wav(r);
+    const int rc = parse_wav(r, sample_format);
     if (rc != RDSP_OK) { fclose(f); free(r); return rc; }
   } else if (fseek(f, 0, SEEK_END) == 0) {
     const long bytes = ftell(f);
     rewind(f);
-    if (bytes >= 0) r->frames = (int64_t)(bytes / 4);
+    if (bytes >= 0) r->frames = (int64_t)((size_t)bytes / pair_bytes(r->sample_format));
   }
   *out = r;
   return RDSP_OK;
 }
 
+int rdsp_iq_reader_open(const char *path, int format, rdsp_iq_reader_t **out) {
+  return rdsp_iq_reader_open_samples(path, format, RDSP_SRC_S16, out);
+}
+
 double rdsp_iq_reader_sample_rate(const rdsp_iq_reader_t *r) { return r ? r->sample_rate : 0.0; }
 int64_t rdsp_iq_reader_frames(const rdsp_iq_reader_t *r) { return r ? r->frames : -1; }
 int rdsp_iq_reader_format(const rdsp_iq_reader_t *r) { return r ? r->format : 0; }
+int rdsp_iq_reader_sample_format(const rdsp_iq_reader_t *r) { return r ? r->sample_format : RDSP_ERR_INVALID; }
+
+/* up to n pairs of the file's own elements into dst; returns the pairs delivered (short only at the end) */
+size_t rdsp_iq_reader_read_samples(rdsp_iq_reader_t *r, void *dst, size_t n) {
+  if (!r || !dst) return 0;
+  if (r->frames >= 0 && (int64_t)n > r->frames - r->pos) n = (size_t)(r->frames - r->pos);
+  const size_t got = fread(dst, pair_bytes(r->sample_format), n, r->f);
+  r->pos += (int64_t)got;
+  return got;
+}
 
 /* up to n IQ pairs into dst[2*n]; returns the pairs delivered (short only at the end) */
 size_t rdsp_iq_reader_read(rdsp_iq_reader_t *r, int16_t *dst, size_t n) {
   if (!r || !dst) return 0;
-  if (r->frames >= 0 && (int64_t)n > r->frames - r->pos) n = (size_t)(r->frames - r->pos);
-  const size_t got = fread(dst, 4, n, r->f);
-  r->pos += (int64_t)got;
-  return got;
+  if (r->sample_format != RDSP_SRC_S16) {
+    rdsp_set_error("rdsp_iq_reader_read: the recording is not int16 (sample format %d); use rdsp_iq_reader_read_samples", r->sample_format);
+    return 0;
+  }
+  return rdsp_iq_reader_read_samples(r, dst, n);
 }
 
 void rdsp_iq_reader_close(rdsp_iq_reader_t *r) {

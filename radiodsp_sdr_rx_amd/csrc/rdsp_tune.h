@@ -9,6 +9,9 @@
  * at most (2 pi / TUNE_N)^2 / 8 = 4.7e-6 at TUNE_N = 1024, below 2^-17 with the rounding of the table and of the fmaf
  * (tests/test_engine_tuning.py sweeps it).  Phase 0 is entry 0 with a zero fraction: exactly (1, 0), so a receiver whose
  * shift is 0 gets its source's pairs unchanged, -32768 included.
+ *
+ * The source rows may hold int16, uint8, int8 or float32 pairs (rdsp_engine_set_source_format): src_value below is the one
+ * place where an element becomes the float that enters the arithmetic, for all three passes and for the host restatements.
  */
 #ifndef RDSP_TUNE_H
 #define RDSP_TUNE_H
@@ -55,11 +58,75 @@ RDSP_HD uint32_t tune_q16(float v) {
   return (uint32_t)(uint16_t)(int16_t)(int)v;
 }
 
+/* ---- the value of a source sample (rdsp_engine_set_source_format): the float, in counts on the int16 scale, that enters the
+ * arithmetic of all three passes.  `bits` is the element zero-extended (a float's bit pattern).  ONE function for the kernels
+ * and the host restatements; everything after it is the same arithmetic in every format.
+ *   S16  (float)x
+ *   U8   offset binary: (float)(2 u - 255) x 128, exact, +-32 640, symmetric about 127.5 where a dongle's zero sits
+ *   S8   (float)s x 256, exact
+ *   F32  full scale +-1.0: NaN -> 0; otherwise clamp(x, -256, 256) x 32768 (the scale is exact; +-inf and wild values stay
+ *        finite at +-2^23 counts, and the output saturates as always)
+ * Every 8-bit value is an exact int16, and a float k / 32768 is the int16 k: those rows give the bits of the int16 pass. */
+constexpr int SRC_S16 = 0, SRC_U8 = 1, SRC_S8 = 2, SRC_F32 = 3, SRC_FORMATS = 4;
+RDSP_HD float src_value(int fmt, uint32_t bits) {
+  switch (fmt) {
+    case SRC_U8: return (float)(2 * (int)(bits & 0xffu) - 255) * 128.0f;
+    case SRC_S8: return (float)(int8_t)(uint8_t)(bits & 0xffu) * 256.0f;
+    case SRC_F32: {
+      const float x = __builtin_bit_cast(float, bits);
+      if (x != x) return 0.0f;
+      return fminf(fmaxf(x, -256.0f), 256.0f) * 32768.0f;
+    }
+    default: return (float)(int16_t)(uint16_t)(bits & 0xffffu);
+  }
+}
+/* bytes of a pair I, Q (interleaved in every format); words of a pair in the engine's history: S16 keeps the packed word, the
+ * other formats keep float2 VALUES, so that a fresh history is exactly 0 in every format (no uint8 byte has the value 0) */
+RDSP_HD int src_pair_bytes(int fmt) { return fmt == SRC_F32 ? 8 : fmt == SRC_S16 ? 4 : 2; }
+RDSP_HD int src_hist_words(int fmt) { return fmt == SRC_S16 ? 1 : 2; }
+/* where pair i of a row in format F lies */
+template <int F>
+RDSP_HD const void *src_at(const void *row, size_t i) {
+  if constexpr (F == SRC_F32) return (const uint2 *)row + i;
+  else if constexpr (F == SRC_S16) return (const uint32_t *)row + i;
+  else return (const uint16_t *)row + i;
+}
+/* pair i of a row in format F; the row is aligned to a pair */
+template <int F>
+RDSP_HD float2 src_pair(const void *row, long long i) {
+  if constexpr (F == SRC_F32) {
+    const uint2 w = ((const uint2 *)row)[i];
+    return make_float2(src_value(F, w.x), src_value(F, w.y));
+  } else if constexpr (F == SRC_S16) {
+    const uint32_t w = ((const uint32_t *)row)[i];
+    return make_float2(src_value(F, w & 0xffffu), src_value(F, w >> 16));
+  } else {
+    const uint32_t w = ((const uint16_t *)row)[i];
+    return make_float2(src_value(F, w & 0xffu), src_value(F, w >> 8));
+  }
+}
+/* pair i of the call's row, or for i < 0 of the `keep` pairs the engine kept from the calls before */
+template <int F, typename I>
+RDSP_HD float2 src_or_hist(const void *row, const void *hist, I i, int keep) {
+  if constexpr (F == SRC_S16) {
+    const uint32_t w = i >= 0 ? ((const uint32_t *)row)[i] : ((const uint32_t *)hist)[i + keep];
+    return make_float2(src_value(F, w & 0xffffu), src_value(F, w >> 16));
+  } else {
+    return i >= 0 ? src_pair<F>(row, i) : ((const float2 *)hist)[i + keep];
+  }
+}
+
 /* one int16 pair (a word I | Q << 16) times (c + j s), rotated as the engine's shifter rotates */
 RDSP_HD uint32_t tune_pair(uint32_t w, float2 cs) {
-  const float i = (float)(int16_t)(uint16_t)(w & 0xffffu), q = (float)(int16_t)(uint16_t)(w >> 16);
+  const float i = src_value(SRC_S16, w & 0xffffu), q = src_value(SRC_S16, w >> 16);
   const float ir = fmaf(i, cs.x, -(q * cs.y));
   const float qr = fmaf(q, cs.x, i * cs.y);
+  return tune_q16(ir) | tune_q16(qr) << 16;
+}
+/* the same on a pair of values */
+RDSP_HD uint32_t tune_pair(float2 x, float2 cs) {
+  const float ir = fmaf(x.x, cs.x, -(x.y * cs.y));
+  const float qr = fmaf(x.y, cs.x, x.x * cs.y);
   return tune_q16(ir) | tune_q16(qr) << 16;
 }
 
@@ -75,13 +142,14 @@ inline uint32_t tune_dphi(float tuning_offset, double station_hz) { return ddc_d
 
 /* the pass's arguments: receivers are visited in `order` (grouped by source); cpw receivers per workgroup */
 struct TuneParams {
-  const uint32_t *src; size_t src_stride;   /* [source][t] words I | Q << 16 */
+  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs */
   uint32_t *dst; size_t dst_stride;         /* [ch][t] */
   const int *order, *source_of;             /* [n_channels] */
   uint32_t *phase; const uint32_t *dphi;    /* [n_channels] */
   const float4 *tab;                        /* [TUNE_N] */
   int n_channels, cpw;
-  uint32_t n_samples;                       /* a multiple of 4 */
+  uint32_t n_samples;                       /* a multiple of 8 */
+  int format;                               /* SRC_* */
 };
 constexpr int TUNE_THREADS = 256;
 constexpr int TUNE_MAX_CPW = 8;
@@ -168,9 +236,15 @@ RDSP_HD uint32_t ddc_rot(float re, float im, float2 cs) {
 RDSP_HD uint32_t ddc_output(const float2 *g, int T, const uint32_t *newest, float2 cs) {
   float re = 0.0f, im = 0.0f;
   for (int k = 0; k < T; k++) {
-    const uint32_t w = newest[-k];
-    ddc_mac(re, im, g[k], (float)(int16_t)(uint16_t)(w & 0xffffu), (float)(int16_t)(uint16_t)(w >> 16));
+    const float2 x = src_pair<SRC_S16>(newest, -k);
+    ddc_mac(re, im, g[k], x.x, x.y);
   }
+  return ddc_rot(re, im, cs);
+}
+/* the same on values (src_pair of any format, or the history's) */
+RDSP_HD uint32_t ddc_output(const float2 *g, int T, const float2 *newest, float2 cs) {
+  float re = 0.0f, im = 0.0f;
+  for (int k = 0; k < T; k++) ddc_mac(re, im, g[k], newest[-k].x, newest[-k].y);
   return ddc_rot(re, im, cs);
 }
 
@@ -180,8 +254,9 @@ constexpr int DDC_THREADS = 256;
 constexpr int DDC_C = 4;                          /* receivers per wave, a register block */
 constexpr int DDC_RPW = DDC_C * (DDC_THREADS / 64); /* receivers per workgroup */
 struct DdcParams {
-  const uint32_t *src; size_t src_stride;   /* [source][t] words I | Q << 16, n_out * D per row */
-  uint32_t *hist;                           /* [source][15 D]: the pairs before the call; rewritten after the pass */
+  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs, n_out * D per row */
+  void *hist;                               /* [source][15 D]: the pairs before the call (S16: words; otherwise float2 values);
+                                               rewritten after the pass */
   uint32_t *dst; size_t dst_stride;         /* [ch][m] */
   const int *order, *source_of;             /* [n_channels] */
   const int *wg_first, *wg_count;           /* [n_wg] */
@@ -191,6 +266,7 @@ struct DdcParams {
   float2 *g;                                /* [n_channels][16 D], written by the pass's first kernel */
   int n_channels, n_sources, n_wg, D;
   uint32_t n_out;                           /* a multiple of 128 */
+  int format;                               /* SRC_* */
 };
 
 /* ---- sources at 44 100 P / Q Hz: tune, low-pass and change the rate by Q / P in one polyphase pass (rdsp_engine_set_source_rate) --
@@ -254,14 +330,23 @@ inline void rate_taps(int P, int Q, double gain, float *out) {
   delete[] h;
 }
 /* the tap on the sample: two rounded products */
-RDSP_HD float2 rate_u(float h, uint32_t w) {
-  return make_float2(h * (float)(int16_t)(uint16_t)(w & 0xffffu), h * (float)(int16_t)(uint16_t)(w >> 16));
-}
+RDSP_HD float2 rate_u(float h, float2 x) { return make_float2(h * x.x, h * x.y); }
+RDSP_HD float2 rate_u(float h, uint32_t w) { return rate_u(h, make_float2(src_value(SRC_S16, w & 0xffffu), src_value(SRC_S16, w >> 16))); }
 /* one output: hb points at its branch's Tb taps, newest at x[n(i)] (the Tb - 1 words before it are read) */
 RDSP_HD uint32_t rate_output(const float4 *tab, const float *hb, int Tb, uint32_t dphi, const uint32_t *newest, float2 cs) {
   float re = 0.0f, im = 0.0f;
   uint32_t ph = 0u;
   for (int j = 0; j < Tb; j++, ph -= dphi) { /* ph = 0 - j dphi */
+    const float2 u = rate_u(hb[j], newest[-j]);
+    ddc_mac(re, im, tune_phasor(tab, ph), u.x, u.y);
+  }
+  return ddc_rot(re, im, cs);
+}
+/* the same on values */
+RDSP_HD uint32_t rate_output(const float4 *tab, const float *hb, int Tb, uint32_t dphi, const float2 *newest, float2 cs) {
+  float re = 0.0f, im = 0.0f;
+  uint32_t ph = 0u;
+  for (int j = 0; j < Tb; j++, ph -= dphi) {
     const float2 u = rate_u(hb[j], newest[-j]);
     ddc_mac(re, im, tune_phasor(tab, ph), u.x, u.y);
   }
@@ -278,8 +363,9 @@ constexpr int RATE_TILE = 2 * RATE_O;
 constexpr int RATE_RPW = 64 * RATE_C * 2; /* receivers per workgroup: two waves split them */
 constexpr int RATE_CHUNK = 128;           /* taps staged in LDS at a time */
 struct RateParams {
-  const uint32_t *src; size_t src_stride;   /* [source][t] words I | Q << 16, `pairs` per row, rows 4-byte aligned */
-  uint32_t *hist;                           /* [source][Tb]: the pairs before the call; rewritten after the pass */
+  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs, `pairs` per row, rows pair-aligned */
+  void *hist;                               /* [source][Tb]: the pairs before the call (S16: words; otherwise float2 values);
+                                               rewritten after the pass */
   uint32_t *dst; size_t dst_stride;         /* [ch][i] */
   const int *order, *source_of;             /* [n_channels] */
   const int *wg_first, *wg_count;           /* [n_wg] */
@@ -289,6 +375,7 @@ struct RateParams {
   RateStep *sched;                          /* [n_out], written by the pass's first kernel */
   int n_channels, n_sources, n_wg, P, Q;
   uint32_t frac, n_out, pairs;              /* n_out a multiple of 128 */
+  int format;                               /* SRC_* */
 };
 
 }  // namespace rdsp_tune

@@ -10,7 +10,13 @@ from ._lib import check, load
 LSBmode, USBmode, CW_LSBmode, CW_USBmode, AMmode, SAMmode = range(6)      # as the compiled tuningMode() passes them
 audioAM, audioCW, audio2100, audio2700, audio3100, audioNone = 0, 1, 3, 6, 8, 10
 AGCoff, AGCfast, AGCmedium, AGCslow = range(4)
+SRC_S16, SRC_U8, SRC_S8, SRC_F32 = range(4)                              # RDSP_SRC_*: what the source rows hold
 _F32P = C.POINTER(C.c_float)
+
+
+def _src_dtype(fmt):
+    import torch
+    return (torch.int16, torch.uint8, torch.int8, torch.float32)[fmt]
 
 
 class Engine:
@@ -89,39 +95,52 @@ class Engine:
         """pairs of every source row the NEXT update_sources(..., n_blocks=n_blocks) consumes"""
         return int(self.lib.rdsp_engine_source_pairs(self.h, int(n_blocks)))
 
+    def set_source_format(self, fmt):
+        """the source rows are SRC_S16 (default), SRC_U8 (offset binary, .cu8), SRC_S8 (.cs8) or SRC_F32 (full scale +-1.0): one
+        format per engine, read in place by update_sources().  A setting (kept by reset and the rate setters); another format
+        begins another stream (source histories and frac zeroed, phases kept).  After set_sources()."""
+        check(self.lib.rdsp_engine_set_source_format(self.h, int(fmt)))
+
+    def source_format(self):
+        return int(self.lib.rdsp_engine_source_format(self.h))
+
     def tune(self, first_channel, station_hz):
         """receivers first_channel ... get the stations station_hz (Hz from their source stream's centre, |f| < D x 22050)"""
         st = np.ascontiguousarray(np.atleast_1d(station_hz), np.float64)
         check(self.lib.rdsp_engine_tune(self.h, int(first_channel), st.size, st.ctypes.data_as(C.POINTER(C.c_double))))
 
     def update_sources(self, d_src, out=None, stream=None, n_blocks=None):
-        """d_src: torch int16 [n_sources, n D, 2] on the engine's device, n a multiple of 128, D the source decimation ->
+        """d_src: torch int16 (uint8 / int8 / float32 under the matching set_source_format) [n_sources, n D, 2] on the engine's
+        device, n a multiple of 128, D the source decimation ->
         int16 [n_channels, n, 2]: every receiver tuned to its station in its source row (and for D > 1 low-passed and
         decimated), then update().  With n_blocks: n = n_blocks x 128 outputs from the first source_pairs(n_blocks) pairs of
-        every row of d_src, which may be a view into a longer buffer (rows any even number of int16 apart); required with a
+        every row of d_src, which may be a view into a longer buffer (rows any whole number of pairs apart); required with a
         rational rate (set_source_rate)."""
-        import torch
         nsrc, n_in, two = d_src.shape
         D = getattr(self, "D", 1)
+        import torch
+        fmt = self.source_format()
+        dtype = _src_dtype(fmt)
+        assert d_src.dtype == dtype, f"the engine's source format {fmt} takes {dtype} rows, not {d_src.dtype}"
         if n_blocks is not None:
             n, need = int(n_blocks) * 128, self.source_pairs(n_blocks)
-            assert two == 2 and d_src.dtype == torch.int16 and n_in >= need, "d_src holds fewer pairs than source_pairs(n_blocks)"
+            assert two == 2 and n_in >= need, "d_src holds fewer pairs than source_pairs(n_blocks)"
             assert d_src.stride(2) == 1 and d_src.stride(1) == 2 and d_src.stride(0) % 2 == 0
             assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
             if out is None:
                 out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
             s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
             stride = d_src.stride(0) // 2 if nsrc > 1 else max(n_in, need)
-            check(self.lib.rdsp_engine_update_sources(self.h, d_src.data_ptr(), stride, int(n_blocks), out.data_ptr(), n, C.c_void_p(s)))
+            check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), stride, int(n_blocks), out.data_ptr(), n, C.c_void_p(s)))
             return out
         assert D >= 1, "a rational source rate is set: pass n_blocks"
         n = n_in // D
-        assert two == 2 and n_in == n * D and n % 128 == 0 and d_src.dtype == torch.int16 and d_src.is_contiguous()
+        assert two == 2 and n_in == n * D and n % 128 == 0 and d_src.is_contiguous()
         assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
         if out is None:
             out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(self.lib.rdsp_engine_update_sources(self.h, d_src.data_ptr(), n_in, n // 128, out.data_ptr(), n, C.c_void_p(s)))
+        check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), n_in, n // 128, out.data_ptr(), n, C.c_void_p(s)))
         return out
 
     def set_groups(self, first_channels):

@@ -7,18 +7,26 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .engine import SRC_F32, SRC_S8, SRC_S16, SRC_U8  # noqa: F401  (RDSP_SRC_*: what a recording's elements are)
 
 IO_AUTO, IO_RAW, IO_WAV = 0, 1, 2
 
 
-class IqReader:
-    """One receiver channel's recording: RAW int16 I,Q pairs or 16-bit stereo WAV (I left, Q right)."""
+_SRC_DTYPE = (np.int16, np.uint8, np.int8, np.float32)
 
-    def __init__(self, path, fmt=IO_AUTO):
+
+class IqReader:
+    """One receiver channel's recording: RAW int16 I,Q pairs or 16-bit stereo WAV (I left, Q right).  With sample_format
+    (SRC_*, or -1 for what a WAV header says) also RAW uint8 / int8 / float32 pairs and 8-bit or float32 WAV."""
+
+    def __init__(self, path, fmt=IO_AUTO, sample_format=None):
         self.h = None
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.rdsp_iq_reader_open(str(path).encode(), int(fmt), C.byref(h)))
+        if sample_format is None:
+            _lib.check(self.lib.rdsp_iq_reader_open(str(path).encode(), int(fmt), C.byref(h)))
+        else:
+            _lib.check(self.lib.rdsp_iq_reader_open_samples(str(path).encode(), int(fmt), int(sample_format), C.byref(h)))
         self.h = h
 
     @property
@@ -28,9 +36,18 @@ class IqReader:
     @property
     def format(self): return int(self.lib.rdsp_iq_reader_format(self.h))
 
+    @property
+    def sample_format(self): return int(self.lib.rdsp_iq_reader_sample_format(self.h))
+
     def read(self, n_pairs):
         buf = np.empty((n_pairs, 2), np.int16)
         got = self.lib.rdsp_iq_reader_read(self.h, buf.ctypes.data_as(_lib._i16p), n_pairs)
+        return buf[:got]
+
+    def read_samples(self, n_pairs):
+        """up to n_pairs pairs in the file's own format: int16 / uint8 / int8 / float32 [n, 2]"""
+        buf = np.empty((n_pairs, 2), _SRC_DTYPE[self.sample_format])
+        got = self.lib.rdsp_iq_reader_read_samples(self.h, buf.ctypes.data_as(C.c_void_p), n_pairs)
         return buf[:got]
 
     def close(self):
