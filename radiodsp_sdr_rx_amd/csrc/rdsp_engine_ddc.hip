@@ -4,10 +4,11 @@
  * engine's IF, low-passed by a 16 D-tap FIR and decimated by D.  The definition and the order of the arithmetic are
  * rdsp_tune.h's (ddc_tap, ddc_mac, ddc_rot); D = 1 is rdsp_engine_tune.hip, which this file does not touch.
  *
- * Three kernels a call, in stream order:
+ * Two kernels a call, in stream order:
  *   rdsp_engine_ddc_taps_kernel    g[ch][k] = h[k] e^{-j k dphi[ch]}, one lane a tap, vector stores;
  *   rdsp_engine_ddc_kernel         the filter bank (below);
- *   rdsp_engine_ddc_finish_kernel  the last 15 D pairs of every source row -> the engine's history, phases += n_out D dphi.
+ * after them the engine runs the finish kernel of both filter-bank passes (rdsp_engine_tune.hip): the last 15 D pairs of every
+ * source row -> the engine's history, phases += n_out D dphi.
  *
  * The filter bank: a workgroup takes up to DDC_RPW receivers of ONE source that are neighbours in `order` and a tile of
  * 64 O outputs, O = 4, 2 or 1 by D (rdsp_engine_ddc_launch).  It stages the (64 O + 15) D pairs the tile needs in LDS once
@@ -26,8 +27,6 @@
  * Compiled with -ffp-contract=off: every fused operation is an fmaf.
  */
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
 
 #include "rdsp_tune.h"
 
@@ -111,36 +110,20 @@ __global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_kernel(DdcParams 
   }
 }
 
-template <int F>
-__global__ __launch_bounds__(DDC_THREADS) void rdsp_engine_ddc_finish_kernel(DdcParams p) {
-  const uint32_t keep = (uint32_t)(DDC_HIST_PER_PHASE * p.D), n_in = p.n_out * (uint32_t)p.D; /* n_in >= 128 D > keep */
-  const uint32_t i = blockIdx.x * DDC_THREADS + threadIdx.x;
-  if (i < (uint32_t)p.n_sources * keep) {
-    const uint32_t s = i / keep, t = i - s * keep;
-    const void *row = src_at<F>(p.src, (size_t)s * p.src_stride);
-    if constexpr (F == SRC_S16) ((uint32_t *)p.hist)[i] = ((const uint32_t *)row)[(n_in - keep) + t];
-    else ((float2 *)p.hist)[i] = src_pair<F>(row, (long long)(n_in - keep) + t);
-  }
-  if (i < (uint32_t)p.n_channels) p.phase[i] = tune_phase(p.phase[i], (uint32_t)p.D * p.dphi[i], p.n_out);
-}
-
 constexpr size_t DDC_LDS_BUDGET = 163840 / 3;
 size_t ddc_lds_bytes(int D, int O) { return (size_t)D * (size_t)(64 * O + DDC_HIST_PER_PHASE) * sizeof(float2); } /* at most 40 448 at O = 1 */
 
 template <int F>
-void ddc_launch(const DdcParams &p, int O, size_t grid, size_t lds, size_t n_fin, hipStream_t s) {
+void ddc_launch(const DdcParams &p, int O, size_t grid, size_t lds, hipStream_t s) {
   if (O == 4) hipLaunchKernelGGL((rdsp_engine_ddc_kernel<F, 4>), dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
   else if (O == 2) hipLaunchKernelGGL((rdsp_engine_ddc_kernel<F, 2>), dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
   else hipLaunchKernelGGL((rdsp_engine_ddc_kernel<F, 1>), dim3((unsigned)grid), dim3(DDC_THREADS), lds, s, p);
-  hipLaunchKernelGGL(rdsp_engine_ddc_finish_kernel<F>, dim3((unsigned)((n_fin + DDC_THREADS - 1) / DDC_THREADS)), dim3(DDC_THREADS), 0, s, p);
 }
 }  // namespace
 
 hipError_t rdsp_engine_ddc_launch(const DdcParams &p, hipStream_t s) {
-  if (p.format < 0 || p.format >= SRC_FORMATS) return hipErrorInvalidValue;
   const size_t T = (size_t)(DDC_TAPS_PER_PHASE * p.D);
   const size_t n_g = (size_t)p.n_channels * T;
-  hipLaunchKernelGGL(rdsp_engine_ddc_taps_kernel, dim3((unsigned)((n_g + DDC_THREADS - 1) / DDC_THREADS)), dim3(DDC_THREADS), 0, s, p);
   /* outputs per lane: the most whose tile leaves room for three workgroups' LDS on a CU (measured: D = 24 runs faster at 4
    * than at 2, D = 30 and 40 faster at 2 than at 4 or 1, D = 56 and 64 no faster at 2 than at 1); 4 needs whole tiles of 256 */
   int O = 4;
@@ -148,12 +131,8 @@ hipError_t rdsp_engine_ddc_launch(const DdcParams &p, hipStream_t s) {
   const size_t lds = ddc_lds_bytes(p.D, O);
   const size_t grid = (size_t)p.n_wg * (p.n_out / (64u * O));
   if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  const size_t n_fin = std::max((size_t)p.n_sources * (size_t)(DDC_HIST_PER_PHASE * p.D), (size_t)p.n_channels);
-  switch (p.format) {
-    case SRC_S16: ddc_launch<SRC_S16>(p, O, grid, lds, n_fin, s); break;
-    case SRC_U8: ddc_launch<SRC_U8>(p, O, grid, lds, n_fin, s); break;
-    case SRC_S8: ddc_launch<SRC_S8>(p, O, grid, lds, n_fin, s); break;
-    default: ddc_launch<SRC_F32>(p, O, grid, lds, n_fin, s); break;
-  }
-  return hipGetLastError();
+  return dispatch_format(p.format, [&](auto f) {
+    hipLaunchKernelGGL(rdsp_engine_ddc_taps_kernel, dim3((unsigned)((n_g + DDC_THREADS - 1) / DDC_THREADS)), dim3(DDC_THREADS), 0, s, p);
+    ddc_launch<decltype(f)::value>(p, O, grid, lds, s);
+  });
 }

@@ -1,8 +1,9 @@
 /*
- * rdsp_engine_host.hip -- the host object behind rdsp_engine_t (include/rdsp.h): the sketch's settings, receiver groups,
- * receivers on shared IQ sources (the set-up of the tuning and decimating passes), the signal state as a blob, and every
- * rdsp_engine_* entry point.  The kernels and the signal path are rdsp_engine.hip's; a call hands rdsp_engine_launch
- * (rdsp_engine_int.h) one group's arguments.  Every device buffer has one owner (DevBuf): deleting the object frees them.
+ * rdsp_engine_host.hip -- the host object behind rdsp_engine_t (include/rdsp.h): the sketch's settings, receiver groups, the
+ * signal state as a blob, and every rdsp_engine_* entry point.  The kernels and the signal path are rdsp_engine.hip's; a call
+ * hands rdsp_engine_launch (rdsp_engine_int.h) one group's arguments.  Receivers on shared IQ sources are the front end's
+ * (rdsp_engine_sources.h): the entry points here check their arguments and make one call into it.  Every device buffer has
+ * one owner (DevBuf): deleting the object frees them.
  * Compiled with the kernels' flags (-ffp-contract=off): the constants and tables computed here are held bit for bit. */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -14,7 +15,7 @@
 
 #include "rdsp_engine_int.h"
 #include "rdsp_engine_laws.h"
-#include "rdsp_tune.h"
+#include "rdsp_engine_sources.h"
 
 using namespace rdsp_eng;
 
@@ -27,19 +28,6 @@ struct EngSettings {
 };
 /* the planes of a channel's signal state: create allocates them, reset fills them, save_state / load_state move them */
 enum { PL_ST, PL_RING_I, PL_RING_Q, PL_NB, PL_ALS, N_PLANES };
-/* the device side of shared IQ streams, from the first rdsp_engine_set_sources on: phase accumulators and steps per channel,
- * the tuned rows, the source map, the decimating pass's workgroup list (from the map, whatever D is), the phasor table */
-struct EngSources {
-  DevBuf<uint32_t> phase, dphi, tuned;
-  DevBuf<int> source_of, order, wg_first, wg_count;
-  DevBuf<int> rate_wg_first, rate_wg_count; /* the polyphase pass's workgroups: runs of at most RATE_RPW receivers */
-  DevBuf<float4> tune_tab;
-  rdsp_dev::Event dphi_ev; /* the last upload of dphi has left dphi_stage */
-};
-/* sources at D > 1: the prototype's taps, every receiver's translated taps, and per SOURCE the last 15 D pairs */
-struct EngDdc { DevBuf<float> h; DevBuf<float2> g; DevBuf<uint32_t> hist; }; /* hist: src_hist_words(format) words a pair */
-/* sources at 44 100 P / Q Hz, Q > 1: the prototype by branches hb[r][j], per SOURCE the last Tb pairs, the call's schedule */
-struct EngRate { DevBuf<float> hb; DevBuf<uint32_t> hist; DevBuf<rdsp_tune::RateStep> sched; };
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -53,22 +41,9 @@ struct rdsp_engine {
   std::vector<EngSettings> grp; /* at least one */
   std::vector<int> first;       /* first channel of each group, ascending; first[0] = 0 */
   int sel = -1;                 /* the group the setters address; -1: all of them */
-  /* shared IQ streams (rdsp_engine_set_sources / tune / update_sources) */
-  std::unique_ptr<EngSources> src;
-  std::vector<double> station;  /* per channel, Hz from its stream's centre (0 until tuned) */
-  std::vector<float> tune_to;   /* per group: the tuning offset the steps were computed with */
-  std::vector<uint32_t> dphi_stage; /* the host side of the last dphi upload; reused once dphi_ev has passed */
-  bool dphi_stale = true;
-  /* sources at ddc_D x 44 100 Hz (rdsp_engine_set_source_decimation) */
-  int n_sources = 0, ddc_D = 1, n_wg = 0;
-  float ddc_gain = 1.0f;
-  std::unique_ptr<EngDdc> ddc; /* while ddc_D > 1 */
-  /* sources at 44 100 rate_P / rate_Q Hz (rdsp_engine_set_source_rate), in lowest terms; while `rate` exists rate_Q > 1 and ddc_D is 1 */
-  int rate_P = 1, rate_Q = 1, n_rate_wg = 0;
-  uint32_t frac = 0; /* (outputs since the last reset x rate_P) mod rate_Q */
-  std::unique_ptr<EngRate> rate;
-  /* the format of the source rows (rdsp_engine_set_source_format): a setting; the histories hold words for S16, float2 values otherwise */
-  int src_format = rdsp_tune::SRC_S16;
+  /* shared IQ streams (rdsp_engine_set_sources / tune / update_sources): the front end, from the first set_sources on */
+  std::unique_ptr<EngFrontEnd> src;
+  std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
 };
 
 namespace {
@@ -81,22 +56,8 @@ void engine_sam_constants(rdsp_engine_t *e) { /* 0xed34 with the constructor's l
   e->sam_ga = g1 + g2;
   e->sam_gb = g2;
 }
-/* what the arguments of the tuning and the decimating pass share (rdsp_engine_update_sources) */
-template <typename P>
-P source_pass(const rdsp_engine_t *e, const void *d_src, size_t src_stride) {
-  P p;
-  p.src = d_src; p.src_stride = src_stride; p.format = e->src_format;
-  p.dst = e->src->tuned; p.dst_stride = (size_t)e->max_blocks * BS;
-  p.order = e->src->order; p.source_of = e->src->source_of;
-  p.phase = e->src->phase; p.dphi = e->src->dphi; p.tab = e->src->tune_tab; p.n_channels = e->n_channels;
-  return p;
-}
-/* words of the source histories: keep pairs of every source, in the engine's format */
-size_t hist_words(const rdsp_engine_t *e, size_t keep) { return (size_t)e->n_sources * keep * (size_t)rdsp_tune::src_hist_words(e->src_format); }
-/* |station| must stay below it: half the source rate */
-double source_band_hz(const rdsp_engine_t *e) {
-  return e->rate ? (rdsp_tune::TUNE_MAX_HZ * (double)e->rate_P) / (double)e->rate_Q : (double)e->ddc_D * rdsp_tune::TUNE_MAX_HZ;
-}
+/* the stream of source rows; an engine without sources answers as one at 44 100 Hz on int16 rows */
+SourceStream source_stream(const rdsp_engine_t *e) { return e && e->src ? e->src->st : SourceStream(); }
 /* the setters address the selected group, or all of them */
 template <typename F>
 int for_selected(rdsp_engine_t *e, F f) {
@@ -251,7 +212,7 @@ int rdsp_engine_set_groups(rdsp_engine_t *e, int n_groups, const int *first_chan
   e->grp.swap(grp);
   e->first.assign(first_channel, first_channel + n_groups);
   e->sel = -1;
-  e->dphi_stale = true; /* a channel's step follows its new group's mode */
+  if (e->src) e->src->steps_changed(); /* a channel's step follows its new group's mode */
   return RDSP_OK;
 }
 int rdsp_engine_groups(const rdsp_engine_t *e) { return e ? (int)e->grp.size() : 0; }
@@ -286,10 +247,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   for (int k = 0; k < N_PLANES && err == hipSuccess; k++)
     err = fill[k].empty() ? hipMemsetAsync(e->plane[k], 0, n * e->plane_words[k] * 4, s)
                           : hipMemcpyAsync(e->plane[k], fill[k].data(), fill[k].size() * 4, hipMemcpyHostToDevice, s);
-  if (err == hipSuccess && e->src) err = hipMemsetAsync(e->src->phase, 0, n * 4, s); /* the stations are settings: kept */
-  if (err == hipSuccess && e->ddc) err = hipMemsetAsync(e->ddc->hist, 0, hist_words(e, (size_t)rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D) * 4, s);
-  if (err == hipSuccess && e->rate) err = hipMemsetAsync(e->rate->hist, 0, hist_words(e, (size_t)rdsp_tune::rate_tb(e->rate_P, e->rate_Q)) * 4, s);
-  e->frac = 0;
+  if (err == hipSuccess && e->src) err = e->src->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -399,91 +357,25 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
   return RDSP_OK;
 }
 
-/* ---- shared IQ streams: receivers tuned to stations inside source rows ----------------------------------------------------
- * rdsp_engine_update_sources runs a tuning pass (rdsp_engine_tune.hip, arithmetic in rdsp_tune.h) that writes each
- * receiver's row -- its source row times e^{+j phi}, phi advancing by round((TuningOffset - station) 2^32 / 44100) per
- * sample -- into `tuned`, then the engine's own launches of rdsp_engine_update on those rows.  The steps are computed here
- * from each channel's station and its group's current mode; they are uploaded only when one of them changed. */
+/* ---- shared IQ streams: receivers tuned to stations inside source rows (the front end, rdsp_engine_sources.hip) ---------- */
 namespace {
-hipError_t upload_dphi(rdsp_engine_t *e, hipStream_t s) {
-  bool changed = e->dphi_stale || e->tune_to.size() != e->grp.size();
-  for (size_t g = 0; !changed && g < e->grp.size(); g++) changed = e->tune_to[g] != e->grp[g].tuning_offset;
-  if (!changed) return hipSuccess;
-  hipError_t err = hipEventSynchronize(e->src->dphi_ev); /* the last upload has left dphi_stage */
-  e->tune_to.resize(e->grp.size());
-  for (size_t g = 0; g < e->grp.size(); g++) {
-    const int c1 = range_end(e->first, g, e->n_channels);
-    for (int c = e->first[g]; c < c1; c++) e->dphi_stage[(size_t)c] = e->rate ? rdsp_tune::rate_dphi(e->grp[g].tuning_offset, e->station[(size_t)c], e->rate_P, e->rate_Q)
-                                                                      : rdsp_tune::ddc_dphi(e->grp[g].tuning_offset, e->station[(size_t)c], e->ddc_D);
-    e->tune_to[g] = e->grp[g].tuning_offset;
-  }
-  if (err == hipSuccess) err = hipMemcpyAsync(e->src->dphi, e->dphi_stage.data(), e->dphi_stage.size() * 4, hipMemcpyHostToDevice, s);
-  if (err == hipSuccess) err = hipEventRecord(e->src->dphi_ev, s);
-  if (err == hipSuccess) e->dphi_stale = false;
-  return err;
+bool gain_ok(float gain) { return gain > 0.0f && std::isfinite(gain); }
+/* the refusal of everything that needs rdsp_engine_set_sources first */
+bool no_sources(const rdsp_engine_t *e, const char *who) {
+  if (!e->src) rdsp_set_error("%s: no sources; call rdsp_engine_set_sources first", who);
+  return !e->src;
 }
-/* the device side of a decimation D on n_sources rows: the history is new (zero) when either changed, the taps always.
- * The caller has waited for queued work. */
-hipError_t ddc_setup(rdsp_engine_t *e, int D, float gain, int n_sources) {
-  hipError_t err = hipSuccess;
-  if (e->rate) { /* an integer rate replaces a rational one: its histories and its schedule go */
-    e->rate.reset();
-    e->rate_P = e->rate_Q = 1;
-    e->frac = 0;
-    e->n_sources = -1; /* what follows is new */
-  }
-  if (D != e->ddc_D || n_sources != e->n_sources) {
-    e->ddc.reset();
-    e->ddc_D = 1; /* until everything below exists */
-    e->n_sources = n_sources;
-    if (D > 1) {
-      const size_t T = (size_t)rdsp_tune::DDC_TAPS_PER_PHASE * D, keep = hist_words(e, (size_t)rdsp_tune::DDC_HIST_PER_PHASE * D);
-      auto d = std::make_unique<EngDdc>();
-      err = d->h.alloc(T);
-      if (err == hipSuccess) err = d->g.alloc((size_t)e->n_channels * T);
-      if (err == hipSuccess) err = d->hist.alloc(keep);
-      if (err == hipSuccess) err = hipMemset(d->hist, 0, keep * 4);
-      if (err != hipSuccess) return err;
-      e->ddc = std::move(d);
-    }
-  }
-  if (D > 1) {
-    std::vector<float> h((size_t)rdsp_tune::DDC_TAPS_PER_PHASE * D);
-    rdsp_tune::ddc_taps(D, (double)gain, h.data());
-    err = hipMemcpy(e->ddc->h, h.data(), h.size() * 4, hipMemcpyHostToDevice);
-    if (err != hipSuccess) return err;
-  }
-  e->ddc_D = D;
-  e->ddc_gain = gain;
-  e->dphi_stale = true; /* the step is per source sample */
-  return hipSuccess;
+/* the first channel whose station lies outside +-band, or -1 */
+int station_outside(const rdsp_engine_t *e, double band) {
+  for (size_t c = 0; c < e->station.size(); c++)
+    if (!(fabs(e->station[c]) < band)) return (int)c;
+  return -1;
 }
-/* the device side of a rate P / Q (lowest terms, Q > 1) on n_sources rows: histories and schedule are new (zero) when the
- * rate or the number of rows changed, the taps always.  The caller has waited for queued work. */
-hipError_t rate_setup(rdsp_engine_t *e, int P, int Q, float gain, int n_sources) {
-  const size_t Tb = (size_t)rdsp_tune::rate_tb(P, Q), keep = (size_t)n_sources * Tb * (size_t)rdsp_tune::src_hist_words(e->src_format);
-  std::vector<float> h(Tb * (size_t)Q), hb(Tb * (size_t)Q);
-  rdsp_tune::rate_taps(P, Q, (double)gain, h.data());
-  for (size_t r = 0; r < (size_t)Q; r++)
-    for (size_t j = 0; j < Tb; j++) hb[r * Tb + j] = h[j * (size_t)Q + r];
-  if (!e->rate || P != e->rate_P || Q != e->rate_Q || n_sources != e->n_sources) {
-    auto d = std::make_unique<EngRate>();
-    hipError_t err = d->hb.alloc(hb.size());
-    if (err == hipSuccess) err = d->hist.alloc(keep);
-    if (err == hipSuccess) err = d->sched.alloc((size_t)e->max_blocks * BS);
-    if (err == hipSuccess) err = hipMemset(d->hist, 0, keep * 4);
-    if (err != hipSuccess) return err;
-    e->rate = std::move(d);
-    e->ddc.reset(); /* a rational rate replaces an integer one */
-    e->ddc_D = 1;
-    e->rate_P = P; e->rate_Q = Q; e->n_sources = n_sources;
-    e->frac = 0;
-  }
-  const hipError_t err = hipMemcpy(e->rate->hb, hb.data(), hb.size() * 4, hipMemcpyHostToDevice);
-  if (err != hipSuccess) return err;
-  e->ddc_gain = gain;
-  e->dphi_stale = true; /* the step is per source sample */
-  return hipSuccess;
+/* the end of every setter that may begin another stream */
+int configure_sources(rdsp_engine_t *e, const char *who, int P, int Q, float gain, int format) {
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = e->src->configure(P, Q, gain, e->src->st.n_sources, format);
+  return err == hipSuccess ? RDSP_OK : engine_fail(who, err);
 }
 }  // namespace
 
@@ -506,126 +398,65 @@ int rdsp_engine_set_sources(rdsp_engine_t *e, int n_sources, const int *source_o
       rdsp_set_error("rdsp_engine_set_sources: channel %d listens to source %d of %d", c, source_of_channel[c], n_sources);
       return RDSP_ERR_INVALID;
     }
-  const size_t n = (size_t)e->n_channels;
-  std::vector<int> order(n);
-  for (size_t c = 0; c < n; c++) order[c] = (int)c;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return source_of_channel[a] < source_of_channel[b]; });
-  /* the decimating pass's workgroups: runs of at most DDC_RPW receivers of one source, in `order` */
-  std::vector<int> wg_first, wg_count;
-  for (size_t i = 0; i < n;) {
-    size_t j = i + 1;
-    while (j < n && j - i < (size_t)rdsp_tune::DDC_RPW && source_of_channel[order[j]] == source_of_channel[order[i]]) j++;
-    wg_first.push_back((int)i);
-    wg_count.push_back((int)(j - i));
-    i = j;
-  }
-  /* the polyphase pass's: runs of at most RATE_RPW */
-  std::vector<int> rate_wg_first, rate_wg_count;
-  for (size_t i = 0; i < n;) {
-    size_t j = i + 1;
-    while (j < n && j - i < (size_t)rdsp_tune::RATE_RPW && source_of_channel[order[j]] == source_of_channel[order[i]]) j++;
-    rate_wg_first.push_back((int)i);
-    rate_wg_count.push_back((int)(j - i));
-    i = j;
-  }
   hipError_t err = hipSetDevice(e->device);
-  if (err == hipSuccess && e->src) err = hipDeviceSynchronize(); /* queued passes may still read the old map */
   if (err == hipSuccess && !e->src) {
-    auto q = std::make_unique<EngSources>(); /* the object stays without sources unless all of it exists */
-    err = q->phase.alloc(n);
-    if (err == hipSuccess) err = q->dphi.alloc(n);
-    if (err == hipSuccess) err = q->source_of.alloc(n);
-    if (err == hipSuccess) err = q->order.alloc(n);
-    if (err == hipSuccess) err = q->wg_first.alloc(n);
-    if (err == hipSuccess) err = q->wg_count.alloc(n);
-    if (err == hipSuccess) err = q->rate_wg_first.alloc(n);
-    if (err == hipSuccess) err = q->rate_wg_count.alloc(n);
-    if (err == hipSuccess) err = q->tune_tab.alloc(rdsp_tune::TUNE_N);
-    if (err == hipSuccess) err = q->tuned.alloc(n * (size_t)e->max_blocks * BS);
-    if (err == hipSuccess) err = q->dphi_ev.create(hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventRecord(q->dphi_ev, nullptr);
-    if (err == hipSuccess) err = hipMemset(q->phase, 0, n * 4);
-    if (err == hipSuccess) err = hipMemcpy(q->tune_tab, rdsp_engine_tune_table(), rdsp_tune::TUNE_N * sizeof(float4), hipMemcpyHostToDevice);
+    auto q = std::make_unique<EngFrontEnd>(e->n_channels, e->max_blocks); /* the object stays without sources unless all of it exists */
+    err = q->init();
     if (err != hipSuccess) {
       rdsp_set_error("rdsp_engine_set_sources: %s", hipGetErrorString(err));
       return RDSP_ERR_NOMEM;
     }
     e->src = std::move(q);
-    if (e->station.empty()) e->station.assign(n, 0.0);
-    e->dphi_stage.assign(n, 0u);
+    if (e->station.empty()) e->station.assign((size_t)e->n_channels, 0.0);
   }
-  if (err == hipSuccess) err = hipMemcpy(e->src->source_of, source_of_channel, n * sizeof(int), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(e->src->order, order.data(), n * sizeof(int), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(e->src->wg_first, wg_first.data(), wg_first.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(e->src->wg_count, wg_count.data(), wg_count.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(e->src->rate_wg_first, rate_wg_first.data(), rate_wg_first.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(e->src->rate_wg_count, rate_wg_count.data(), rate_wg_count.size() * sizeof(int), hipMemcpyHostToDevice);
-  /* another number of rows: their histories start at zero */
-  if (err == hipSuccess) err = e->rate ? rate_setup(e, e->rate_P, e->rate_Q, e->ddc_gain, n_sources) : ddc_setup(e, e->ddc_D, e->ddc_gain, n_sources);
-  if (err != hipSuccess) return engine_fail("rdsp_engine_set_sources", err);
-  e->n_wg = (int)wg_first.size();
-  e->n_rate_wg = (int)rate_wg_first.size();
-  e->dphi_stale = true;
-  return RDSP_OK;
+  if (err == hipSuccess) err = e->src->set_map(n_sources, source_of_channel);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_set_sources", err);
 }
 
 int rdsp_engine_set_source_decimation(rdsp_engine_t *e, int D, float gain) {
-  if (!e || D < 1 || D > rdsp_tune::DDC_MAX_D || !(gain > 0.0f) || !std::isfinite(gain)) {
+  if (!e || D < 1 || D > rdsp_tune::DDC_MAX_D || !gain_ok(gain)) {
     rdsp_set_error("rdsp_engine_set_source_decimation: bad argument (D %d of 1 .. %d, gain %g must be finite and above 0)", D, rdsp_tune::DDC_MAX_D, (double)gain);
     return RDSP_ERR_INVALID;
   }
-  if (!e->src) {
-    rdsp_set_error("rdsp_engine_set_source_decimation: no sources; call rdsp_engine_set_sources first");
-    return RDSP_ERR_NOT_READY;
+  if (no_sources(e, "rdsp_engine_set_source_decimation")) return RDSP_ERR_NOT_READY;
+  SourceStream to;
+  to.P = D;
+  if (const int c = station_outside(e, to.band_hz()); c >= 0) {
+    rdsp_set_error("rdsp_engine_set_source_decimation: channel %d is tuned to %g Hz, outside a source at %d x 44100 Hz", c, e->station[(size_t)c], D);
+    return RDSP_ERR_INVALID;
   }
-  for (size_t c = 0; c < e->station.size(); c++)
-    if (!(fabs(e->station[c]) < (double)D * rdsp_tune::TUNE_MAX_HZ)) {
-      rdsp_set_error("rdsp_engine_set_source_decimation: channel %zu is tuned to %g Hz, outside a source at %d x 44100 Hz", c, e->station[c], D);
-      return RDSP_ERR_INVALID;
-    }
   if ((uint64_t)e->n_channels * (uint64_t)(rdsp_tune::DDC_TAPS_PER_PHASE * D) > 0xffffffffull) {
     rdsp_set_error("rdsp_engine_set_source_decimation: %d channels x %d taps do not fit the pass's tap table", e->n_channels, rdsp_tune::DDC_TAPS_PER_PHASE * D);
     return RDSP_ERR_UNSUPPORTED;
   }
-  hipError_t err = hipSetDevice(e->device);
-  if (err == hipSuccess) err = hipDeviceSynchronize(); /* queued passes read the taps and the histories */
-  if (err == hipSuccess) err = ddc_setup(e, D, gain, e->n_sources);
-  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_set_source_decimation", err);
+  return configure_sources(e, "rdsp_engine_set_source_decimation", D, 1, gain, e->src->st.format);
 }
-int rdsp_engine_source_decimation(const rdsp_engine_t *e) { return e && !e->rate ? e->ddc_D : 0; }
+int rdsp_engine_source_decimation(const rdsp_engine_t *e) { return e && source_stream(e).Q == 1 ? source_stream(e).P : 0; }
 
 int rdsp_engine_set_source_rate(rdsp_engine_t *e, int P, int Q, float gain) {
-  if (!e || !rdsp_tune::rate_reduce(P, Q) || !(gain > 0.0f) || !std::isfinite(gain)) {
+  if (!e || !rdsp_tune::rate_reduce(P, Q) || !gain_ok(gain)) {
     rdsp_set_error("rdsp_engine_set_source_rate: bad argument (in lowest terms 1 <= Q <= %d and Q <= P <= %d Q: P %d, Q %d; gain %g must be "
                    "finite and above 0)", rdsp_tune::RATE_MAX_Q, rdsp_tune::RATE_MAX_RATIO, P, Q, (double)gain);
     return RDSP_ERR_INVALID;
   }
-  if (!e->src) {
-    rdsp_set_error("rdsp_engine_set_source_rate: no sources; call rdsp_engine_set_sources first");
-    return RDSP_ERR_NOT_READY;
+  if (no_sources(e, "rdsp_engine_set_source_rate")) return RDSP_ERR_NOT_READY;
+  if (Q == 1) return rdsp_engine_set_source_decimation(e, P, gain); /* an integer multiple: its checks and its texts */
+  SourceStream to;
+  to.P = P; to.Q = Q;
+  if (const int c = station_outside(e, to.band_hz()); c >= 0) {
+    rdsp_set_error("rdsp_engine_set_source_rate: channel %d is tuned to %g Hz, outside a source at 44100 x %d / %d Hz", c, e->station[(size_t)c], P, Q);
+    return RDSP_ERR_INVALID;
   }
-  if (Q == 1) return rdsp_engine_set_source_decimation(e, P, gain); /* an integer multiple: the decimating pass itself */
-  const double band = (rdsp_tune::TUNE_MAX_HZ * (double)P) / (double)Q;
-  for (size_t c = 0; c < e->station.size(); c++)
-    if (!(fabs(e->station[c]) < band)) {
-      rdsp_set_error("rdsp_engine_set_source_rate: channel %zu is tuned to %g Hz, outside a source at 44100 x %d / %d Hz", c, e->station[c], P, Q);
-      return RDSP_ERR_INVALID;
-    }
-  hipError_t err = hipSetDevice(e->device);
-  if (err == hipSuccess) err = hipDeviceSynchronize(); /* queued passes read the taps and the histories */
-  if (err == hipSuccess) err = rate_setup(e, P, Q, gain, e->n_sources);
-  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_set_source_rate", err);
+  return configure_sources(e, "rdsp_engine_set_source_rate", P, Q, gain, e->src->st.format);
 }
 int rdsp_engine_source_rate(const rdsp_engine_t *e, int *P, int *Q) {
   if (!e || !P || !Q) return RDSP_ERR_INVALID;
-  *P = e->rate ? e->rate_P : e->ddc_D;
-  *Q = e->rate ? e->rate_Q : 1;
+  *P = source_stream(e).P;
+  *Q = source_stream(e).Q;
   return RDSP_OK;
 }
 size_t rdsp_engine_source_pairs(const rdsp_engine_t *e, int n_blocks) {
-  if (!e || n_blocks < 0) return 0;
-  const uint32_t n_out = (uint32_t)n_blocks * BS;
-  return e->rate ? (size_t)rdsp_tune::rate_pairs(e->frac, e->rate_P, e->rate_Q, n_out) : (size_t)n_out * (size_t)e->ddc_D;
+  return e && n_blocks >= 0 ? source_stream(e).pairs((uint32_t)n_blocks * BS) : 0;
 }
 int rdsp_engine_rate_of_hz(double fs_hz, int *P, int *Q) {
   const double top = (double)rdsp_tune::RATE_MAX_RATIO * rdsp_tune::TUNE_FS;
@@ -642,7 +473,7 @@ int rdsp_engine_rate_of_hz(double fs_hz, int *P, int *Q) {
   return RDSP_OK;
 }
 int rdsp_engine_rate_taps(int P, int Q, float gain, float *out) {
-  if (!rdsp_tune::rate_reduce(P, Q) || !(gain > 0.0f) || !std::isfinite(gain) || !out) {
+  if (!rdsp_tune::rate_reduce(P, Q) || !gain_ok(gain) || !out) {
     rdsp_set_error("rdsp_engine_rate_taps: bad argument (in lowest terms 1 <= Q <= %d and Q <= P <= %d Q: P %d, Q %d; gain %g)",
                    rdsp_tune::RATE_MAX_Q, rdsp_tune::RATE_MAX_RATIO, P, Q, (double)gain);
     return RDSP_ERR_INVALID;
@@ -651,7 +482,7 @@ int rdsp_engine_rate_taps(int P, int Q, float gain, float *out) {
   return RDSP_OK;
 }
 int rdsp_engine_ddc_taps(int D, float gain, float *out) {
-  if (D < 1 || D > rdsp_tune::DDC_MAX_D || !(gain > 0.0f) || !std::isfinite(gain) || !out) {
+  if (D < 1 || D > rdsp_tune::DDC_MAX_D || !gain_ok(gain) || !out) {
     rdsp_set_error("rdsp_engine_ddc_taps: bad argument (D %d of 1 .. %d, gain %g)", D, rdsp_tune::DDC_MAX_D, (double)gain);
     return RDSP_ERR_INVALID;
   }
@@ -664,14 +495,15 @@ int rdsp_engine_tune(rdsp_engine_t *e, int first_channel, int n_channels, const 
     rdsp_set_error("rdsp_engine_tune: bad argument (channels %d .. %d of %d)", first_channel, first_channel + n_channels - 1, e ? e->n_channels : 0);
     return RDSP_ERR_INVALID;
   }
+  const double band = source_stream(e).band_hz();
   for (int k = 0; k < n_channels; k++)
-    if (!(fabs(station_hz[k]) < source_band_hz(e))) {
-      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], source_band_hz(e));
+    if (!(fabs(station_hz[k]) < band)) {
+      rdsp_set_error("rdsp_engine_tune: channel %d: station %g Hz; |f| must be below %g Hz", first_channel + k, station_hz[k], band);
       return RDSP_ERR_INVALID;
     }
   if (e->station.empty()) e->station.assign((size_t)e->n_channels, 0.0);
   std::copy(station_hz, station_hz + n_channels, e->station.begin() + first_channel);
-  e->dphi_stale = true;
+  if (e->src) e->src->steps_changed();
   return RDSP_OK;
 }
 
@@ -683,77 +515,38 @@ int rdsp_engine_set_source_format(rdsp_engine_t *e, int format) {
     rdsp_set_error("rdsp_engine_set_source_format: bad argument (format %d of RDSP_SRC_S16 = 0, U8 = 1, S8 = 2, F32 = 3)", format);
     return RDSP_ERR_INVALID;
   }
-  if (!e->src) {
-    rdsp_set_error("rdsp_engine_set_source_format: no sources; call rdsp_engine_set_sources first");
-    return RDSP_ERR_NOT_READY;
-  }
-  if (format == e->src_format) return RDSP_OK;
-  hipError_t err = hipSetDevice(e->device);
-  if (err == hipSuccess) err = hipDeviceSynchronize(); /* queued passes read the histories */
-  DevBuf<uint32_t> *hist = e->rate ? &e->rate->hist : e->ddc ? &e->ddc->hist : nullptr;
-  DevBuf<uint32_t> fresh; /* the object keeps its format unless the new histories exist */
-  if (err == hipSuccess && hist) {
-    const size_t keep = e->rate ? (size_t)rdsp_tune::rate_tb(e->rate_P, e->rate_Q) : (size_t)rdsp_tune::DDC_HIST_PER_PHASE * e->ddc_D;
-    const size_t words = (size_t)e->n_sources * keep * (size_t)rdsp_tune::src_hist_words(format);
-    err = fresh.alloc(words);
-    if (err == hipSuccess) err = hipMemset(fresh, 0, words * 4);
-  }
-  if (err != hipSuccess) return engine_fail("rdsp_engine_set_source_format", err);
-  if (hist) std::swap(hist->p, fresh.p);
-  e->src_format = format;
-  e->frac = 0;
-  return RDSP_OK;
+  if (no_sources(e, "rdsp_engine_set_source_format")) return RDSP_ERR_NOT_READY;
+  const EngFrontEnd &f = *e->src;
+  return format == f.st.format ? RDSP_OK : configure_sources(e, "rdsp_engine_set_source_format", f.st.P, f.st.Q, f.gain, format);
 }
-int rdsp_engine_source_format(const rdsp_engine_t *e) { return e ? e->src_format : RDSP_ERR_INVALID; }
+int rdsp_engine_source_format(const rdsp_engine_t *e) { return e ? source_stream(e).format : RDSP_ERR_INVALID; }
 
 namespace {
 /* both entry points; who: the one that was called, for the error text */
 int update_source_rows(const char *who, rdsp_engine_t *e, const void *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
-  const size_t pair = e ? (size_t)rdsp_tune::src_pair_bytes(e->src_format) : 4;
-  if (e && e->rate) { /* a rational rate: rows of rdsp_engine_source_pairs pairs, aligned to a pair */
-    if (!d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < rdsp_engine_source_pairs(e, n_blocks) || (uintptr_t)d_src % pair != 0 ||
-        out_stride < (size_t)n_blocks * BS) {
+  const SourceStream st = source_stream(e);
+  const size_t pair = (size_t)rdsp_tune::src_pair_bytes(st.format), need = st.pairs((uint32_t)std::max(n_blocks, 0) * BS);
+  const bool bad = !e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < need || out_stride < (size_t)n_blocks * BS;
+  if (st.Q > 1) { /* a rational rate: rows of rdsp_engine_source_pairs pairs, aligned to a pair */
+    if (bad || (uintptr_t)d_src % pair != 0) {
       rdsp_set_error("%s: bad argument (n_blocks %d of at most %d; source rows %zu-byte aligned and at least "
-                     "rdsp_engine_source_pairs = %zu pairs long at 44100 x %d / %d Hz)", who, n_blocks, e->max_blocks, pair, rdsp_engine_source_pairs(e, std::max(n_blocks, 0)), e->rate_P, e->rate_Q);
+                     "rdsp_engine_source_pairs = %zu pairs long at 44100 x %d / %d Hz)", who, n_blocks, e->max_blocks, pair, need, st.P, st.Q);
       return RDSP_ERR_INVALID;
     }
-  } else if (!e || !d_src || !d_lr || n_blocks < 0 || n_blocks > e->max_blocks || src_stride < (size_t)n_blocks * BS * (size_t)e->ddc_D || (src_stride * pair) % 16 != 0 ||
-      ((uintptr_t)d_src & 15) != 0 || out_stride < (size_t)n_blocks * BS) {
+  } else if (bad || (src_stride * pair) % 16 != 0 || ((uintptr_t)d_src & 15) != 0) {
     rdsp_set_error("%s: bad argument (n_blocks %d of at most %d; source rows 16-byte aligned, a multiple of 16 "
-                   "bytes apart and at least n_blocks * 128 * D pairs long, D = %d)", who, n_blocks, e ? e->max_blocks : 0, e ? e->ddc_D : 0);
+                   "bytes apart and at least n_blocks * 128 * D pairs long, D = %d)", who, n_blocks, e ? e->max_blocks : 0, e ? st.P : 0);
     return RDSP_ERR_INVALID;
   }
-  if (!e->src) {
-    rdsp_set_error("%s: no sources; call rdsp_engine_set_sources first", who);
-    return RDSP_ERR_NOT_READY;
-  }
+  if (no_sources(e, who)) return RDSP_ERR_NOT_READY;
   if (!e->tables) {
     rdsp_set_error("%s: the engine's coefficient tables are not loaded (rdsp_engine_load_tables)", who);
     return RDSP_ERR_NOT_READY;
   }
   if (n_blocks == 0) return RDSP_OK;
-  hipStream_t s = (hipStream_t)stream;
   hipError_t err = hipSetDevice(e->device);
-  if (err == hipSuccess) err = upload_dphi(e, s);
-  if (err != hipSuccess) return engine_fail(who, err);
-  if (e->rate) { /* tune, low-pass and resample by Q / P: rdsp_engine_rate.hip */
-    auto q = source_pass<rdsp_tune::RateParams>(e, d_src, src_stride);
-    q.hist = e->rate->hist; q.hb = e->rate->hb; q.sched = e->rate->sched; q.wg_first = e->src->rate_wg_first; q.wg_count = e->src->rate_wg_count;
-    q.n_sources = e->n_sources; q.n_wg = e->n_rate_wg; q.P = e->rate_P; q.Q = e->rate_Q;
-    q.frac = e->frac; q.n_out = (uint32_t)n_blocks * BS; q.pairs = (uint32_t)rdsp_engine_source_pairs(e, n_blocks);
-    err = rdsp_engine_rate_launch(q, s);
-    if (err == hipSuccess) e->frac = rdsp_tune::rate_frac_after(e->frac, e->rate_P, e->rate_Q, q.n_out);
-  } else if (e->ddc_D > 1) { /* tune, low-pass and decimate: rdsp_engine_ddc.hip */
-    auto q = source_pass<rdsp_tune::DdcParams>(e, d_src, src_stride);
-    q.hist = e->ddc->hist; q.h = e->ddc->h; q.g = e->ddc->g; q.wg_first = e->src->wg_first; q.wg_count = e->src->wg_count;
-    q.n_sources = e->n_sources; q.n_wg = e->n_wg; q.D = e->ddc_D; q.n_out = (uint32_t)n_blocks * BS;
-    err = rdsp_engine_ddc_launch(q, s);
-  } else { /* tune: rdsp_engine_tune.hip */
-    auto p = source_pass<rdsp_tune::TuneParams>(e, d_src, src_stride);
-    p.cpw = std::min(rdsp_tune::TUNE_MAX_CPW, std::max(1, e->n_channels / 1024)); /* about a thousand workgroups or more */
-    p.n_samples = (uint32_t)n_blocks * BS;
-    err = rdsp_engine_tune_launch(p, s);
-  }
+  const SourceTuning tuning{e->first, [e](size_t g) { return e->grp[g].tuning_offset; }, e->station};
+  if (err == hipSuccess) err = e->src->run(d_src, src_stride, n_blocks, tuning, (hipStream_t)stream);
   if (err != hipSuccess) return engine_fail(who, err);
   return rdsp_engine_update(e, (const int16_t *)e->src->tuned.p, (size_t)e->max_blocks * BS, n_blocks, d_lr, out_stride, stream);
 }
@@ -765,8 +558,8 @@ int rdsp_engine_update_source_samples(rdsp_engine_t *e, const void *d_src, size_
 }
 
 int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t src_stride, int n_blocks, int16_t *d_lr, size_t out_stride, void *stream) {
-  if (e && e->src_format != rdsp_tune::SRC_S16) {
-    rdsp_set_error("rdsp_engine_update_sources: the engine's source format is %d, not int16; call rdsp_engine_update_source_samples", e->src_format);
+  if (source_stream(e).format != rdsp_tune::SRC_S16) {
+    rdsp_set_error("rdsp_engine_update_sources: the engine's source format is %d, not int16; call rdsp_engine_update_source_samples", source_stream(e).format);
     return RDSP_ERR_INVALID;
   }
   return update_source_rows("rdsp_engine_update_sources", e, d_src, src_stride, n_blocks, d_lr, out_stride, stream);

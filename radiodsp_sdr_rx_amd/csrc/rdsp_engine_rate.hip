@@ -5,10 +5,11 @@
  * of the arithmetic are rdsp_tune.h's (rate_step, rate_u, ddc_mac, rate_phase, ddc_rot); Q = 1 is rdsp_engine_ddc.hip, which
  * this file does not touch.
  *
- * Three kernels a call, in stream order:
+ * Two kernels a call, in stream order:
  *   rdsp_engine_rate_sched_kernel   sched[i] = {n(i), r(i)}, the 64-bit divisions of the schedule, once per output;
  *   rdsp_engine_rate_kernel         the filter bank (below);
- *   rdsp_engine_rate_finish_kernel  the last Tb pairs of every source row -> the engine's history, phases += pairs dphi.
+ * after them the engine runs the finish kernel of both filter-bank passes (rdsp_engine_tune.hip): the last Tb pairs of every
+ * source row -> the engine's history, phases += pairs dphi.
  *
  * The filter bank.  Consecutive outputs use different branches and their windows start Dc or Dc - 1 pairs apart, so a lane
  * cannot be an output as in the decimating pass.  What IS uniform is everything that does not depend on the receiver: the
@@ -27,8 +28,6 @@
  * Compiled with -ffp-contract=off: every fused operation is an fmaf.
  */
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
 
 #include "rdsp_tune.h"
 
@@ -135,39 +134,15 @@ __global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_kernel(RatePara
   }
 }
 
-template <int F>
-__global__ __launch_bounds__(RATE_THREADS) void rdsp_engine_rate_finish_kernel(RateParams p) {
-  const uint32_t keep = (uint32_t)rate_tb(p.P, p.Q); /* pairs >= 128 P / Q - 1 > 16 Dc: the row alone holds them */
-  const uint32_t i = blockIdx.x * RATE_THREADS + threadIdx.x;
-  if (i < (uint32_t)p.n_sources * keep) {
-    const uint32_t s = i / keep, t = i - s * keep;
-    const void *row = src_at<F>(p.src, (size_t)s * p.src_stride);
-    if constexpr (F == SRC_S16) ((uint32_t *)p.hist)[i] = ((const uint32_t *)row)[(p.pairs - keep) + t];
-    else ((float2 *)p.hist)[i] = src_pair<F>(row, (long long)(p.pairs - keep) + t);
-  }
-  if (i < (uint32_t)p.n_channels) p.phase[i] = tune_phase(p.phase[i], p.dphi[i], p.pairs);
-}
-
-template <int F>
-void rate_launch(const RateParams &p, size_t grid, size_t n_fin, hipStream_t s) {
-  hipLaunchKernelGGL(rdsp_engine_rate_kernel<F>, dim3((unsigned)grid), dim3(RATE_THREADS), 0, s, p);
-  hipLaunchKernelGGL(rdsp_engine_rate_finish_kernel<F>, dim3((unsigned)((n_fin + RATE_THREADS - 1) / RATE_THREADS)), dim3(RATE_THREADS), 0, s, p);
-}
 }  // namespace
 
 hipError_t rdsp_engine_rate_launch(const RateParams &p, hipStream_t s) {
   /* the bank's vector stores: 16 outputs of a receiver are 64 bytes, whole in its row */
   if (p.n_out % RATE_TILE != 0 || p.dst_stride % 4 != 0 || ((uintptr_t)p.dst & 15) != 0 || p.pairs < (uint32_t)rate_tb(p.P, p.Q)) return hipErrorInvalidValue;
-  if (p.format < 0 || p.format >= SRC_FORMATS) return hipErrorInvalidValue;
   const size_t grid = (size_t)p.n_wg * (p.n_out / RATE_TILE);
   if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rdsp_engine_rate_sched_kernel, dim3((p.n_out + RATE_THREADS - 1) / RATE_THREADS), dim3(RATE_THREADS), 0, s, p);
-  const size_t n_fin = std::max((size_t)p.n_sources * (size_t)rate_tb(p.P, p.Q), (size_t)p.n_channels);
-  switch (p.format) {
-    case SRC_S16: rate_launch<SRC_S16>(p, grid, n_fin, s); break;
-    case SRC_U8: rate_launch<SRC_U8>(p, grid, n_fin, s); break;
-    case SRC_S8: rate_launch<SRC_S8>(p, grid, n_fin, s); break;
-    default: rate_launch<SRC_F32>(p, grid, n_fin, s); break;
-  }
-  return hipGetLastError();
+  return dispatch_format(p.format, [&](auto f) {
+    hipLaunchKernelGGL(rdsp_engine_rate_sched_kernel, dim3((p.n_out + RATE_THREADS - 1) / RATE_THREADS), dim3(RATE_THREADS), 0, s, p);
+    hipLaunchKernelGGL(rdsp_engine_rate_kernel<decltype(f)::value>, dim3((unsigned)grid), dim3(RATE_THREADS), 0, s, p);
+  });
 }

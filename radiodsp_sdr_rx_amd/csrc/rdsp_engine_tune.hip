@@ -9,9 +9,16 @@
  * source rows is a template parameter, rdsp_tune.h's src_value the one conversion), phases in closed form ph0 + t dphi.  The phase
  * words are read before the one barrier and written after the last row, by the lanes that read them.
  *
+ * The file also holds what the two filter-bank passes (rdsp_engine_ddc.hip, rdsp_engine_rate.hip) do after their banks, ONE
+ * kernel for both: rdsp_engine_source_finish_kernel copies the last `keep` pairs of every source row into the engine's
+ * history and advances every receiver's phase by pairs dphi.  It lives here because this is the pass file that belongs to no
+ * rate: the host's front end (rdsp_engine_sources.hip) stays free of device code, and neither bank's file owns the other's tail.
+ *
  * Compiled with -ffp-contract=off: every fused operation is an fmaf.
  */
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "rdsp_tune.h"
 
@@ -74,16 +81,33 @@ __global__ __launch_bounds__(TUNE_THREADS) void rdsp_engine_tune_kernel(TunePara
   if (tid < p.cpw && ch_of[tid] >= 0) p.phase[ch_of[tid]] = tune_phase(ph0_of[tid], dphi_of[tid], p.n_samples);
 }
 
+/* pairs >= keep: a call is at least 128 outputs, 128 D > 15 D pairs and 128 P / Q - 1 > 16 ceil(P / Q) (the launchers check) */
+template <int F>
+__global__ __launch_bounds__(TUNE_THREADS) void rdsp_engine_source_finish_kernel(SourceParams p, void *hist, uint32_t keep, uint32_t pairs, int n_sources) {
+  const uint32_t i = blockIdx.x * TUNE_THREADS + threadIdx.x;
+  if (i < (uint32_t)n_sources * keep) {
+    const uint32_t s = i / keep, t = i - s * keep;
+    const void *row = src_at<F>(p.src, (size_t)s * p.src_stride);
+    if constexpr (F == SRC_S16) ((uint32_t *)hist)[i] = ((const uint32_t *)row)[(pairs - keep) + t];
+    else ((float2 *)hist)[i] = src_pair<F>(row, (long long)(pairs - keep) + t);
+  }
+  if (i < (uint32_t)p.n_channels) p.phase[i] = tune_phase(p.phase[i], p.dphi[i], pairs);
+}
+
 }  // namespace
 
 hipError_t rdsp_engine_tune_launch(const TuneParams &p, hipStream_t s) {
   const unsigned grid = (unsigned)((p.n_channels + p.cpw - 1) / p.cpw);
-  switch (p.format) {
-    case SRC_S16: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_S16>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
-    case SRC_U8: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_U8>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
-    case SRC_S8: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_S8>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
-    case SRC_F32: hipLaunchKernelGGL(rdsp_engine_tune_kernel<SRC_F32>, dim3(grid), dim3(TUNE_THREADS), 0, s, p); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_format(p.format, [&](auto f) {
+    hipLaunchKernelGGL(rdsp_engine_tune_kernel<decltype(f)::value>, dim3(grid), dim3(TUNE_THREADS), 0, s, p);
+  });
+}
+
+hipError_t rdsp_engine_source_finish_launch(const SourceParams &p, void *hist, uint32_t keep, uint32_t pairs, int n_sources, hipStream_t s) {
+  if (keep == 0 || pairs < keep || !hist) return hipErrorInvalidValue;
+  const size_t n = std::max((size_t)n_sources * keep, (size_t)p.n_channels);
+  return dispatch_format(p.format, [&](auto f) {
+    hipLaunchKernelGGL(rdsp_engine_source_finish_kernel<decltype(f)::value>, dim3((unsigned)((n + TUNE_THREADS - 1) / TUNE_THREADS)), dim3(TUNE_THREADS), 0, s,
+                       p, hist, keep, pairs, n_sources);
+  });
 }

@@ -20,6 +20,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #ifndef RDSP_HD
 #define RDSP_HD __host__ __device__ __forceinline__
 #endif
@@ -116,15 +118,27 @@ RDSP_HD float2 src_or_hist(const void *row, const void *hist, I i, int keep) {
   }
 }
 
-/* one int16 pair (a word I | Q << 16) times (c + j s), rotated as the engine's shifter rotates */
-RDSP_HD uint32_t tune_pair(uint32_t w, float2 cs) {
-  const float i = src_value(SRC_S16, w & 0xffffu), q = src_value(SRC_S16, w >> 16);
-  const float ir = fmaf(i, cs.x, -(q * cs.y));
-  const float qr = fmaf(q, cs.x, i * cs.y);
-  return tune_q16(ir) | tune_q16(qr) << 16;
+/* fmt in f's argument as a compile-time constant (an std::integral_constant): the one switch of the launchers */
+template <typename Fn>
+inline hipError_t dispatch_format(int fmt, Fn f) {
+  switch (fmt) {
+    case SRC_S16: f(std::integral_constant<int, SRC_S16>()); break;
+    case SRC_U8: f(std::integral_constant<int, SRC_U8>()); break;
+    case SRC_S8: f(std::integral_constant<int, SRC_S8>()); break;
+    case SRC_F32: f(std::integral_constant<int, SRC_F32>()); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
-/* the same on a pair of values */
-RDSP_HD uint32_t tune_pair(float2 x, float2 cs) {
+
+/* a pair as values: of an int16 word I | Q << 16, or the values themselves.  What follows takes either through it. */
+RDSP_HD float2 pair_value(uint32_t w) { return make_float2(src_value(SRC_S16, w & 0xffffu), src_value(SRC_S16, w >> 16)); }
+RDSP_HD float2 pair_value(float2 x) { return x; }
+
+/* one pair (a word or values) times (c + j s), rotated as the engine's shifter rotates */
+template <typename X>
+RDSP_HD uint32_t tune_pair(X pair, float2 cs) {
+  const float2 x = pair_value(pair);
   const float ir = fmaf(x.x, cs.x, -(x.y * cs.y));
   const float qr = fmaf(x.y, cs.x, x.x * cs.y);
   return tune_q16(ir) | tune_q16(qr) << 16;
@@ -134,22 +148,44 @@ RDSP_HD uint32_t tune_pair(float2 x, float2 cs) {
 RDSP_HD uint32_t tune_phase(uint32_t ph0, uint32_t dphi, uint32_t t) { return ph0 + t * dphi; }
 
 /* host only: the step per source sample that moves a station at station_hz (from the stream's centre) to the engine's IF, the
- * source at D x 44 100 Hz (rdsp_engine_set_source_decimation below; D = 1 divides by TUNE_FS itself) */
-inline uint32_t ddc_dphi(float tuning_offset, double station_hz, int D) {
-  return (uint32_t)(unsigned long long)llround(((double)tuning_offset - station_hz) * 4294967296.0 / ((double)D * TUNE_FS));
+ * source at 44 100 P / Q Hz (Q = 1: P x 44 100 Hz, the division by 1.0 exact; P = Q = 1 divides by TUNE_FS itself) */
+inline uint32_t rate_dphi(float tuning_offset, double station_hz, int P, int Q) {
+  return (uint32_t)(unsigned long long)llround(((double)tuning_offset - station_hz) * 4294967296.0 / (((double)P * TUNE_FS) / (double)Q));
 }
-inline uint32_t tune_dphi(float tuning_offset, double station_hz) { return ddc_dphi(tuning_offset, station_hz, 1); }
+inline uint32_t ddc_dphi(float tuning_offset, double station_hz, int D) { return rate_dphi(tuning_offset, station_hz, D, 1); }
+inline uint32_t tune_dphi(float tuning_offset, double station_hz) { return rate_dphi(tuning_offset, station_hz, 1, 1); }
 
-/* the pass's arguments: receivers are visited in `order` (grouped by source); cpw receivers per workgroup */
-struct TuneParams {
-  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs */
+/* what the arguments of all three passes share.  Receivers are visited in `order` (grouped by source).  The order of the
+ * fields here and in the three structs that extend it decides how the compiler groups the kernels' scalar argument loads: with
+ * this one the tuning, the decimating and the int16 polyphase kernel keep the registers and instruction counts they had with a
+ * struct each (docs/engine.md). */
+struct SourceParams {
+  int n_channels;
+  int format;                               /* SRC_* */
+  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs; rows pair-aligned */
   uint32_t *dst; size_t dst_stride;         /* [ch][t] */
   const int *order, *source_of;             /* [n_channels] */
   uint32_t *phase; const uint32_t *dphi;    /* [n_channels] */
   const float4 *tab;                        /* [TUNE_N] */
-  int n_channels, cpw;
+};
+/* host only: the workgroups of a filter-bank pass: runs of at most `max` receivers of ONE source that are neighbours in `order`
+ * (n receivers).  first[w], count[w] (room for n each) describe run w; returns how many there are. */
+inline int source_runs(const int *order, const int *source_of, int n, int max, int *first, int *count) {
+  int runs = 0;
+  for (int i = 0; i < n;) {
+    int j = i + 1;
+    while (j < n && j - i < max && source_of[order[j]] == source_of[order[i]]) j++;
+    first[runs] = i;
+    count[runs++] = j - i;
+    i = j;
+  }
+  return runs;
+}
+
+/* the tuning pass's arguments: cpw receivers per workgroup */
+struct TuneParams : SourceParams {
+  int cpw;
   uint32_t n_samples;                       /* a multiple of 8 */
-  int format;                               /* SRC_* */
 };
 constexpr int TUNE_THREADS = 256;
 constexpr int TUNE_MAX_CPW = 8;
@@ -196,23 +232,29 @@ inline double ddc_i0(double x) {
   }
   return sum;
 }
-/* host only: the prototype, T = 16 D taps: a sinc with its cutoff at the output's Nyquist frequency (22 050 Hz) under a
- * Kaiser window of beta = 9, normalised to sum 1 (summed in tap order), times gain, rounded to float.  Symmetric: every
- * term is a function of |2 k - (T - 1)|. */
 constexpr double DDC_KAISER_BETA = 9.0;
-inline void ddc_taps(int D, double gain, float *out) {
-  const int T = DDC_TAPS_PER_PHASE * D;
-  double h[DDC_TAPS_PER_PHASE * DDC_MAX_D], sum = 0.0;
+RDSP_HD int rate_dc(int P, int Q) { return (P + Q - 1) / Q; }
+RDSP_HD int rate_tb(int P, int Q) { return DDC_TAPS_PER_PHASE * rate_dc(P, Q); }
+/* host only, libm-free: the prototype of a source at 44 100 P / Q Hz (the polyphase pass below; Q = 1: this pass, P = D), Tp = Tb Q
+ * taps at the rate 44 100 P: a sinc with its cutoff at the output's Nyquist frequency (22 050 Hz) under a Kaiser window of
+ * beta = 9, normalised to sum 1 (summed in tap order), times Q gain (every branch then sums to about gain), rounded to float.
+ * Symmetric: every term is a function of |2 i - (Tp - 1)|.  Up to 451 584 taps: the doubles are taken from the heap. */
+inline void rate_taps(int P, int Q, double gain, float *out) {
+  const int Tp = rate_tb(P, Q) * Q;
+  double *h = new double[(size_t)Tp], sum = 0.0;
   const double i0b = ddc_i0(DDC_KAISER_BETA);
-  for (int k = 0; k < T; k++) {
-    const int q = 2 * k - (T - 1) < 0 ? (T - 1) - 2 * k : 2 * k - (T - 1); /* odd: the sinc's argument is q / (2 D), never 0 */
-    const double u = (3.141592653589793 * (double)q) / (2.0 * (double)D);
-    const double rho = (double)q / (double)(T - 1);
-    h[k] = (ddc_sin_halfpi(q, D) / u) * (ddc_i0(DDC_KAISER_BETA * sqrt(1.0 - rho * rho)) / i0b);
+  for (int i = 0; i < Tp; i++) {
+    const int q = 2 * i - (Tp - 1) < 0 ? (Tp - 1) - 2 * i : 2 * i - (Tp - 1); /* odd: the sinc's argument is q / (2 P), never 0 */
+    const double u = (3.141592653589793 * (double)q) / (2.0 * (double)P);
+    const double rho = (double)q / (double)(Tp - 1);
+    h[i] = (ddc_sin_halfpi(q, P) / u) * (ddc_i0(DDC_KAISER_BETA * sqrt(1.0 - rho * rho)) / i0b);
   }
-  for (int k = 0; k < T; k++) sum += h[k];
-  for (int k = 0; k < T; k++) out[k] = (float)((h[k] / sum) * gain);
+  for (int i = 0; i < Tp; i++) sum += h[i];
+  const double scale = (double)Q * gain;
+  for (int i = 0; i < Tp; i++) out[i] = (float)((h[i] / sum) * scale);
+  delete[] h;
 }
+inline void ddc_taps(int D, double gain, float *out) { rate_taps(D, 1, gain, out); }
 
 /* tap k of a receiver: the prototype's tap translated onto the station */
 RDSP_HD float2 ddc_tap(const float4 *tab, float h, uint32_t dphi, uint32_t k) {
@@ -232,19 +274,15 @@ RDSP_HD uint32_t ddc_rot(float re, float im, float2 cs) {
   const float qr = fmaf(im, cs.x, re * cs.y);
   return tune_q16(ir) | tune_q16(qr) << 16;
 }
-/* one output: newest points at x[(m + 1) D - 1] (the T - 1 words before it are read), g at the receiver's T taps */
-RDSP_HD uint32_t ddc_output(const float2 *g, int T, const uint32_t *newest, float2 cs) {
+/* one output: newest points at x[(m + 1) D - 1] (the T - 1 pairs before it are read; words, or the values of src_pair of any
+ * format and of the history), g at the receiver's T taps */
+template <typename X>
+RDSP_HD uint32_t ddc_output(const float2 *g, int T, const X *newest, float2 cs) {
   float re = 0.0f, im = 0.0f;
   for (int k = 0; k < T; k++) {
-    const float2 x = src_pair<SRC_S16>(newest, -k);
+    const float2 x = pair_value(newest[-k]);
     ddc_mac(re, im, g[k], x.x, x.y);
   }
-  return ddc_rot(re, im, cs);
-}
-/* the same on values (src_pair of any format, or the history's) */
-RDSP_HD uint32_t ddc_output(const float2 *g, int T, const float2 *newest, float2 cs) {
-  float re = 0.0f, im = 0.0f;
-  for (int k = 0; k < T; k++) ddc_mac(re, im, g[k], newest[-k].x, newest[-k].y);
   return ddc_rot(re, im, cs);
 }
 
@@ -253,20 +291,13 @@ RDSP_HD uint32_t ddc_output(const float2 *g, int T, const float2 *newest, float2
 constexpr int DDC_THREADS = 256;
 constexpr int DDC_C = 4;                          /* receivers per wave, a register block */
 constexpr int DDC_RPW = DDC_C * (DDC_THREADS / 64); /* receivers per workgroup */
-struct DdcParams {
-  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs, n_out * D per row */
-  void *hist;                               /* [source][15 D]: the pairs before the call (S16: words; otherwise float2 values);
-                                               rewritten after the pass */
-  uint32_t *dst; size_t dst_stride;         /* [ch][m] */
-  const int *order, *source_of;             /* [n_channels] */
+struct DdcParams : SourceParams {           /* n_out * D pairs per source row */
+  const void *hist;                         /* [source][15 D]: the pairs before the call (S16: words; otherwise float2 values) */
   const int *wg_first, *wg_count;           /* [n_wg] */
-  uint32_t *phase; const uint32_t *dphi;    /* [n_channels] */
-  const float4 *tab;                        /* [TUNE_N] */
   const float *h;                           /* [16 D] */
   float2 *g;                                /* [n_channels][16 D], written by the pass's first kernel */
-  int n_channels, n_sources, n_wg, D;
+  int n_wg, D;
   uint32_t n_out;                           /* a multiple of 128 */
-  int format;                               /* SRC_* */
 };
 
 /* ---- sources at 44 100 P / Q Hz: tune, low-pass and change the rate by Q / P in one polyphase pass (rdsp_engine_set_source_rate) --
@@ -285,8 +316,6 @@ struct DdcParams {
 constexpr int RATE_MAX_Q = 441;
 constexpr int RATE_MAX_RATIO = DDC_MAX_D; /* P <= 64 Q */
 
-RDSP_HD int rate_dc(int P, int Q) { return (P + Q - 1) / Q; }
-RDSP_HD int rate_tb(int P, int Q) { return DDC_TAPS_PER_PHASE * rate_dc(P, Q); }
 struct RateStep { int n, r; }; /* newest pair's local index, branch */
 RDSP_HD RateStep rate_step(uint32_t frac, int P, int Q, uint32_t i) {
   const uint64_t t = (uint64_t)frac + ((uint64_t)i + 1u) * (uint64_t)P;
@@ -307,46 +336,18 @@ inline bool rate_reduce(int &P, int &Q) {
   P /= a; Q /= a;
   return Q <= RATE_MAX_Q && P >= Q && (long long)P <= (long long)RATE_MAX_RATIO * Q;
 }
-/* host only: the step per source sample of a source at 44 100 P / Q Hz; Q = 1 gives ddc_dphi(..., P) */
-inline uint32_t rate_dphi(float tuning_offset, double station_hz, int P, int Q) {
-  return (uint32_t)(unsigned long long)llround(((double)tuning_offset - station_hz) * 4294967296.0 / (((double)P * TUNE_FS) / (double)Q));
-}
-/* host only, libm-free: the prototype, ddc_taps at the rate 44 100 P with Tp = Tb Q taps (cutoff 22 050 Hz, Kaiser beta 9),
- * normalised to sum 1 (summed in tap order), times Q gain: every branch then sums to about gain.  Q = 1 gives ddc_taps(P)
- * bit for bit.  Up to 451 584 taps: the doubles are taken from the heap. */
-inline void rate_taps(int P, int Q, double gain, float *out) {
-  const int Tp = rate_tb(P, Q) * Q;
-  double *h = new double[(size_t)Tp], sum = 0.0;
-  const double i0b = ddc_i0(DDC_KAISER_BETA);
-  for (int i = 0; i < Tp; i++) {
-    const int q = 2 * i - (Tp - 1) < 0 ? (Tp - 1) - 2 * i : 2 * i - (Tp - 1);
-    const double u = (3.141592653589793 * (double)q) / (2.0 * (double)P);
-    const double rho = (double)q / (double)(Tp - 1);
-    h[i] = (ddc_sin_halfpi(q, P) / u) * (ddc_i0(DDC_KAISER_BETA * sqrt(1.0 - rho * rho)) / i0b);
-  }
-  for (int i = 0; i < Tp; i++) sum += h[i];
-  const double scale = (double)Q * gain;
-  for (int i = 0; i < Tp; i++) out[i] = (float)((h[i] / sum) * scale);
-  delete[] h;
-}
 /* the tap on the sample: two rounded products */
-RDSP_HD float2 rate_u(float h, float2 x) { return make_float2(h * x.x, h * x.y); }
-RDSP_HD float2 rate_u(float h, uint32_t w) { return rate_u(h, make_float2(src_value(SRC_S16, w & 0xffffu), src_value(SRC_S16, w >> 16))); }
-/* one output: hb points at its branch's Tb taps, newest at x[n(i)] (the Tb - 1 words before it are read) */
-RDSP_HD uint32_t rate_output(const float4 *tab, const float *hb, int Tb, uint32_t dphi, const uint32_t *newest, float2 cs) {
+template <typename X>
+RDSP_HD float2 rate_u(float h, X pair) {
+  const float2 x = pair_value(pair);
+  return make_float2(h * x.x, h * x.y);
+}
+/* one output: hb points at its branch's Tb taps, newest at x[n(i)] (the Tb - 1 pairs before it are read; words or values) */
+template <typename X>
+RDSP_HD uint32_t rate_output(const float4 *tab, const float *hb, int Tb, uint32_t dphi, const X *newest, float2 cs) {
   float re = 0.0f, im = 0.0f;
   uint32_t ph = 0u;
   for (int j = 0; j < Tb; j++, ph -= dphi) { /* ph = 0 - j dphi */
-    const float2 u = rate_u(hb[j], newest[-j]);
-    ddc_mac(re, im, tune_phasor(tab, ph), u.x, u.y);
-  }
-  return ddc_rot(re, im, cs);
-}
-/* the same on values */
-RDSP_HD uint32_t rate_output(const float4 *tab, const float *hb, int Tb, uint32_t dphi, const float2 *newest, float2 cs) {
-  float re = 0.0f, im = 0.0f;
-  uint32_t ph = 0u;
-  for (int j = 0; j < Tb; j++, ph -= dphi) {
     const float2 u = rate_u(hb[j], newest[-j]);
     ddc_mac(re, im, tune_phasor(tab, ph), u.x, u.y);
   }
@@ -362,26 +363,27 @@ constexpr int RATE_O = 16;                /* outputs per wave; two waves of a wo
 constexpr int RATE_TILE = 2 * RATE_O;
 constexpr int RATE_RPW = 64 * RATE_C * 2; /* receivers per workgroup: two waves split them */
 constexpr int RATE_CHUNK = 128;           /* taps staged in LDS at a time */
-struct RateParams {
-  const void *src; size_t src_stride;       /* [source][t] pairs in `format`, the stride in pairs, `pairs` per row, rows pair-aligned */
-  void *hist;                               /* [source][Tb]: the pairs before the call (S16: words; otherwise float2 values);
-                                               rewritten after the pass */
-  uint32_t *dst; size_t dst_stride;         /* [ch][i] */
-  const int *order, *source_of;             /* [n_channels] */
-  const int *wg_first, *wg_count;           /* [n_wg] */
-  uint32_t *phase; const uint32_t *dphi;    /* [n_channels] */
-  const float4 *tab;                        /* [TUNE_N] */
+struct RateParams : SourceParams {          /* `pairs` pairs per source row */
   const float *hb;                          /* [Q][Tb] */
   RateStep *sched;                          /* [n_out], written by the pass's first kernel */
-  int n_channels, n_sources, n_wg, P, Q;
+  const void *hist;                         /* [source][Tb]: the pairs before the call (S16: words; otherwise float2 values) */
+  const int *wg_first, *wg_count;           /* [n_wg] */
+  int n_wg, P, Q;
   uint32_t frac, n_out, pairs;              /* n_out a multiple of 128 */
-  int format;                               /* SRC_* */
 };
+
+/* ---- what a source keeps between calls: its last rate_keep(P, Q) pairs, src_hist_words(format) words each.  Nothing else
+ * computes a history's size.  The pass follows from the rate: Q > 1 the polyphase pass, else P > 1 the decimating pass, else
+ * the tuning pass, which keeps nothing. */
+RDSP_HD int rate_keep(int P, int Q) { return Q > 1 ? rate_tb(P, Q) : P > 1 ? DDC_HIST_PER_PHASE * P : 0; }
 
 }  // namespace rdsp_tune
 
 hipError_t rdsp_engine_tune_launch(const rdsp_tune::TuneParams &p, hipStream_t s);
 hipError_t rdsp_engine_ddc_launch(const rdsp_tune::DdcParams &p, hipStream_t s);
 hipError_t rdsp_engine_rate_launch(const rdsp_tune::RateParams &p, hipStream_t s);
+/* after a filter bank, in its stream: the last `keep` of the call's `pairs` pairs of every source row -> hist (words for S16,
+ * float2 values otherwise), and every receiver's phase += pairs dphi */
+hipError_t rdsp_engine_source_finish_launch(const rdsp_tune::SourceParams &p, void *hist, uint32_t keep, uint32_t pairs, int n_sources, hipStream_t s);
 
 #endif
