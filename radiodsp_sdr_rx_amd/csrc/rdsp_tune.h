@@ -1,7 +1,7 @@
 /*
  * rdsp_tune.h -- the arithmetic of rdsp_engine_t's tuning pass (rdsp_engine_update_sources, include/rdsp.h): receiver
  * ch's row is its source row times e^{+j phi[n]}, phi a uint32 phase accumulator, requantized to int16.  Shared by the
- * kernel (rdsp_engine_tune.hip) and the host restatement of the tests (tests/host/host_tune_check.cpp), so both evaluate
+ * kernel (rdsp_engine_tune.hip) and the host restatement of the tests (tests/host/host_source_pass_check.cpp), so both evaluate
  * the same operations in the same order; both are compiled with -ffp-contract=off, and every fused operation is an fmaf.
  *
  * The phasor: a table of TUNE_N entries {cos, sin of 2 pi k / TUNE_N, and the steps to entry k + 1}, generated on the host
@@ -195,7 +195,7 @@ constexpr int TUNE_MAX_CPW = 8;
  *   y[m] = sat16(rne(e^{+j phi_m} * sum_{k < T} g_k x[(m + 1) D - 1 - k])),  g_k = h_k e^{-j 2 pi k dphi / 2^32},  T = 16 D,
  *   phi_{m + 1} = phi_m + D dphi,  dphi = round((TuningOffset - station) 2^32 / (D 44100)).
  * h is the prototype low-pass below (a design of this build).  The order of the operations, fixed here for the kernel
- * (rdsp_engine_ddc.hip) and for the host restatement (tests/host/host_ddc_check.cpp): g_k = (h_k c, h_k s), (c, s) =
+ * (rdsp_engine_ddc.hip) and for the host restatement (tests/host/host_source_pass_check.cpp): g_k = (h_k c, h_k s), (c, s) =
  * tune_phasor(-k dphi); ONE serial chain over k = 0 ... T - 1 per component, four fmaf a tap (ddc_mac); the rotation,
  * rounding and saturation of tune_pair (ddc_rot).  The chain has no tile, register block or call size in it, so neither
  * has the result. */

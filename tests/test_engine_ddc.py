@@ -2,199 +2,37 @@
 (rdsp_engine_set_source_decimation, include/rdsp.h; kernel csrc/rdsp_engine_ddc.hip, arithmetic csrc/rdsp_tune.h).
 
 `-m "not gpu"`: the prototype filter is the one specified (and the numpy evaluation of its formula, bit for bit: the
-library uses no libm function for it); the numpy restatement below is rdsp_tune.h's arithmetic compiled on the host
-(tests/host/host_ddc_check.cpp), bit for bit; the restated row stays within a derived bound of a float64 evaluation of the
-definition; it is a receiver (a station at +200 kHz comes out at the IF, what folds onto the IF is gone); it does not
-depend on how the stream is cut into calls.
+library uses no libm function for it); the numpy restatement (tests/engine_sources_model.py, at Q = 1) is rdsp_tune.h's
+arithmetic compiled on the host (tests/host/host_source_pass_check.cpp), bit for bit; the restated row stays within a derived
+bound of a float64 evaluation of the definition; it is a receiver (a station at +200 kHz comes out at the IF, what folds onto
+the IF is gone); it does not depend on how the stream is cut into calls.
 `-m gpu`: the audio of every receiver, bit for bit, against oracle_lib.OracleEngine run on the restated row, as
 tests/test_engine_tuning.py does for D = 1."""
 import ctypes
-import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_engine_tuning import HERE, M32, ROOT, TUNING_OFFSET, _Rx, _band, _engine, fmaf, phasor, tuned_row
-
-F32 = np.float32
-HIST = 15          # a source keeps its last 15 D pairs
-BETA = 9.0
-
-
-# ---- the restatement in numpy ---------------------------------------------------------------------------------------------
-def dphi_of(tuning_offset, station_hz, rate=44100.0):
-    """round((TuningOffset - station) 2^32 / rate), half away from zero, mod 2^32 (test_engine_tuning.dphi_of with a rate)"""
-    x = (float(F32(tuning_offset)) - float(station_hz)) * 4294967296.0 / rate
-    a = abs(x)
-    r = math.floor(a)
-    if a - r >= 0.5:
-        r += 1
-    return (r if x >= 0 else -r) & M32
-
-
-def fma32(a, b, c):
-    """test_engine_tuning.fmaf, with a short cut: a b is exact in double, so rounding the double sum a b + c to float32
-    differs from rounding the exact sum only if the double sum sits on a midpoint between two float32 (the low 29 bits of
-    its mantissa are 1 << 28) -- no such element, no double rounding, and the 6-operation path is fmaf's answer.  (The
-    values here are sums of products of float32 taps above 1e-12 with integers, far above float32's subnormals, where the
-    midpoints sit elsewhere.)"""
-    a, b, c = (np.asarray(v, F32) for v in (a, b, c))
-    s = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)
-    if np.any((s.view(np.uint64) & np.uint64(0x1FFFFFFF)) == np.uint64(0x10000000)):
-        return fmaf(a, b, c)
-    return s.astype(F32)
-
-
-def phasor2(tab, ph):
-    c, s = phasor(tab, np.asarray(ph, np.uint32).reshape(-1))
-    return c.reshape(np.shape(ph)), s.reshape(np.shape(ph))
-
-
-def sin_halfpi(q, D):
-    """sin(pi q / (2 D)), q >= 0 integers: rdsp_tune.h's ddc_sin_halfpi in numpy -- the same operations in the same order"""
-    r = q % (4 * D)
-    sign = np.where(r >= 2 * D, -1.0, 1.0)
-    r = np.where(r >= 2 * D, r - 2 * D, r)
-    r = np.where(r > D, 2 * D - r, r)
-    a = (3.141592653589793 * r.astype(np.float64)) / (2.0 * float(D))
-    a2 = a * a
-    term, total = a.copy(), a.copy()
-    for n in range(1, 15):
-        term = -(term * a2) / float((2 * n) * (2 * n + 1))
-        total = total + term
-    return sign * total
-
-
-def i0(x):
-    y = np.asarray(x, np.float64) / 2.0
-    term, total = np.ones_like(y), np.ones_like(y)
-    for n in range(1, 41):
-        t = y / float(n)
-        term = term * (t * t)
-        total = total + term
-    return total
-
-
-def taps_of(D, gain=1.0):
-    """the specified prototype: sinc with its cutoff at 22 050 Hz under a Kaiser window (beta 9), 16 D taps, sum 1 (summed
-    in tap order), times gain, rounded to float32"""
-    T = 16 * D
-    q = np.abs(2 * np.arange(T) - (T - 1))
-    u = (3.141592653589793 * q.astype(np.float64)) / (2.0 * float(D))
-    rho = q.astype(np.float64) / float(T - 1)
-    h = (sin_halfpi(q, D) / u) * (i0(BETA * np.sqrt(1.0 - rho * rho)) / i0(BETA))
-    total = 0.0
-    for v in h:
-        total += float(v)
-    return ((h / total) * float(gain)).astype(F32)
-
-
-def receiver_taps(h, dphi, tab):
-    """g[r][k] = (h_k c, h_k s), (c, s) the table's phasor at -k dphi[r]"""
-    k = np.arange(len(h), dtype=np.uint64)
-    ph = ((np.uint64(1 << 32) - ((k[None, :] * np.asarray(dphi, np.uint64)[:, None]) & np.uint64(M32))) & np.uint64(M32)).astype(np.uint32)
-    c, s = phasor2(tab, ph)
-    return h[None, :] * c, h[None, :] * s
-
-
-def ddc_rows(xh, D, h, dphi, ph0, tab):
-    """one call of receivers that share a source.  xh: int16 [15 D + n_out D, 2], the row with the source's history in
-    front; dphi, ph0: the receivers' steps and phases -> int16 [R, n_out, 2].  Per component ONE chain over k ascending:
-    re = fmaf(gx, xi, re); re = fmaf(-gy, xq, re); im = fmaf(gx, xq, im); im = fmaf(gy, xi, im); then tune_pair's rotation"""
-    T = 16 * D
-    n_out = (len(xh) - HIST * D) // D
-    dphi, ph0 = np.asarray(dphi, np.uint64), np.asarray(ph0, np.uint64)
-    gx, gy = receiver_taps(h, dphi, tab)
-    xi, xq = xh[:, 0].astype(F32), xh[:, 1].astype(F32)
-    re = np.zeros((len(dphi), n_out), F32)
-    im = np.zeros((len(dphi), n_out), F32)
-    for k in range(T):
-        a, b = xi[T - 1 - k::D][None, :n_out], xq[T - 1 - k::D][None, :n_out]
-        re = fma32(gx[:, k:k + 1], a, re)
-        re = fma32(-gy[:, k:k + 1], b, re)
-        im = fma32(gx[:, k:k + 1], b, im)
-        im = fma32(gy[:, k:k + 1], a, im)
-    ph = ((ph0[:, None] + np.arange(n_out, dtype=np.uint64)[None, :] * ((dphi * np.uint64(D)) & np.uint64(M32))[:, None]) & np.uint64(M32)).astype(np.uint32)
-    c, s = phasor2(tab, ph)
-    sat = lambda v: np.clip(np.rint(v), -32768, 32767).astype(np.int16)
-    return np.stack([sat(fmaf(re, c, -(im * s))), sat(fmaf(im, c, re * s))], -1)
-
-
-def ddc_stream(src_row, D, h, steps, tab, cuts=None):
-    """receivers of one source over a stream: steps uint32-valued [R, n_blocks], the step of each receiver in each block.
-    The stream is cut where a step changes and at `cuts` (blocks); history and phases are carried -> (int16 [R, n, 2],
-    phases after)"""
-    steps = np.asarray(steps, np.uint64)
-    R, nb = steps.shape
-    marks = sorted({0, nb} | {b for b in range(1, nb) if np.any(steps[:, b] != steps[:, b - 1])} | set(cuts or ()))
-    hist = np.zeros((HIST * D, 2), np.int16)
-    ph = np.zeros(R, np.uint64)
-    out = []
-    for a, b in zip(marks[:-1], marks[1:]):
-        x = src_row[a * 128 * D:b * 128 * D]
-        out.append(ddc_rows(np.concatenate([hist, x]), D, h, steps[:, a], ph, tab))
-        ph = (ph + np.uint64((b - a) * 128 * D) * steps[:, a]) & np.uint64(M32)
-        hist = x[-HIST * D:]
-    return np.concatenate(out, 1), ph
-
-
-def _table(rdsp):
-    return np.ctypeslib.as_array(rdsp.load().rdsp_engine_tune_table(), (1024, 4)).copy()
-
-
-def _lib_taps(D, gain=1.0):
-    from radiodsp_sdr_rx_amd.engine import ddc_taps
-    return ddc_taps(D, gain)
-
-
-def _tone(f, n, fs, amp, phase=0.0):
-    return amp * np.exp(2j * np.pi * (f / fs) * np.arange(n) + 1j * phase)
-
-
-def _int16(z):
-    return np.stack([np.clip(np.round(z.real), -32768, 32767), np.clip(np.round(z.imag), -32768, 32767)], -1).astype(np.int16)
-
-
-def _wide(seed, n_sources, n_blocks, D, level=0.05):
-    """int16 [n_sources, n_blocks 128 D, 2] at D x 44 100 Hz: in each, twenty carriers anywhere in the band, half of them
-    modulated or keyed, and noise; source 0 starts with full-scale pairs (saturation behind a gain above 1)"""
-    r = np.random.default_rng(seed)
-    fs, n = D * 44100.0, n_blocks * 128 * D
-    t = np.arange(n)
-    out = np.zeros((n_sources, n, 2), np.int16)
-    for s in range(n_sources):
-        z = np.zeros(n, np.complex128)
-        for _ in range(20):
-            f = r.uniform(-0.49, 0.49) * fs
-            env = 1 + 0.5 * np.sin(2 * np.pi * r.uniform(100, 800) / fs * t) if r.random() < 0.5 else (np.sin(2 * np.pi * r.uniform(2, 9) / fs * t) > 0)
-            z += r.uniform(0.2, 1.0) * level * env * np.exp(2j * np.pi * f / fs * t + 1j * r.uniform(0, 6))
-        z += 0.3 * level * (r.standard_normal(n) + 1j * r.standard_normal(n))
-        out[s] = _int16(z * 32767)
-    out[0, :32 * D] = np.repeat(np.array([[-32768, 32767], [32767, -32768], [32767, 32767], [-32768, -32768]], np.int16), 8 * D, 0)
-    return out
+from engine_sources_model import (F32, HIST, M32, S16, TUNING_OFFSET, Rx, _band, _int16, _phasor_modulus_error, _script_97, _tone, ddc_rows,
+                                  dphi_of, engine, host_program, host_rows, lib_taps, receiver_taps, stream, table, taps_of, wide)
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host_check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("ddc") / "host_ddc_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-I",
-                           os.path.join(ROOT, "radiodsp_sdr_rx_amd", "csrc"), os.path.join(HERE, "host", "host_ddc_check.cpp"),
-                           "-o", exe])
-    return exe
+def host_check():
+    return host_program()
 
 
 def test_ddc_filter_is_the_one_specified(rdsp):
     """rdsp_engine_ddc_taps for every D in 2 ... 64 at gain 1: symmetric bit for bit; sum 1 within the rounding of 16 D
     floats (2^-25 each); ripple <= 0.001 dB on |f| <= 12 000 Hz and <= -89 dB from 32 100 Hz on (the design conditions; the
-    worst measured values are printed); and EQUAL BIT FOR BIT to the numpy evaluation of the same formula (taps_of above):
-    the library evaluates sine and I0 by series of + - * / only and sqrt, so no libm stands between the two.  The gain
-    multiplies before the rounding; refusals of the host-only call."""
+    worst measured values are printed); and EQUAL BIT FOR BIT to the numpy evaluation of the same formula
+    (engine_sources_model.taps_of): the library evaluates sine and I0 by series of + - * / only and sqrt, so no libm stands
+    between the two.  The gain multiplies before the rounding; refusals of the host-only call."""
     worst_ripple, worst_stop = 0.0, -1e9
     for D in range(2, 65):
-        h = _lib_taps(D)
+        h = lib_taps(D)
         T = 16 * D
         assert h.dtype == F32 and len(h) == T and np.array_equal(h, h[::-1]), D
         assert abs(float(h.astype(np.float64).sum()) - 1.0) <= T * 2.0 ** -25, D
@@ -209,7 +47,7 @@ def test_ddc_filter_is_the_one_specified(rdsp):
         assert np.abs(h.astype(np.float64)).sum() <= 1.65, D
         worst_ripple, worst_stop = max(worst_ripple, ripple), max(worst_stop, stop)
     print(f"ddc taps: worst ripple {worst_ripple:.6f} dB, worst stop band {worst_stop:.2f} dB")
-    assert np.array_equal(_lib_taps(16, 37.5).view(np.uint32), taps_of(16, 37.5).view(np.uint32))
+    assert np.array_equal(lib_taps(16, 1, 37.5).view(np.uint32), taps_of(16, 1, 37.5).view(np.uint32))
     lib = rdsp.load()
     o = np.zeros(16 * 64, F32)
     p = o.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
@@ -225,7 +63,7 @@ def test_ddc_numpy_restatement_is_the_headers_arithmetic(host_check, tmp_path, r
     drawn phases, on a drawn row under a gain of 3 with edge pairs (+-32767, -32768, 0, +-1 in every combination),
     full-scale stretches that saturate, and a history; the host check's own checks (symmetry, the series against libm,
     the step at D, the DC gain) pass too"""
-    out = subprocess.run([host_check], capture_output=True, text=True)
+    out = subprocess.run([host_check, "check"], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.rstrip().endswith("OK"), out.stdout + out.stderr
     r = np.random.default_rng(100 + D)
     n_out, n_rx, gain = 256, 24, 3.0
@@ -241,41 +79,21 @@ def test_ddc_numpy_restatement_is_the_headers_arithmetic(host_check, tmp_path, r
     stations = np.concatenate([r.uniform(-lim + 1, lim - 1, n_rx - 4), [0.0, 8390.0, lim - 0.1, -lim + 0.1]])
     modes = np.arange(n_rx) % 7
     to = np.array([TUNING_OFFSET[int(m)] for m in modes], F32)
-    dphi = np.array([dphi_of(t, s, D * 44100.0) for t, s in zip(to, stations)], np.uint64)
+    dphi = np.array([dphi_of(t, s, D) for t, s in zip(to, stations)], np.uint64)
     ph0 = r.integers(0, 1 << 32, n_rx, dtype=np.uint64)
     ph0[:3] = 0
-    par = np.concatenate([[D, n_out, n_rx], np.stack([dphi, ph0], 1).reshape(-1)]).astype(np.uint32)
-    par.tofile(tmp_path / "params.bin")
-    np.array([gain], F32).tofile(tmp_path / "gain.bin")
-    xh.tofile(tmp_path / "src.bin")
-    to.tofile(tmp_path / "to.bin")
-    stations.astype(np.float64).tofile(tmp_path / "station.bin")
-    out = subprocess.run([host_check, "rows", str(tmp_path)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    tab = _table(rdsp)
+    want = host_rows(host_check, tmp_path, S16, xh[HIST * D:], xh[:HIST * D], D, 1, 0, gain, dphi, ph0, n_out, to, stations)
+    tab = table(rdsp)
     h = np.fromfile(tmp_path / "taps.bin", F32)
-    assert np.array_equal(h.view(np.uint32), taps_of(D, gain).view(np.uint32))
-    assert np.array_equal(h.view(np.uint32), _lib_taps(D, gain).view(np.uint32))
+    assert np.array_equal(h.view(np.uint32), taps_of(D, 1, gain).view(np.uint32))
+    assert np.array_equal(h.view(np.uint32), lib_taps(D, 1, gain).view(np.uint32))
     assert list(np.fromfile(tmp_path / "dphi.bin", np.uint32)) == [int(d) for d in dphi]
     g = np.fromfile(tmp_path / "g.bin", F32).reshape(n_rx, 16 * D, 2)
     gx, gy = receiver_taps(h, dphi, tab)
     assert np.array_equal(gx.view(np.uint32), g[..., 0].view(np.uint32)) and np.array_equal(gy.view(np.uint32), g[..., 1].view(np.uint32))
-    want = np.fromfile(tmp_path / "out.bin", np.uint32).reshape(n_rx, n_out)
     got = np.ascontiguousarray(ddc_rows(xh, D, h, dphi, ph0, tab)).view(np.uint32)[..., 0]
     assert np.array_equal(got, want), np.argwhere(got != want)[:4]
     assert (np.abs(ddc_rows(xh, D, h, dphi, ph0, tab).astype(int)) >= 32767).sum() > 50      # the rails were reached
-
-
-def _phasor_modulus_error(tab):
-    """what the bound of the next test stands on: |table phasor - e^{j phi}| as a complex MODULUS (the chord's error is
-    radial, (2 pi / 1024)^2 / 8 = 4.7e-6, plus the roundings of the table and of the fmaf): the worst of a million drawn
-    phases, the neighbours of every table entry and every entry's midpoint"""
-    r = np.random.default_rng(1)
-    k = np.arange(1024, dtype=np.uint64) << np.uint64(22)
-    ph = np.concatenate([r.integers(0, 1 << 32, 1000000, dtype=np.uint64), k, (k + np.uint64(1)) & np.uint64(M32), (k - np.uint64(1)) & np.uint64(M32), k + np.uint64(1 << 21)]).astype(np.uint32)
-    c, s = phasor(tab, ph)
-    a = 2 * np.pi * ph.astype(np.float64) / 4294967296.0
-    return np.hypot(c - np.cos(a), s - np.sin(a)).max()
 
 
 @pytest.mark.parametrize("D", [2, 5, 16, 64])
@@ -289,16 +107,16 @@ def test_ddc_restatement_against_exact_arithmetic(rdsp, D):
     once more: 2^-17 A.  gamma, the roundings: the product h_k c: 2^-24 A; the chain of n = 2 T fmaf per component, each
     rounding a partial sum of at most A: 2 T x 2^-24 A; the rotation's product and its fmaf: 2 x 2^-24 A; one more 2^-24 A
     for every second-order term: gamma = (2 T + 4) 2^-24."""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     assert _phasor_modulus_error(tab) < 2.0 ** -17
     T, nb, gain = 16 * D, 6, 2.0
-    src = _wide(7 + D, 1, nb, D, level=0.08)[0]
-    h = _lib_taps(D, gain)
+    src = wide(7 + D, 1, nb, D, level=0.08)[0]
+    h = lib_taps(D, 1, gain)
     r = np.random.default_rng(D)
     lim = D * 22050.0
     stations = np.concatenate([r.uniform(-lim + 1, lim - 1, 4), [0.0, lim - 1.0]])
-    dphi = np.array([dphi_of(TUNING_OFFSET[m % 7], s, D * 44100.0) for m, s in enumerate(stations)], np.uint64)
-    got, _ = ddc_stream(src, D, h, np.repeat(dphi[:, None], nb, 1), tab)
+    dphi = np.array([dphi_of(TUNING_OFFSET[m % 7], s, D) for m, s in enumerate(stations)], np.uint64)
+    got, _ = stream(src, D, 1, h, np.repeat(dphi[:, None], nb, 1), tab)
     x = np.concatenate([np.zeros(HIST * D), src[:, 0].astype(np.float64) + 1j * src[:, 1].astype(np.float64)])
     n_out = nb * 128
     A = np.convolve(np.abs(x), np.abs(h.astype(np.float64)))[T - 1::D][:n_out]
@@ -323,14 +141,14 @@ def test_ddc_is_a_receiver(rdsp):
     the amplitude within the ripple bound (0.001 dB) plus one count.  Then a 0.9 full-scale interferer at station -
     TuningOffset + 44 100 + 7 890 = 246 600 Hz, which the shift puts at 51 990 Hz and the decimation would fold onto 7 890 Hz in
     the IF band: no sample of the tuned row moves by more than 2 counts (0.9 x 32767 x 10^(-89 / 20) = 1.05 before rounding)"""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     D, nb = 16, 36
     fs, n = D * 44100.0, nb * 128 * D
-    h = _lib_taps(D)
+    h = lib_taps(D)
     to = TUNING_OFFSET[1]
-    steps = np.full((1, nb), dphi_of(to, 200000.0, fs), np.uint64)
+    steps = np.full((1, nb), dphi_of(to, 200000.0, D), np.uint64)
     amp = 0.25 * 32767
-    y = ddc_stream(_int16(_tone(201000.0, n, fs, amp)), D, h, steps, tab)[0][0]
+    y = stream(_int16(_tone(201000.0, n, fs, amp)), D, 1, h, steps, tab)[0][0]
     z = (y[128:128 + 4410, 0] + 1j * y[128:128 + 4410, 1]).astype(np.complex128)
     spec = np.abs(np.fft.fft(z))
     assert abs(np.fft.fftfreq(4410, 1 / 44100.0)[np.argmax(spec)] - (to + 1000.0)) < 1e-6
@@ -339,8 +157,8 @@ def test_ddc_is_a_receiver(rdsp):
     assert abs(got - amp) <= amp * (10 ** (0.001 / 20) - 1) + 1.0
     f_int = 200000.0 - to + 44100.0 + 7890.0
     a = 0.09 * 32767
-    clean = ddc_stream(_int16(_tone(201000.0, n, fs, a)), D, h, steps, tab)[0][0]
-    dirty = ddc_stream(_int16(_tone(201000.0, n, fs, a) + _tone(f_int, n, fs, 0.9 * 32767, 1.0)), D, h, steps, tab)[0][0]
+    clean = stream(_int16(_tone(201000.0, n, fs, a)), D, 1, h, steps, tab)[0][0]
+    dirty = stream(_int16(_tone(201000.0, n, fs, a) + _tone(f_int, n, fs, 0.9 * 32767, 1.0)), D, 1, h, steps, tab)[0][0]
     moved = np.abs(dirty.astype(int) - clean.astype(int))[16:].max()       # behind the filter's own length
     print(f"ddc receiver: the folding interferer moves a sample by at most {moved} counts")
     assert moved <= 2
@@ -350,91 +168,22 @@ def test_ddc_is_a_receiver(rdsp):
 def test_ddc_restatement_does_not_depend_on_the_call_split(rdsp, D):
     """32 blocks in one call, against calls of 1, 7 and 32 blocks with the history and the phases carried: sample for
     sample; and the phases after the stream are the closed form 32 x 128 x D x dphi"""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     nb = 32
-    src = _wide(3, 1, nb, D)[0]
-    h = _lib_taps(D, 1.5)
+    src = wide(3, 1, nb, D)[0]
+    h = lib_taps(D, 1, 1.5)
     r = np.random.default_rng(4)
-    dphi = np.array([dphi_of(TUNING_OFFSET[m], s, D * 44100.0) for m, s in zip((0, 1, 4), r.uniform(-D * 22000.0, D * 22000.0, 3))], np.uint64)
+    dphi = np.array([dphi_of(TUNING_OFFSET[m], s, D) for m, s in zip((0, 1, 4), r.uniform(-D * 22000.0, D * 22000.0, 3))], np.uint64)
     steps = np.repeat(dphi[:, None], nb, 1)
-    whole, ph = ddc_stream(src, D, h, steps, tab)
+    whole, ph = stream(src, D, 1, h, steps, tab)
     assert [int(p) for p in ph] == [(nb * 128 * D * int(d)) & M32 for d in dphi]
     for split in (1, 7, 32):
-        cut, ph2 = ddc_stream(src, D, h, steps, tab, cuts=range(0, nb, split))
+        cut, ph2 = stream(src, D, 1, h, steps, tab, cuts=range(0, nb, split))
         assert np.array_equal(cut, whole) and np.array_equal(ph, ph2), split
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-class _RxD(_Rx):
-    """test_engine_tuning._Rx on sources at D x 44 100 Hz: the engine's decimation is set between set_sources and the first
-    tune, the steps are per source sample, and the restated rows are ddc_stream's (all receivers of a source at once)"""
-
-    def __init__(self, eng, src, source_of, firsts, stations, D, gain):
-        import torch
-        self.eng, self.src, self.n, self.D, self.gain = eng, src, eng.n_channels, D, gain
-        self.source_of = [int(s) for s in source_of]
-        eng.set_sources(src.shape[0], self.source_of)
-        eng.set_source_decimation(D, gain)
-        assert eng.source_decimation() == D
-        self.firsts, self.modes = [0], [0]
-        self.set_groups(firsts)
-        self.station = np.zeros(self.n)
-        self.tune(0, stations)
-        self.calls = [[] for _ in range(self.n)]
-        self.steps = [[] for _ in range(self.n)]
-        self.d = torch.from_numpy(src).cuda()
-        self.outs = []
-        self.tab = eng.tune_table()
-        self.h = _lib_taps(D, gain)
-        self.rows = {}
-
-    def run(self, a, b, split):
-        w = 128 * self.D
-        for u in range(a, b, split):
-            v = min(b, u + split)
-            for c in range(self.n):
-                self.steps[c] += [dphi_of(TUNING_OFFSET[self.modes[self.group_of(c)]], self.station[c], self.D * 44100.0)] * (v - u)
-            self.outs.append(self.eng.update_sources(self.d[:, u * w:v * w].contiguous()))
-
-    def restate(self, channels):
-        for s in sorted({self.source_of[c] for c in channels}):
-            cs = [c for c in channels if self.source_of[c] == s and c not in self.rows]
-            if cs:
-                y, _ = ddc_stream(self.src[s], self.D, self.h, np.array([self.steps[c] for c in cs], np.uint64), self.tab)
-                self.rows.update(zip(cs, y))
-
-    def want(self, c):
-        import oracle_lib
-        self.restate([c])
-        return oracle_lib.OracleEngine().run(self.rows[c], self.calls[c])
-
-    def check(self, y, channels=None):
-        channels = list(range(self.n) if channels is None else channels)
-        self.restate(channels)
-        super().check(y, channels)
-
-
 _stream_cache = {}
-
-
-def _script_97(R, split, nb):
-    """five groups in LSB, USB, CW, AM, SAM; at block 13 a third of the receivers retune; at block 20 the groups are cut
-    anew into six and every group's mode is set again; at block 27 two groups change mode and one its audio filter"""
-    r = np.random.default_rng(77)
-    lim = R.D * 22050.0
-    for g, m in enumerate([0, 1, 2, 4, 5]):
-        R.call(0, g, "setDemodMode", m)
-    R.run(0, 13, split)
-    R.tune(5, r.uniform(-lim + 1, lim - 1, 32))
-    R.run(13, 20, split)
-    R.set_groups([0, 11, 40, 58, 70, 90])
-    for g, m in enumerate([0, 1, 2, 4, 5, 3]):              # channels 11-18 go from LSB to USB, 70-76 from AM to SAM, 90-96 to CW
-        R.call(20, g, "setDemodMode", m)
-    R.run(20, 27, split)
-    R.call(27, 2, "setDemodMode", 3)
-    R.call(27, 4, "setDemodMode", 1)
-    R.call(27, 1, "setAudioFilter", 3)
-    R.run(27, nb, split)
 
 
 @pytest.mark.gpu
@@ -447,14 +196,14 @@ def test_gpu_ddc_against_the_restatement(rdsp, D, split):
     the split, so it is computed once per D."""
     nch, nb, gain = 97, 40, 2.5
     r = np.random.default_rng(20 + D)
-    src = _wide(40 + D, 3, nb, D)
+    src = wide(40 + D, 3, nb, D)
     source_of = r.integers(0, 3, nch)
     lim = D * 22050.0
     stations = r.uniform(-lim + 1, lim - 1, nch)
     stations[:3] = [lim - 0.5, -lim + 0.5, 0.0]
-    eng = _engine(nch, 32)
+    eng = engine(nch, 32)
     eng.sketch_setup()
-    R = _RxD(eng, src, source_of, [0, 19, 40, 58, 77], stations, D, gain)
+    R = Rx(eng, src, source_of, [0, 19, 40, 58, 77], stations, D, 1, gain)
     _script_97(R, split, nb)
     y = R.result()
     if D not in _stream_cache:
@@ -476,9 +225,9 @@ def test_gpu_ddc_decimation_one_is_the_tuning_pass(rdsp):
     nch, nb = 97, 256
     src = _band(40, 3, nb)
     source_of = r.integers(0, 3, nch)
-    eng = _engine(nch, 64)
+    eng = engine(nch, 64)
     eng.sketch_setup()
-    R = _Rx(eng, src, source_of, [0, 19, 40, 58, 77], r.uniform(-21500, 21500, nch))
+    R = Rx(eng, src, source_of, [0, 19, 40, 58, 77], r.uniform(-21500, 21500, nch))
     eng.set_source_decimation(1, 1.0)
     assert eng.source_decimation() == 1
     for g, m in enumerate([0, 1, 2, 4, 5]):
@@ -502,11 +251,11 @@ def test_gpu_ddc_reset_history_and_state_as_data(rdsp):
     import torch
     D, nb, k, gain = 5, 24, 9, 2.0
     r = np.random.default_rng(9)
-    src = _wide(61, 2, nb, D)
+    src = wide(61, 2, nb, D)
     lim = D * 22050.0
-    a = _engine(6, 8)
+    a = engine(6, 8)
     a.sketch_setup()
-    A = _RxD(a, src, [0, 1, 1, 0, 1, 0], [0], r.uniform(-lim + 1, lim - 1, 6), D, gain)
+    A = Rx(a, src, [0, 1, 1, 0, 1, 0], [0], r.uniform(-lim + 1, lim - 1, 6), D, 1, gain)
     A.run(0, nb, 8)
     first = A.result()
     A.check(first)
@@ -514,9 +263,9 @@ def test_gpu_ddc_reset_history_and_state_as_data(rdsp):
     A.outs = []
     A.run(0, nb, 8)
     assert np.array_equal(A.result(), first)
-    fresh = _engine(6, 8)
+    fresh = engine(6, 8)
     fresh.sketch_setup()
-    Fr = _RxD(fresh, src, A.source_of, [0], A.station, D, gain)
+    Fr = Rx(fresh, src, A.source_of, [0], A.station, D, 1, gain)
     Fr.run(0, 1, 8)
     assert np.array_equal(Fr.result(), first[:, :128])
     # state as data: a runs 9 blocks, b hears the same 9 blocks with receivers of its own, then takes a's channels 2, 3
@@ -526,9 +275,9 @@ def test_gpu_ddc_reset_history_and_state_as_data(rdsp):
     blob = a.save_state(2, 2)
     assert blob.size == a.lib.rdsp_engine_state_bytes(a.h, 2) == 16 + 2 * (10368 + 4)
     assert list(blob[:16].view(np.uint32)) == [0x45534452, 1, 2, 1]
-    b = _engine(9, 16)
+    b = engine(9, 16)
     b.sketch_setup()
-    B = _RxD(b, src, [0] * 5 + [1, 0] + [1] * 2, [0], r.uniform(-lim + 1, lim - 1, 9), D, gain)
+    B = Rx(b, src, [0] * 5 + [1, 0] + [1] * 2, [0], r.uniform(-lim + 1, lim - 1, 9), D, 1, gain)
     B.tune(5, A.station[2:4])
     B.run(0, k, 16)
     b.load_state(5, blob)
@@ -545,11 +294,11 @@ def test_gpu_ddc_at_the_bench_shape(rdsp):
     receiver of every source in the pass's order, the receivers around two workgroup boundaries and 32 drawn ones -- 68 or
     more -- bit for bit"""
     nch, nblk, nsrc, D = 4096, 32, 16, 16
-    src = _wide(5, nsrc, nblk, D)
-    eng = _engine(nch, nblk)
+    src = wide(5, nsrc, nblk, D)
+    eng = engine(nch, nblk)
     eng.sketch_setup()
     lim = D * 22050.0
-    R = _RxD(eng, src, np.arange(nch) % nsrc, [0], np.random.default_rng(5).uniform(-lim + 1, lim - 1, nch), D, 4.0)
+    R = Rx(eng, src, np.arange(nch) % nsrc, [0], np.random.default_rng(5).uniform(-lim + 1, lim - 1, nch), D, 1, 4.0)
     R.run(0, nblk, nblk)
     y = R.result()
     per = nch // nsrc                                       # position p of source s in the pass's order is channel p nsrc + s
@@ -567,9 +316,9 @@ def test_gpu_ddc_refusals(rdsp):
     import torch
     from radiodsp_sdr_rx_amd._lib import RdspError
     D = 4
-    src = torch.from_numpy(_wide(95, 2, 16, D)).cuda()
+    src = torch.from_numpy(wide(95, 2, 16, D)).cuda()
     out = torch.empty((4, 8 * 128, 2), dtype=torch.int16, device="cuda")
-    eng, twin = _engine(4, 8), _engine(4, 8)
+    eng, twin = engine(4, 8), engine(4, 8)
     for e in (eng, twin):
         e.sketch_setup()
     with pytest.raises(RdspError) as ex:

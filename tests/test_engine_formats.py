@@ -3,13 +3,12 @@ rdsp_engine_update_source_samples, include/rdsp.h; the value of a sample is csrc
 the arithmetic of the three passes as it was), and rdsp_iq_reader_t on recordings in those formats (csrc/rdsp_io.c).
 
 `-m "not gpu"`: the value table, exactly; each pass under the header's arithmetic compiled on the host
-(tests/host/host_format_check.cpp): an 8-bit row gives the bits of the int16 pass on the widened row, a float row of k / 32768
-the bits of the int16 row k, a random float row the bits of the numpy restatement (values() below, then the chains of
-test_engine_tuning / _ddc / _rate, which take values as they take int16) and stays within the project's bound of a float64
-evaluation of the definition; the readers.
+(tests/host/host_source_pass_check.cpp): an 8-bit row gives the bits of the int16 pass on the widened row, a float row of
+k / 32768 the bits of the int16 row k, a random float row the bits of the numpy restatement (tests/engine_sources_model.py:
+values(), then the chains of the three passes, which take values as they take int16) and stays within the project's bound of a
+float64 evaluation of the definition; the readers.
 `-m gpu`: 8-bit and k / 32768 rows against an int16 twin bit for bit, call by call, state blobs included; random float rows
 against rdsp_engine_update on the restated rows; the format as a setting; the refusals; the Python wrapper."""
-import ctypes as C
 import os
 import struct
 import subprocess
@@ -17,121 +16,25 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_engine_ddc import _lib_taps, _phasor_modulus_error, _table, ddc_rows, ddc_stream, dphi_of
-from test_engine_rate import _dc, _fs, _lib_rate_taps, _pairs, _wide_rate, rate_rows, rate_stream, schedule
-from test_engine_tuning import HERE, M32, ROOT, TUNING_OFFSET, _engine, tune_pairs, tuned_row
-
-F32 = np.float32
+import engine_sources_model as model
+from engine_sources_model import (DTYPE, F32, FL, HERE, M32, ROOT, S8, S16, U8, _c_call, _dc, _dphis, _pairs, _phasor_modulus_error, _raw_of,
+                                  _setup, _stations, _stream, _to_u8, call_rows, engine, host_program, host_rows, lib_taps, schedule, stream,
+                                  table, values, wide, widened)
 S16, U8, S8, FL = 0, 1, 2, 3
 DTYPE = (np.int16, np.uint8, np.int8, np.float32)
 CPU_RATES = [(1, 1), (3, 1), (3, 2), (160, 147)]
 GPU_RATES = [(1, 1), (2, 1), (30, 1), (48, 1), (3, 2), (160, 147), (17, 2)]
 
 
-# ---- the restatement in numpy ---------------------------------------------------------------------------------------------
-def values(fmt, raw):
-    """the table of include/rdsp.h: what a row's elements are worth, float32 counts on the int16 scale"""
-    raw = np.asarray(raw)
-    assert raw.dtype == DTYPE[fmt]
-    if fmt == U8:
-        return (2 * raw.astype(np.int32) - 255).astype(F32) * F32(128.0)
-    if fmt == S8:
-        return raw.astype(F32) * F32(256.0)
-    if fmt == FL:
-        with np.errstate(invalid="ignore"):
-            return np.where(np.isnan(raw), F32(0.0), np.minimum(np.maximum(raw, F32(-256.0)), F32(256.0)) * F32(32768.0)).astype(F32)
-    return raw.astype(F32)
-
-
-def widened(fmt, raw):
-    """an 8-bit row as the int16 row of the same values (every one is an exact int16)"""
-    v = values(fmt, raw)
-    assert np.all(v == np.rint(v)) and v.min() >= -32768 and v.max() <= 32767
-    return v.astype(np.int16)
-
-
-def one_call(xh, P, Q, frac, gain, dphi, ph0, tab, n_out):
-    """one call of receivers that share a source: xh the VALUES (or int16) with the pairs before the call in front"""
-    if (P, Q) == (1, 1):
-        t = np.arange(n_out, dtype=np.uint64)
-        return np.stack([tune_pairs(xh, ((np.uint64(p) + t * np.uint64(d)) & np.uint64(M32)).astype(np.uint32), tab) for d, p in zip(dphi, ph0)])
-    if Q == 1:
-        return ddc_rows(xh, P, _lib_taps(P, gain), dphi, ph0, tab)
-    return rate_rows(xh, P, Q, frac, _lib_rate_taps(P, Q, gain), dphi, ph0, tab, n_out)
-
-
-def restate(vals, P, Q, gain, dphi, nb, tab, cuts=None):
+def _restate(vals, P, Q, gain, dphi, nb, tab, cuts=None):
     """receivers of one source over a stream of nb blocks from a reset, at constant steps: the tuned rows [R, nb 128, 2]"""
-    steps = np.repeat(np.asarray(dphi, np.uint64)[:, None], nb, 1)
-    if (P, Q) == (1, 1):                                   # the phase is carried across the cuts
-        marks = sorted({0, nb} | set(cuts or ()))
-        ph = [0] * len(steps)
-        out = []
-        for a, b in zip(marks[:-1], marks[1:]):
-            out.append(np.stack([tuned_row(vals[a * 128:b * 128], s[a:b], tab, phase0=p) for s, p in zip(steps, ph)]))
-            ph = [(p + (b - a) * 128 * int(s[a])) & M32 for s, p in zip(steps, ph)]
-        return np.concatenate(out, 1)
-    if Q == 1:
-        return ddc_stream(vals, P, _lib_taps(P, gain), steps, tab, cuts)[0]
-    return rate_stream(vals, P, Q, _lib_rate_taps(P, Q, gain), steps, tab, cuts)[0]
-
-
-def _keep(P, Q):
-    return 0 if (P, Q) == (1, 1) else 15 * P if Q == 1 else 16 * _dc(P, Q)
-
-
-def _to_u8(x):
-    return np.clip(np.rint(x.astype(np.float64) / 256.0 + 127.5), 0, 255).astype(np.uint8)
-
-
-def _to_s8(x):
-    return np.clip(np.rint(x.astype(np.float64) / 256.0), -128, 127).astype(np.int8)
-
-
-def _raw_of(fmt, x, seed=0):
-    """a row of format fmt from an int16 band x: 8-bit by its high byte; float as k / 32768 (seed 0) or with a drawn fraction
-    of a count added (random non-integer values)"""
-    if fmt == U8:
-        return _to_u8(x)
-    if fmt == S8:
-        return _to_s8(x)
-    if fmt == FL:
-        j = np.random.default_rng(seed).uniform(-0.5, 0.5, x.shape) if seed else 0.0
-        return ((x.astype(np.float64) + j) / 32768.0).astype(F32)
-    return x
-
-
-def _stations(seed, n, P, Q):
-    lim = (22050.0 * P) / Q
-    st = np.random.default_rng(seed).uniform(-lim + 1, lim - 1, n)
-    st[:2] = [lim - 0.5, 0.0]
-    return st
-
-
-def _dphis(stations, P, Q):
-    return np.array([dphi_of(TUNING_OFFSET[0], s, _fs(P, Q)) for s in stations], np.uint64)
+    return stream(vals, P, Q, lib_taps(P, Q, gain), np.repeat(np.asarray(dphi, np.uint64)[:, None], nb, 1), tab, cuts)[0]
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host_check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("formats") / "host_format_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-I",
-                           os.path.join(ROOT, "radiodsp_sdr_rx_amd", "csrc"), os.path.join(HERE, "host", "host_format_check.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def _host_rows(exe, d, fmt, raw, hist_vals, P, Q, frac, gain, dphi, ph0, n_out):
-    """host_format_check rows: the call's pairs `raw` in their own format, the VALUES of the pairs before it -> words [R, n_out]"""
-    kind = 0 if (P, Q) == (1, 1) else 1 if Q == 1 else 2
-    np.concatenate([[fmt, kind, P, Q, frac, n_out, len(dphi)], np.stack([dphi, ph0], 1).reshape(-1)]).astype(np.uint32).tofile(d / "params.bin")
-    np.array([gain], F32).tofile(d / "gain.bin")
-    np.ascontiguousarray(hist_vals, F32).tofile(d / "hist.bin")
-    np.ascontiguousarray(raw, DTYPE[fmt]).tofile(d / "src.bin")
-    out = subprocess.run([exe, "rows", str(d)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return np.fromfile(d / "out.bin", np.uint32).reshape(len(dphi), n_out)
+def host_check():
+    return host_program()
 
 
 def _words(rows):
@@ -142,7 +45,7 @@ def _case(P, Q, seed, n_out=256, n_rx=6):
     """a call 37 outputs into a stream (frac not 0 at a rational rate): int16 band with the history in front, steps, phases"""
     r = np.random.default_rng(seed)
     frac, pairs, _, _ = schedule(P, Q, 37, n_out)
-    keep = _keep(P, Q)
+    keep = model.keep(P, Q)
     x = r.integers(-9000, 9000, (keep + pairs, 2)).astype(np.int16)
     x[r.integers(0, len(x), 24)] = r.choice(np.array([-32768, -32767, -1, 0, 1, 32767], np.int16), (24, 2))
     dphi = _dphis(_stations(seed + 1, n_rx, P, Q), P, Q)
@@ -154,7 +57,7 @@ def _case(P, Q, seed, n_out=256, n_rx=6):
 def test_format_sample_value_table(host_check):
     """src_value compiled on the host: all 256 bytes under U8 ((2 u - 255) x 128) and S8 (s x 256), and the floats 0, +-1,
     +-2^-15, a denormal, 0.999 999 94, +-256, +-256.5, +-3e38, +-inf, NaN: the table's values exactly (NaN -> 0, +-2^23 beyond
-    +-256), and the numpy statement of the table used below agrees"""
+    +-256), and the numpy statement of the table (engine_sources_model.values) agrees"""
     out = subprocess.run([host_check, "values"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     got = {"u8": {}, "s8": {}, "f32": {}}
@@ -189,12 +92,12 @@ def test_format_8bit_row_is_the_int16_pass_on_the_widened_row(host_check, tmp_pa
     raw = _raw_of(fmt, x * 3)
     raw[:4] = [[0, 255], [255, 0], [128, 127], [1, 254]] if fmt == U8 else [[-128, 127], [127, -128], [0, -1], [1, -127]]
     v, w = values(fmt, raw), widened(fmt, raw)
-    tab = _table(rdsp)
-    got = _host_rows(host_check, tmp_path, fmt, raw[keep:], v[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
-    twin = _host_rows(host_check, tmp_path, S16, w[keep:], v[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
+    tab = table(rdsp)
+    got = host_rows(host_check, tmp_path, fmt, raw[keep:], v[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
+    twin = host_rows(host_check, tmp_path, S16, w[keep:], v[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
     assert got.any() and np.array_equal(got, twin)
-    assert np.array_equal(got, _words(one_call(v, P, Q, frac, 2.0, dphi, ph0, tab, 256)))
-    assert np.array_equal(got, _words(one_call(w, P, Q, frac, 2.0, dphi, ph0, tab, 256)))
+    assert np.array_equal(got, _words(call_rows(v, P, Q, frac, lib_taps(P, Q, 2.0), dphi, ph0, tab, 256)))
+    assert np.array_equal(got, _words(call_rows(w, P, Q, frac, lib_taps(P, Q, 2.0), dphi, ph0, tab, 256)))
 
 
 @pytest.mark.parametrize("P,Q", CPU_RATES)
@@ -203,8 +106,8 @@ def test_format_float_rows_of_integers_are_the_int16_rows(host_check, tmp_path, 
     frac, keep, x, dphi, ph0 = _case(P, Q, 50 + P)
     raw = _raw_of(FL, x)
     assert np.array_equal(values(FL, raw), x.astype(F32))
-    got = _host_rows(host_check, tmp_path, FL, raw[keep:], x[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
-    twin = _host_rows(host_check, tmp_path, S16, x[keep:], x[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
+    got = host_rows(host_check, tmp_path, FL, raw[keep:], x[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
+    twin = host_rows(host_check, tmp_path, S16, x[keep:], x[:keep], P, Q, frac, 2.0, dphi, ph0, 256)
     assert got.any() and np.array_equal(got, twin)
 
 
@@ -216,23 +119,23 @@ def test_format_random_float_rows_against_the_restatement_and_exact_arithmetic(h
     counts, T the taps of an output (0 for the plain tuning pass): tests/test_engine_rate.py and test_engine_ddc.py derive
     it for int16 rows, and it carries over unchanged because the scale 32768 is a power of two: the value of a float
     element is exact, so the arithmetic starts from exact inputs as it does from int16.  The worst ratio is printed."""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     assert _phasor_modulus_error(tab) < 2.0 ** -17
     r = np.random.default_rng(70 + P)
     n_out, gain = 256, 2.0
     frac, pairs, n, br = schedule(P, Q, 37, n_out)
-    keep = _keep(P, Q)
+    keep = model.keep(P, Q)
     raw = r.uniform(-0.05, 0.05, (keep + pairs, 2)).astype(F32)
     v = values(FL, raw)
     assert np.any(v != np.rint(v)) and np.array_equal(v, raw * F32(32768.0))
     dphi = _dphis(_stations(71 + P, 6, P, Q), P, Q)
     ph0 = r.integers(0, 1 << 32, 6, dtype=np.uint64)
-    got = one_call(v, P, Q, frac, gain, dphi, ph0, tab, n_out)
-    host = _host_rows(host_check, tmp_path, FL, raw[keep:], v[:keep], P, Q, frac, gain, dphi, ph0, n_out)
+    got = call_rows(v, P, Q, frac, lib_taps(P, Q, gain), dphi, ph0, tab, n_out)
+    host = host_rows(host_check, tmp_path, FL, raw[keep:], v[:keep], P, Q, frac, gain, dphi, ph0, n_out)
     assert np.array_equal(_words(got), host)
     Dc = _dc(P, Q)
     Tb = 1 if (P, Q) == (1, 1) else 16 * Dc
-    h = np.ones(1) if (P, Q) == (1, 1) else (_lib_taps(P, gain) if Q == 1 else _lib_rate_taps(P, Q, gain)).astype(np.float64)
+    h = np.ones(1) if (P, Q) == (1, 1) else lib_taps(P, Q, gain).astype(np.float64)
     x = np.concatenate([np.zeros(Tb - keep), v[:, 0].astype(np.float64) + 1j * v[:, 1].astype(np.float64)])   # index Tb + n is pair n
     j = np.arange(Tb)
     X = x[Tb + n[:, None] - j[None, :]]
@@ -259,17 +162,17 @@ def test_format_phase_zero_is_the_value(host_check, tmp_path, rdsp):
     z = np.zeros(1, np.uint64)
     u = r.integers(0, 256, (128, 2)).astype(np.uint8)
     u[:2] = [[0, 255], [127, 128]]
-    got = _host_rows(host_check, tmp_path, U8, u, np.zeros((0, 2)), 1, 1, 0, 1.0, z, z, 128)
+    got = host_rows(host_check, tmp_path, U8, u, np.zeros((0, 2)), 1, 1, 0, 1.0, z, z, 128)
     assert np.array_equal(got[0], _words(widened(U8, u)))
     f = r.uniform(-1.2, 1.2, (128, 2)).astype(F32)
     f[:6] = [[1.0, -1.0], [0.5 / 32768, 1.5 / 32768], [2.5 / 32768, -0.5 / 32768], [np.nan, np.inf], [-np.inf, 3e38], [-3e38, 0.99999994]]
-    got = _host_rows(host_check, tmp_path, FL, f, np.zeros((0, 2)), 1, 1, 0, 1.0, z, z, 128)
+    got = host_rows(host_check, tmp_path, FL, f, np.zeros((0, 2)), 1, 1, 0, 1.0, z, z, 128)
     with np.errstate(invalid="ignore"):
         want = np.clip(np.rint(np.where(np.isnan(f), 0.0, f.astype(np.float64) * 32768.0)), -32768, 32767).astype(np.int16)
     assert np.array_equal(got[0], _words(want))
     assert list(want[1]) == [0, 2] and list(want[2]) == [2, 0] and list(want[3]) == [0, 32767] and list(want[4]) == [-32768, 32767]
-    tab = _table(rdsp)
-    assert np.array_equal(_words(one_call(values(FL, f), 1, 1, 0, 1.0, z, z, tab, 128)), got)
+    tab = table(rdsp)
+    assert np.array_equal(_words(call_rows(values(FL, f), 1, 1, 0, None, z, z, tab, 128)), got)
 
 
 @pytest.mark.parametrize("P,Q", CPU_RATES)
@@ -277,14 +180,14 @@ def test_format_phase_zero_is_the_value(host_check, tmp_path, rdsp):
 def test_format_restatement_does_not_depend_on_the_call_split(rdsp, fmt, P, Q):
     """8 blocks of a U8 and of a random float row in one call, against calls of 1 and 7 blocks with the history (kept as values),
     frac and the phases carried: sample for sample"""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     nb = 8
-    v = values(fmt, _raw_of(fmt, _wide_rate(5 + P, 1, nb, P, Q, level=0.3)[0], seed=9))
+    v = values(fmt, _raw_of(fmt, wide(5 + P, 1, nb, P, Q, level=0.3)[0], seed=9))
     dphi = _dphis(_stations(6, 3, P, Q), P, Q)
-    whole = restate(v, P, Q, 1.5, dphi, nb, tab)
+    whole = _restate(v, P, Q, 1.5, dphi, nb, tab)
     assert whole.any()
     for split in (1, 7):
-        assert np.array_equal(restate(v, P, Q, 1.5, dphi, nb, tab, cuts=range(0, nb, split)), whole), split
+        assert np.array_equal(_restate(v, P, Q, 1.5, dphi, nb, tab, cuts=range(0, nb, split)), whole), split
 
 
 # ---- readers --------------------------------------------------------------------------------------------------------------
@@ -358,58 +261,6 @@ def test_format_readers_under_address_and_ub_sanitizers(tmp_path):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _setup(nch, n_sources, source_of, P, Q, gain, stations, fmt, max_blocks=8):
-    e = _engine(nch, max_blocks)
-    e.sketch_setup()
-    e.set_sources(n_sources, source_of)
-    if (P, Q) != (1, 1):
-        e.set_source_rate(P, Q, gain)
-    if fmt != S16:
-        e.set_source_format(fmt)
-    assert e.source_format() == fmt
-    e.tune(0, stations)
-    return e
-
-
-def _c_call(e, rows, nb, out, entry="rdsp_engine_update_source_samples", stride=None, ptr=None):
-    """the C entry itself: rows a device tensor [n_sources, pairs, 2], contiguous or a view into a longer buffer"""
-    import torch
-    if stride is None:
-        stride = rows.stride(0) // 2 if rows.shape[0] > 1 else rows.shape[1]
-    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return getattr(e.lib, entry)(e.h, rows.data_ptr() if ptr is None else ptr, stride, nb, out.data_ptr(), out.shape[1], s)
-
-
-def _stream(e, d, P, Q, a, b, split, entry="rdsp_engine_update_source_samples", odd=False):
-    """blocks a ... b of the device rows d in calls of `split`: the calls walk through d (pairs before block a: the closed form
-    of the schedule); integer rates take contiguous 16-byte aligned copies, rational ones views -- with `odd`, views at odd
-    pair offsets of a second long buffer.  -> the audio of every call, on the host"""
-    import torch
-    outs = []
-    long = torch.zeros((d.shape[0], d.shape[1] + 4 * (b - a) + 8, 2), dtype=d.dtype, device="cuda") if odd else None
-    at = 1
-    S = e.pos_pairs
-    for u in range(a, b, split):
-        v = min(b, u + split)
-        pairs = e.source_pairs(v - u)
-        rows = d[:, S:S + pairs]
-        assert rows.shape[1] == pairs
-        if Q == 1:
-            rows = rows.contiguous()
-        elif odd:
-            long[:, at:at + pairs].copy_(rows)
-            rows = long[:, at:at + pairs]
-            assert (rows.data_ptr() // (2 * d.element_size())) % 2 == 1 and not rows.is_contiguous()
-            at += pairs
-            at += (at + 1) % 2
-        out = torch.empty((e.n_channels, (v - u) * 128, 2), dtype=torch.int16, device="cuda")
-        assert _c_call(e, rows, v - u, out, entry) == 0, e.lib.rdsp_last_error()
-        outs.append(out.cpu().numpy())
-        S += pairs
-    e.pos_pairs = S
-    return outs
-
-
 def _shape(P, Q, seed, level=0.3):
     """the shape of the GPU cases: 2 sources, 5 receivers (17 under an integer D > 1: one full 16-receiver workgroup of the
     decimating kernel and a ragged one), 8 blocks"""
@@ -417,7 +268,7 @@ def _shape(P, Q, seed, level=0.3):
     source_of = [int(s) for s in np.random.default_rng(seed).integers(0, 2, nch)]
     if Q == 1 and P > 1:
         source_of = [0] * 16 + [1]
-    return nch, source_of, _stations(seed + 1, nch, P, Q), _wide_rate(seed + 2, 2, 8, P, Q, level=level)
+    return nch, source_of, _stations(seed + 1, nch, P, Q), wide(seed + 2, 2, 8, P, Q, level=level)
 
 
 def _twin_runs(fmt, P, Q, raw, x16, nch, source_of, stations, gain=2.0):
@@ -454,7 +305,7 @@ def test_gpu_format_8bit_against_an_int16_twin(rdsp, fmt, P, Q):
 @pytest.mark.gpu
 @pytest.mark.parametrize("P,Q", GPU_RATES)
 def test_gpu_format_float_rows_of_integers_against_an_int16_twin(rdsp, P, Q):
-    """float rows k / 32768 against the twin on the int16 rows k (the full-scale pairs of _wide_rate among them); odd pair
+    """float rows k / 32768 against the twin on the int16 rows k (the full-scale pairs of wide() among them); odd pair
     offsets (8-byte alignment only) in the 5-block runs of a rational rate"""
     nch, source_of, stations, x = _shape(P, Q, 200 + P, level=0.05)
     _twin_runs(FL, P, Q, _raw_of(FL, x), x, nch, source_of, stations)
@@ -474,16 +325,16 @@ def test_gpu_format_random_float_rows_against_the_restatement(rdsp, P, Q):
     raw[1, at, r.integers(0, 2, 40)] = r.choice(np.array([np.nan, np.inf, -np.inf, 3e38, -3e38], F32), 40)
     raw[1, :3] = [[np.nan, np.inf], [-np.inf, 3e38], [-3e38, np.nan]]
     gain = 2.0
-    tab = _table(rdsp)
+    tab = table(rdsp)
     tuned = np.zeros((nch, 8 * 128, 2), np.int16)
     for s in (0, 1):
         cs = [c for c in range(nch) if source_of[c] == s]
         if cs:
-            tuned[cs] = restate(values(FL, raw[s]), P, Q, gain, _dphis(stations[cs], P, Q), 8, tab)
+            tuned[cs] = _restate(values(FL, raw[s]), P, Q, gain, _dphis(stations[cs], P, Q), 8, tab)
     d, dt = torch.from_numpy(raw).cuda(), torch.from_numpy(tuned).cuda()
     for split in (1, 2, 5):
         e = _setup(nch, 2, source_of, P, Q, gain, stations, FL)
-        t = _engine(nch, 8)
+        t = engine(nch, 8)
         t.sketch_setup()
         e.pos_pairs = 0
         ya = _stream(e, d, P, Q, 0, 8, split, odd=split == 5 and Q > 1)
@@ -501,7 +352,7 @@ def test_gpu_format_more_than_a_workgroup_of_receivers_on_one_source(rdsp):
     the receivers test_gpu_rate_more_than_a_workgroup_of_receivers_on_one_source lists, against the int16 twin"""
     import torch
     P, Q, nch, nb = 160, 147, 300, 4
-    raw = _to_u8(_wide_rate(11, 1, nb, P, Q, level=0.3))
+    raw = _to_u8(wide(11, 1, nb, P, Q, level=0.3))
     stations = _stations(12, nch, P, Q)
     outs = []
     for fmt, rows in ((U8, raw), (S16, widened(U8, raw))):
@@ -523,7 +374,7 @@ def test_gpu_format_is_a_setting(rdsp):
     import torch
     P, Q, gain = 160, 147, 2.0
     nch, source_of, stations, x = _shape(P, Q, 400)
-    x = np.concatenate([x, _wide_rate(403, 2, 8, P, Q, level=0.3)], 1)          # 16 blocks and a few pairs
+    x = np.concatenate([x, wide(403, 2, 8, P, Q, level=0.3)], 1)          # 16 blocks and a few pairs
     u8 = _to_u8(x)
     w = widened(U8, u8)
     fl = _raw_of(FL, w)                                                          # k / 32768 of the same values
@@ -572,7 +423,7 @@ def test_gpu_format_refusals(rdsp):
     on exactly as a twin that never saw those calls"""
     import torch
     from radiodsp_sdr_rx_amd._lib import RdspError
-    fresh = _engine(2, 4)
+    fresh = engine(2, 4)
     with pytest.raises(RdspError) as ex:
         fresh.set_source_format(U8)
     assert ex.value.code == -4 and b"set_sources" in fresh.lib.rdsp_last_error() and fresh.source_format() == S16
@@ -598,7 +449,7 @@ def test_gpu_format_refusals(rdsp):
     y = [_stream(e, d, 2, 1, 0, 4, 4)[0] for e in (eng, twin)]
     assert y[0].any() and np.array_equal(y[0], y[1])
     # a rational rate: rows aligned to one pair
-    raw = {U8: _to_u8(_wide_rate(501, 2, 8, 3, 2, level=0.3))}
+    raw = {U8: _to_u8(wide(501, 2, 8, 3, 2, level=0.3))}
     raw[FL] = _raw_of(FL, widened(U8, raw[U8]), seed=5)
     for fmt in (U8, FL):
         dev = torch.from_numpy(raw[fmt]).cuda()

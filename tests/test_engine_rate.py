@@ -3,159 +3,44 @@ and resampled by Q / P in one polyphase pass (rdsp_engine_set_source_rate, inclu
 csrc/rdsp_engine_rate.hip, schedule and arithmetic csrc/rdsp_tune.h).
 
 `-m "not gpu"`: the prototype filter is the one specified (and the numpy evaluation of its formula, bit for bit); the schedule
-is the one specified, in Python integers; the numpy restatement below is rdsp_tune.h's arithmetic compiled on the host
-(tests/host/host_rate_check.cpp), bit for bit; the restated row stays within a derived bound of a float64 evaluation of the
-definition; it is a receiver at 2.4 MHz; it does not depend on how the stream is cut into calls.
+is the one specified, in Python integers; the numpy restatement (tests/engine_sources_model.py) is rdsp_tune.h's arithmetic
+compiled on the host (tests/host/host_source_pass_check.cpp), bit for bit; the restated row stays within a derived bound of a
+float64 evaluation of the definition; it is a receiver at 2.4 MHz; it does not depend on how the stream is cut into calls.
 `-m gpu`: the audio of every receiver, bit for bit, against oracle_lib.OracleEngine run on the restated row, as
 tests/test_engine_ddc.py does for integer rates."""
 import ctypes
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_engine_ddc import BETA, _int16, _script_97, _table, _tone, dphi_of, fma32, i0, phasor2, sin_halfpi, taps_of, _phasor_modulus_error
-from test_engine_tuning import HERE, M32, ROOT, TUNING_OFFSET, _Rx, _engine, fmaf
+from engine_sources_model import (F32, M32, S16, TUNING_OFFSET, Rx, _dc, _fs, _int16, _pairs, _phasor_modulus_error, _script_97, _tone, dphi_of,
+                                  engine, host_program, host_rows, lib_taps, rate_rows, schedule, stream, table, taps_of, wide)
 
-F32 = np.float32
 RATES = [(3, 2), (65, 64), (160, 147), (640, 147), (2500, 441), (8000, 147), (20480, 441)]
-
-
-def _dc(P, Q):
-    return -(-P // Q)
-
-
-def _fs(P, Q):
-    return (P * 44100.0) / Q                  # the operations of rate_dphi's divisor
-
-
-# ---- the restatement in numpy ---------------------------------------------------------------------------------------------
-def rate_taps_of(P, Q, gain=1.0):
-    """the specified prototype: ddc's sinc under a Kaiser window (beta 9) at the rate 44 100 P, Tp = 16 ceil(P / Q) Q taps,
-    sum 1 (summed in tap order), times Q gain, rounded to float32"""
-    Tp = 16 * _dc(P, Q) * Q
-    q = np.abs(2 * np.arange(Tp) - (Tp - 1))
-    u = (3.141592653589793 * q.astype(np.float64)) / (2.0 * float(P))
-    rho = q.astype(np.float64) / float(Tp - 1)
-    h = (sin_halfpi(q, P) / u) * (i0(BETA * np.sqrt(1.0 - rho * rho)) / i0(BETA))
-    total = 0.0
-    for v in h.tolist():
-        total += v
-    return ((h / total) * (float(Q) * float(gain))).astype(F32)
-
-
-def schedule(P, Q, m0, n_out):
-    """outputs m0 ... m0 + n_out - 1 since the reset: (frac, pairs, n local to the call, r)"""
-    S = (m0 * P) // Q
-    t = [(m0 * P) % Q + (i + 1) * P for i in range(n_out)]
-    return (m0 * P) % Q, ((m0 + n_out) * P) // Q - S, np.array([v // Q - 1 for v in t], np.int64), np.array([v % Q for v in t], np.int64)
-
-
-def rate_rows(xh, P, Q, frac, h, dphi, ph0, tab, n_out):
-    """one call of receivers that share a source.  xh: int16 [Tb + pairs, 2], the row with the source's last Tb pairs in
-    front; h: the prototype; dphi, ph0: the receivers' steps and phases -> int16 [R, n_out, 2].  u_j = h[j Q + r(i)] x[n(i) -
-    j] (two rounded products), e_j the table's phasor at -j dphi; per component ONE chain over j ascending: re = fmaf(ex, ux,
-    re); re = fmaf(-ey, uy, re); im = fmaf(ex, uy, im); im = fmaf(ey, ux, im); then tune_pair's rotation at ph0 + (n + 1 - Dc)
-    dphi"""
-    Dc = _dc(P, Q)
-    Tb = 16 * Dc
-    t = frac + (np.arange(n_out, dtype=np.int64) + 1) * P
-    n, r = t // Q - 1, t % Q
-    assert n[0] >= 0 and n[-1] + 1 + Tb == len(xh)
-    dphi, ph0 = np.asarray(dphi, np.uint64), np.asarray(ph0, np.uint64)
-    xi, xq = xh[:, 0].astype(F32), xh[:, 1].astype(F32)
-    re = np.zeros((len(dphi), n_out), F32)
-    im = np.zeros((len(dphi), n_out), F32)
-    for j in range(Tb):
-        ph = ((np.uint64(1 << 32) - ((np.uint64(j) * dphi) & np.uint64(M32))) & np.uint64(M32)).astype(np.uint32)
-        ex, ey = phasor2(tab, ph)
-        ex, ey = ex[:, None], ey[:, None]
-        hj = h[j * Q + r]
-        ux, uy = (hj * xi[Tb + n - j])[None, :], (hj * xq[Tb + n - j])[None, :]
-        re = fma32(ex, ux, re)
-        re = fma32(-ey, uy, re)
-        im = fma32(ex, uy, im)
-        im = fma32(ey, ux, im)
-    k = ((n + 1 - Dc) % (1 << 32)).astype(np.uint64)
-    ph = ((ph0[:, None] + k[None, :] * dphi[:, None]) & np.uint64(M32)).astype(np.uint32)
-    c, s = phasor2(tab, ph)
-    sat = lambda v: np.clip(np.rint(v), -32768, 32767).astype(np.int16)
-    return np.stack([sat(fmaf(re, c, -(im * s))), sat(fmaf(im, c, re * s))], -1)
-
-
-def rate_stream(src_row, P, Q, h, steps, tab, cuts=None):
-    """receivers of one source over a stream from a reset: steps uint32-valued [R, n_blocks], the step of each receiver in
-    each block.  The stream is cut where a step changes and at `cuts` (blocks); frac, history and phases are carried ->
-    (int16 [R, n, 2], phases after)"""
-    steps = np.asarray(steps, np.uint64)
-    R, nb = steps.shape
-    Tb = 16 * _dc(P, Q)
-    marks = sorted({0, nb} | {b for b in range(1, nb) if np.any(steps[:, b] != steps[:, b - 1])} | set(cuts or ()))
-    x = np.concatenate([np.zeros((Tb, 2), np.int16), src_row])
-    ph = np.zeros(R, np.uint64)
-    out = []
-    for a, b in zip(marks[:-1], marks[1:]):
-        S = (a * 128 * P) // Q
-        frac, pairs = (a * 128 * P) % Q, (b * 128 * P) // Q - S
-        out.append(rate_rows(x[S:S + Tb + pairs], P, Q, frac, h, steps[:, a], ph, tab, (b - a) * 128))
-        ph = (ph + np.uint64(pairs) * steps[:, a]) & np.uint64(M32)
-    return np.concatenate(out, 1), ph
-
-
-def _lib_rate_taps(P, Q, gain=1.0):
-    from radiodsp_sdr_rx_amd.engine import rate_taps
-    return rate_taps(P, Q, gain)
-
-
-def _pairs(P, Q, n_blocks):
-    return (n_blocks * 128 * P) // Q
-
-
-def _wide_rate(seed, n_sources, n_blocks, P, Q, level=0.05):
-    """test_engine_ddc._wide at 44 100 P / Q Hz: int16 [n_sources, floor(n_blocks 128 P / Q), 2], in each twenty carriers
-    anywhere in the band, half of them modulated or keyed, and noise; source 0 starts with full-scale pairs"""
-    r = np.random.default_rng(seed)
-    fs, n, Dc = _fs(P, Q), _pairs(P, Q, n_blocks), _dc(P, Q)
-    t = np.arange(n)
-    out = np.zeros((n_sources, n, 2), np.int16)
-    for s in range(n_sources):
-        z = np.zeros(n, np.complex128)
-        for _ in range(20):
-            f = r.uniform(-0.49, 0.49) * fs
-            env = 1 + 0.5 * np.sin(2 * np.pi * r.uniform(100, 800) / fs * t) if r.random() < 0.5 else (np.sin(2 * np.pi * r.uniform(2, 9) / fs * t) > 0)
-            z += r.uniform(0.2, 1.0) * level * env * np.exp(2j * np.pi * f / fs * t + 1j * r.uniform(0, 6))
-        z += 0.3 * level * (r.standard_normal(n) + 1j * r.standard_normal(n))
-        out[s] = _int16(z * 32767)
-    out[0, :32 * Dc] = np.repeat(np.array([[-32768, 32767], [32767, -32768], [32767, 32767], [-32768, -32768]], np.int16), 8 * Dc, 0)
-    return out
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host_check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("rate") / "host_rate_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-I",
-                           os.path.join(ROOT, "radiodsp_sdr_rx_amd", "csrc"), os.path.join(HERE, "host", "host_rate_check.cpp"),
-                           "-o", exe])
-    return exe
+def host_check():
+    return host_program()
 
 
 def test_rate_filter_is_the_one_specified(rdsp):
     """rdsp_engine_rate_taps over RATES at gain 1: EQUAL BIT FOR BIT to the numpy evaluation of the same formula
-    (rate_taps_of above; no libm stands between the two); symmetric bit for bit; sum Q gain within the rounding of Tp floats
-    (Tp 2^-25 Q); ripple <= 0.001 dB on |f| <= 12 000 Hz; <= -89 dB from 32 100 Hz to the prototype's Nyquist frequency (the
+    (engine_sources_model.taps_of; no libm stands between the two); symmetric bit for bit; sum Q gain within the rounding of
+    Tp floats (Tp 2^-25 Q); ripple <= 0.001 dB on |f| <= 12 000 Hz; <= -89 dB from 32 100 Hz to the prototype's Nyquist frequency (the
     images of the source spectrum included); every branch's sum |hb[r][j]| <= 2.5 (the worst values are printed).  For Q = 1
     the taps are rdsp_engine_ddc_taps' bit for bit; (882, 294) is (3, 1); the refusals of the host-only call."""
-    from radiodsp_sdr_rx_amd.engine import ddc_taps
+    from radiodsp_sdr_rx_amd.engine import ddc_taps, rate_taps
     worst_ripple, worst_stop, worst_abs = 0.0, -1e9, 0.0
     for P, Q in RATES:
-        h = _lib_rate_taps(P, Q)
+        h = lib_taps(P, Q)
         Tb = 16 * _dc(P, Q)
         Tp = Tb * Q
         assert h.dtype == F32 and len(h) == Tp and np.array_equal(h, h[::-1]), (P, Q)
-        assert np.array_equal(h.view(np.uint32), rate_taps_of(P, Q).view(np.uint32)), (P, Q)
+        assert np.array_equal(h.view(np.uint32), taps_of(P, Q).view(np.uint32)), (P, Q)
         assert abs(float(h.astype(np.float64).sum()) - Q) <= Tp * 2.0 ** -25 * Q, (P, Q)
         fs = 44100.0 * P                                             # the prototype's rate
         nfft = 1 << int(math.ceil(math.log2(16 * Tp)))
@@ -167,11 +52,11 @@ def test_rate_filter_is_the_one_specified(rdsp):
         assert ripple <= 0.001 and stop <= -89.0 and branch <= 2.5, (P, Q, ripple, stop, branch)
         worst_ripple, worst_stop, worst_abs = max(worst_ripple, ripple), max(worst_stop, stop), max(worst_abs, branch)
     print(f"rate taps: worst ripple {worst_ripple:.6f} dB, worst stop band {worst_stop:.2f} dB, worst branch sum |h| {worst_abs:.3f}")
-    assert np.array_equal(_lib_rate_taps(160, 147, 37.5).view(np.uint32), rate_taps_of(160, 147, 37.5).view(np.uint32))
+    assert np.array_equal(lib_taps(160, 147, 37.5).view(np.uint32), taps_of(160, 147, 37.5).view(np.uint32))
     for D in (2, 16, 64):
-        assert np.array_equal(_lib_rate_taps(D, 1, 2.5).view(np.uint32), ddc_taps(D, 2.5).view(np.uint32)), D
-        assert np.array_equal(_lib_rate_taps(D, 1, 2.5).view(np.uint32), taps_of(D, 2.5).view(np.uint32)), D
-    assert np.array_equal(_lib_rate_taps(882, 294, 1.5).view(np.uint32), ddc_taps(3, 1.5).view(np.uint32))
+        assert np.array_equal(rate_taps(D, 1, 2.5).view(np.uint32), ddc_taps(D, 2.5).view(np.uint32)), D
+        assert np.array_equal(rate_taps(D, 1, 2.5).view(np.uint32), taps_of(D, 1, 2.5).view(np.uint32)), D
+    assert np.array_equal(rate_taps(882, 294, 1.5).view(np.uint32), ddc_taps(3, 1.5).view(np.uint32))
     lib = rdsp.load()
     o = np.zeros(16 * 64 * 441, F32)
     p = o.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
@@ -228,12 +113,12 @@ def test_rate_schedule(host_check, tmp_path, P, Q):
 
 @pytest.mark.parametrize("P,Q", [(3, 2), (160, 147), (2500, 441), (8000, 147)])
 def test_rate_numpy_restatement_is_the_headers_arithmetic(host_check, tmp_path, rdsp, P, Q):
-    """rate_rows / rate_taps_of / schedule / dphi_of against rdsp_tune.h compiled on the host, bit for bit: 256 outputs of 24
+    """rate_rows / taps_of / schedule / dphi_of against rdsp_tune.h compiled on the host, bit for bit: 256 outputs of 24
     receivers from a NON-ZERO frac (37 outputs into a stream) at the steps of drawn stations in every mode (anywhere in |f| <
     22 050 P / Q, and 0, and the band's edges) from drawn phases, on a drawn row under a gain of 3 with edge pairs (+-32767,
     -32768, 0, +-1 in every combination), full-scale stretches that saturate, and a history; the host check's own checks
     (Q = 1 is the decimating pass's filter, step and window; the schedule over calls; the limits; the DC gain) pass too"""
-    out = subprocess.run([host_check], capture_output=True, text=True)
+    out = subprocess.run([host_check, "check"], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.rstrip().endswith("OK"), out.stdout + out.stderr
     r = np.random.default_rng(100 + P)
     n_out, n_rx, gain, m0 = 256, 24, 3.0, 37
@@ -252,22 +137,15 @@ def test_rate_numpy_restatement_is_the_headers_arithmetic(host_check, tmp_path, 
     stations = np.concatenate([r.uniform(-lim + 1, lim - 1, n_rx - 4), [0.0, 8390.0, lim - 0.1, -lim + 0.1]])
     modes = np.arange(n_rx) % 7
     to = np.array([TUNING_OFFSET[int(m)] for m in modes], F32)
-    dphi = np.array([dphi_of(t, s, _fs(P, Q)) for t, s in zip(to, stations)], np.uint64)
+    dphi = np.array([dphi_of(t, s, P, Q) for t, s in zip(to, stations)], np.uint64)
     ph0 = r.integers(0, 1 << 32, n_rx, dtype=np.uint64)
     ph0[:3] = 0
-    np.concatenate([[P, Q, frac, n_out, n_rx], np.stack([dphi, ph0], 1).reshape(-1)]).astype(np.uint32).tofile(tmp_path / "params.bin")
-    np.array([gain], F32).tofile(tmp_path / "gain.bin")
-    xh.tofile(tmp_path / "src.bin")
-    to.tofile(tmp_path / "to.bin")
-    stations.astype(np.float64).tofile(tmp_path / "station.bin")
-    out = subprocess.run([host_check, "rows", str(tmp_path)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    tab = _table(rdsp)
+    want = host_rows(host_check, tmp_path, S16, xh[Tb:], xh[:Tb], P, Q, frac, gain, dphi, ph0, n_out, to, stations)
+    tab = table(rdsp)
     h = np.fromfile(tmp_path / "taps.bin", F32)
-    assert np.array_equal(h.view(np.uint32), rate_taps_of(P, Q, gain).view(np.uint32))
-    assert np.array_equal(h.view(np.uint32), _lib_rate_taps(P, Q, gain).view(np.uint32))
+    assert np.array_equal(h.view(np.uint32), taps_of(P, Q, gain).view(np.uint32))
+    assert np.array_equal(h.view(np.uint32), lib_taps(P, Q, gain).view(np.uint32))
     assert list(np.fromfile(tmp_path / "dphi.bin", np.uint32)) == [int(d) for d in dphi]
-    want = np.fromfile(tmp_path / "out.bin", np.uint32).reshape(n_rx, n_out)
     rows = rate_rows(xh, P, Q, frac, h, dphi, ph0, tab, n_out)
     got = np.ascontiguousarray(rows).view(np.uint32)[..., 0]
     assert np.array_equal(got, want), np.argwhere(got != want)[:4]
@@ -286,17 +164,17 @@ def test_rate_restatement_against_exact_arithmetic(rdsp, P, Q):
     component where the decimating pass's h c did: 2^-24 A; the chain of 2 Tb fmaf per component, each rounding a partial
     sum of at most A: 2 Tb x 2^-24 A; the rotation's product and its fmaf: 2 x 2^-24 A; one more 2^-24 A for every
     second-order term: gamma = (2 Tb + 4) 2^-24."""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     assert _phasor_modulus_error(tab) < 2.0 ** -17
     Dc = _dc(P, Q)
     Tb, nb, gain = 16 * Dc, 6, 2.0
-    src = _wide_rate(7 + P, 1, nb, P, Q, level=0.08)[0]
-    h = _lib_rate_taps(P, Q, gain)
+    src = wide(7 + P, 1, nb, P, Q, level=0.08)[0]
+    h = lib_taps(P, Q, gain)
     r = np.random.default_rng(P)
     lim = (22050.0 * P) / Q
     stations = np.concatenate([r.uniform(-lim + 1, lim - 1, 4), [0.0, lim - 1.0]])
-    dphi = np.array([dphi_of(TUNING_OFFSET[m % 7], s, _fs(P, Q)) for m, s in enumerate(stations)], np.uint64)
-    got, _ = rate_stream(src, P, Q, h, np.repeat(dphi[:, None], nb, 1), tab)
+    dphi = np.array([dphi_of(TUNING_OFFSET[m % 7], s, P, Q) for m, s in enumerate(stations)], np.uint64)
+    got, _ = stream(src, P, Q, h, np.repeat(dphi[:, None], nb, 1), tab)
     n_out = nb * 128
     _, _, n, br = schedule(P, Q, 0, n_out)
     x = np.concatenate([np.zeros(Tb), src[:, 0].astype(np.float64) + 1j * src[:, 1].astype(np.float64)])
@@ -327,15 +205,15 @@ def test_rate_is_a_receiver_at_2400_kHz(rdsp):
     at station - TuningOffset + 44 100 + 7 890 Hz, which the shift puts at 51 990 Hz and the resampling would fold onto 7 890 Hz
     in the IF band: no sample of the tuned row moves by more than 2 counts (0.9 x 32767 x 10^(-89 / 20) = 1.05 before
     rounding; test_engine_ddc's derivation)"""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     P, Q, nb = 8000, 147, 36
     fs, n = _fs(P, Q), _pairs(P, Q, nb)
     assert fs == 2400000.0
-    h = _lib_rate_taps(P, Q)
+    h = lib_taps(P, Q)
     to = TUNING_OFFSET[1]
-    steps = np.full((1, nb), dphi_of(to, 600000.0, fs), np.uint64)
+    steps = np.full((1, nb), dphi_of(to, 600000.0, P, Q), np.uint64)
     amp = 0.25 * 32767
-    y = rate_stream(_int16(_tone(601000.0, n, fs, amp)), P, Q, h, steps, tab)[0][0]
+    y = stream(_int16(_tone(601000.0, n, fs, amp)), P, Q, h, steps, tab)[0][0]
     z = (y[128:128 + 4410, 0] + 1j * y[128:128 + 4410, 1]).astype(np.complex128)
     spec = np.abs(np.fft.fft(z))
     peak = int(np.argmax(spec))
@@ -348,8 +226,8 @@ def test_rate_is_a_receiver_at_2400_kHz(rdsp):
     assert 20 * np.log10(rest / spec[peak]) <= -85.0
     f_int = 600000.0 - to + 44100.0 + 7890.0
     a = 0.09 * 32767
-    clean = rate_stream(_int16(_tone(601000.0, n, fs, a)), P, Q, h, steps, tab)[0][0]
-    dirty = rate_stream(_int16(_tone(601000.0, n, fs, a) + _tone(f_int, n, fs, 0.9 * 32767, 1.0)), P, Q, h, steps, tab)[0][0]
+    clean = stream(_int16(_tone(601000.0, n, fs, a)), P, Q, h, steps, tab)[0][0]
+    dirty = stream(_int16(_tone(601000.0, n, fs, a) + _tone(f_int, n, fs, 0.9 * 32767, 1.0)), P, Q, h, steps, tab)[0][0]
     moved = np.abs(dirty.astype(int) - clean.astype(int))[16:].max()       # behind the filter's own length
     print(f"rate receiver: the folding interferer moves a sample by at most {moved} counts")
     assert moved <= 2
@@ -359,86 +237,22 @@ def test_rate_is_a_receiver_at_2400_kHz(rdsp):
 def test_rate_restatement_does_not_depend_on_the_call_split(rdsp, P, Q):
     """32 blocks in one call, against calls of 1, 7 and 32 blocks with frac, the history and the phases carried: sample for
     sample; and the phases after the stream are the closed form floor(M P / Q) x dphi"""
-    tab = _table(rdsp)
+    tab = table(rdsp)
     nb = 32
-    src = _wide_rate(3, 1, nb, P, Q)[0]
-    h = _lib_rate_taps(P, Q, 1.5)
+    src = wide(3, 1, nb, P, Q)[0]
+    h = lib_taps(P, Q, 1.5)
     r = np.random.default_rng(4)
     lim = (22000.0 * P) / Q
-    dphi = np.array([dphi_of(TUNING_OFFSET[m], s, _fs(P, Q)) for m, s in zip((0, 1, 4), r.uniform(-lim, lim, 3))], np.uint64)
+    dphi = np.array([dphi_of(TUNING_OFFSET[m], s, P, Q) for m, s in zip((0, 1, 4), r.uniform(-lim, lim, 3))], np.uint64)
     steps = np.repeat(dphi[:, None], nb, 1)
-    whole, ph = rate_stream(src, P, Q, h, steps, tab)
+    whole, ph = stream(src, P, Q, h, steps, tab)
     assert [int(p) for p in ph] == [(((nb * 128 * P) // Q) * int(d)) & M32 for d in dphi]
     for split in (1, 7, 32):
-        cut, ph2 = rate_stream(src, P, Q, h, steps, tab, cuts=range(0, nb, split))
+        cut, ph2 = stream(src, P, Q, h, steps, tab, cuts=range(0, nb, split))
         assert np.array_equal(cut, whole) and np.array_equal(ph, ph2), split
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-class _RxR(_Rx):
-    """test_engine_tuning._Rx on sources at 44 100 P / Q Hz: the engine's rate is set between set_sources and the first tune,
-    the steps are per source sample, a call takes source_pairs(n_blocks) pairs of every row from where the last call stopped
-    -- a view into the one long device buffer, no copy -- and the restated rows are rate_stream's (all receivers of a source
-    at once).  odd: every call's rows start at an odd pair offset of a second long buffer (4-byte alignment only)."""
-
-    def __init__(self, eng, src, source_of, firsts, stations, P, Q, gain, odd=False):
-        import torch
-        self.eng, self.src, self.n, self.P, self.Q, self.gain, self.odd = eng, src, eng.n_channels, P, Q, gain, odd
-        self.source_of = [int(s) for s in source_of]
-        eng.set_sources(src.shape[0], self.source_of)
-        eng.set_source_rate(P, Q, gain)
-        assert eng.source_rate() == (P, Q) and eng.source_decimation() == 0
-        self.firsts, self.modes = [0], [0]
-        self.set_groups(firsts)
-        self.station = np.zeros(self.n)
-        self.tune(0, stations)
-        self.calls = [[] for _ in range(self.n)]
-        self.steps = [[] for _ in range(self.n)]
-        self.d = torch.from_numpy(src).cuda()
-        self.long = torch.zeros((src.shape[0], src.shape[1] + 2 * 128 + 64, 2), dtype=torch.int16, device="cuda") if odd else None
-        self.at = 1                                          # where the next call's rows start in self.long
-        self.nb = (src.shape[1] * Q + Q - 1) // (128 * P)    # whole blocks the source rows hold
-        self.outs = []
-        self.tab = eng.tune_table()
-        self.h = _lib_rate_taps(P, Q, gain)
-        self.rows = {}
-
-    def run(self, a, b, split):
-        P, Q = self.P, self.Q
-        a, b = min(a, self.nb), min(b, self.nb)              # a script written for more blocks than the source has
-        for u in range(a, b, split):
-            v = min(b, u + split)
-            for c in range(self.n):
-                self.steps[c] += [dphi_of(TUNING_OFFSET[self.modes[self.group_of(c)]], self.station[c], _fs(P, Q))] * (v - u)
-            S, pairs = (u * 128 * P) // Q, (v * 128 * P) // Q - (u * 128 * P) // Q
-            assert self.eng.source_pairs(v - u) == pairs
-            rows = self.d[:, S:S + pairs]
-            if self.odd:
-                self.long[:, self.at:self.at + pairs].copy_(rows)
-                rows = self.long[:, self.at:self.at + pairs]
-                assert (rows.data_ptr() // 4) % 2 == 1 and not rows.is_contiguous()
-                self.at += pairs
-                self.at += (self.at + 1) % 2               # odd again
-            self.outs.append(self.eng.update_sources(rows, n_blocks=v - u))
-
-    def restate(self, channels):
-        for s in sorted({self.source_of[c] for c in channels}):
-            cs = [c for c in channels if self.source_of[c] == s and c not in self.rows]
-            if cs:
-                y, _ = rate_stream(self.src[s], self.P, self.Q, self.h, np.array([self.steps[c] for c in cs], np.uint64), self.tab)
-                self.rows.update(zip(cs, y))
-
-    def want(self, c):
-        import oracle_lib
-        self.restate([c])
-        return oracle_lib.OracleEngine().run(self.rows[c], self.calls[c])
-
-    def check(self, y, channels=None):
-        channels = list(range(self.n) if channels is None else channels)
-        self.restate(channels)
-        super().check(y, channels)
-
-
 _stream_cache = {}
 
 
@@ -448,21 +262,20 @@ _stream_cache = {}
 def test_gpu_rate_against_the_restatement(rdsp, P, Q, split):
     """3 sources x 97 receivers (the sources' workgroups ragged) at stations anywhere in |f| < 22 050 P / Q, gain 2.5, 40
     blocks (24 at 8000 / 147) cut into calls of `split`, with a retune, a regrouping and mode changes in mid-stream
-    (test_engine_ddc._script_97): every receiver against the restatement of its own row and calls, bit for bit.  The calls
+    (engine_sources_model._script_97): every receiver against the restatement of its own row and calls, bit for bit.  The calls
     walk through one long device buffer without a copy; in the 7-block runs every call's rows start at an odd pair offset
     (rows 4-byte aligned only).  What the CPU side computes does not depend on the split: once per rate."""
     nch, nb, gain = 97, (24 if (P, Q) == (8000, 147) else 40), 2.5
     r = np.random.default_rng(20 + P)
-    src = _wide_rate(40 + P, 3, nb, P, Q)
+    src = wide(40 + P, 3, nb, P, Q)
     source_of = r.integers(0, 3, nch)
     lim = (22050.0 * P) / Q
     stations = r.uniform(-lim + 1, lim - 1, nch)
     stations[:3] = [lim - 0.5, -lim + 0.5, 0.0]
-    eng = _engine(nch, 32)
+    eng = engine(nch, 32)
     eng.sketch_setup()
-    R = _RxR(eng, src, source_of, [0, 19, 40, 58, 77], stations, P, Q, gain, odd=split == 7)
+    R = Rx(eng, src, source_of, [0, 19, 40, 58, 77], stations, P, Q, gain, odd=split == 7)
     assert R.nb == nb
-    R.D = float(P) / Q                                       # _script_97 draws its retunes inside D x 22 050
     _script_97(R, split, nb)
     y = R.result()
     if (P, Q) not in _stream_cache:
@@ -482,11 +295,11 @@ def test_gpu_rate_more_than_a_workgroup_of_receivers_on_one_source(rdsp):
     receiver, none has two): the first and the last receiver of each workgroup, of each wave's half and of each lane block,
     bit for bit"""
     P, Q, nch, nb = 160, 147, 300, 4
-    src = _wide_rate(11, 1, nb, P, Q)
+    src = wide(11, 1, nb, P, Q)
     lim = (22050.0 * P) / Q
-    eng = _engine(nch, nb)
+    eng = engine(nch, nb)
     eng.sketch_setup()
-    R = _RxR(eng, src, [0] * nch, [0], np.random.default_rng(12).uniform(-lim + 1, lim - 1, nch), P, Q, 2.0)
+    R = Rx(eng, src, [0] * nch, [0], np.random.default_rng(12).uniform(-lim + 1, lim - 1, nch), P, Q, 2.0)
     R.run(0, nb, nb)
     R.check(R.result(), [0, 1, 63, 64, 127, 128, 191, 192, 254, 255, 256, 257, 298, 299])
     eng.close()
@@ -498,11 +311,10 @@ def test_gpu_rate_q_one_is_the_integer_pass(rdsp):
     source_rate() (5, 1); after a rational rate source_decimation() is 0; a later set_source_decimation replaces the
     rational rate (the audio is again that of an engine that only ever had D = 5)"""
     import torch
-    from test_engine_ddc import _wide
     D, nb, g = 5, 8, 2.0
-    src = torch.from_numpy(_wide(31, 2, nb, D)).cuda()
+    src = torch.from_numpy(wide(31, 2, nb, D)).cuda()
     st = np.random.default_rng(5).uniform(-D * 22000.0, D * 22000.0, 6)
-    engs = [_engine(6, nb) for _ in range(3)]
+    engs = [engine(6, nb) for _ in range(3)]
     for k, e in enumerate(engs):
         e.sketch_setup()
         e.set_sources(2, [0, 1, 1, 0, 1, 0])
@@ -533,11 +345,11 @@ def test_gpu_rate_reset_and_state_as_data(rdsp):
     P, Q, nb, k, gain = 160, 147, 24, 9, 2.0
     assert (k * 128 * P) % Q != 0
     r = np.random.default_rng(9)
-    src = _wide_rate(61, 2, nb, P, Q)
+    src = wide(61, 2, nb, P, Q)
     lim = (22050.0 * P) / Q
-    a = _engine(6, 8)
+    a = engine(6, 8)
     a.sketch_setup()
-    A = _RxR(a, src, [0, 1, 1, 0, 1, 0], [0], r.uniform(-lim + 1, lim - 1, 6), P, Q, gain)
+    A = Rx(a, src, [0, 1, 1, 0, 1, 0], [0], r.uniform(-lim + 1, lim - 1, 6), P, Q, gain)
     A.run(0, nb, 8)
     first = A.result()
     A.check(first)
@@ -549,9 +361,9 @@ def test_gpu_rate_reset_and_state_as_data(rdsp):
     assert a.source_pairs(8) == _pairs(P, Q, 8)
     A.run(0, nb, 8)
     assert np.array_equal(A.result(), first)
-    fresh = _engine(6, 8)
+    fresh = engine(6, 8)
     fresh.sketch_setup()
-    Fr = _RxR(fresh, src, A.source_of, [0], A.station, P, Q, gain)
+    Fr = Rx(fresh, src, A.source_of, [0], A.station, P, Q, gain)
     Fr.run(0, 1, 8)
     assert np.array_equal(Fr.result(), first[:, :128])
     # state as data: a runs 9 blocks, b hears the same 9 blocks with receivers of its own, then takes a's channels 2, 3
@@ -561,9 +373,9 @@ def test_gpu_rate_reset_and_state_as_data(rdsp):
     blob = a.save_state(2, 2)
     assert blob.size == a.lib.rdsp_engine_state_bytes(a.h, 2) == 16 + 2 * (10368 + 4)
     assert list(blob[:16].view(np.uint32)) == [0x45534452, 1, 2, 1]
-    b = _engine(9, 16)
+    b = engine(9, 16)
     b.sketch_setup()
-    B = _RxR(b, src, [0] * 5 + [1, 0] + [1] * 2, [0], r.uniform(-lim + 1, lim - 1, 9), P, Q, gain)
+    B = Rx(b, src, [0] * 5 + [1, 0] + [1] * 2, [0], r.uniform(-lim + 1, lim - 1, 9), P, Q, gain)
     B.tune(5, A.station[2:4])
     B.run(0, k, 16)
     b.load_state(5, blob)
@@ -582,9 +394,9 @@ def test_gpu_rate_refusals(rdsp):
     import torch
     from radiodsp_sdr_rx_amd._lib import RdspError
     P, Q = 160, 147
-    src = torch.from_numpy(_wide_rate(95, 2, 16, P, Q)).cuda()
+    src = torch.from_numpy(wide(95, 2, 16, P, Q)).cuda()
     out = torch.empty((4, 8 * 128, 2), dtype=torch.int16, device="cuda")
-    eng, twin = _engine(4, 8), _engine(4, 8)
+    eng, twin = engine(4, 8), engine(4, 8)
     for e in (eng, twin):
         e.sketch_setup()
     with pytest.raises(RdspError) as ex:

@@ -12,9 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_engine_formats import S16, U8, _raw_of, _setup, _stations, _stream
-from test_engine_rate import _wide_rate
-from test_engine_tuning import HERE, ROOT
+from engine_sources_model import HERE, ROOT, S16, U8, _raw_of, _setup, _stations, _stream, wide
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
@@ -42,7 +40,7 @@ SOURCE_OF = [0] * 17 + [1] * 2      # the decimating pass: a full workgroup of 1
 
 def _rows(seed, n_sources, n_blocks, P, Q, fmt):
     import torch
-    return torch.from_numpy(_raw_of(fmt, _wide_rate(seed, n_sources, n_blocks, P, Q, level=0.3))).cuda()
+    return torch.from_numpy(_raw_of(fmt, wide(seed, n_sources, n_blocks, P, Q, level=0.3))).cuda()
 
 
 @pytest.mark.gpu

@@ -1,86 +1,26 @@
 """rdsp_engine_t on shared IQ streams: receivers tuned to stations inside a few source rows (rdsp_engine_set_sources /
 rdsp_engine_tune / rdsp_engine_update_sources, include/rdsp.h).
 
-`-m "not gpu"`: csrc/rdsp_tune.h compiled on the host (tests/host/host_tune_check.cpp, -ffp-contract=off as the kernel is):
-the phasor table gives exactly (1, 0) at phase 0 and stays within 2^-17 of cos / sin, a shift of 0 is the identity, full-scale
-rotations saturate, the accumulator after calls of any size is the closed form; and the numpy restatement below is that
-header's arithmetic bit for bit, its table the library's.
+`-m "not gpu"`: csrc/rdsp_tune.h compiled on the host (tests/host/host_source_pass_check.cpp, -ffp-contract=off as the kernel
+is): the phasor table gives exactly (1, 0) at phase 0 and stays within 2^-17 of cos / sin, a shift of 0 is the identity,
+full-scale rotations saturate, the accumulator after calls of any size is the closed form; and the numpy restatement
+(tests/engine_sources_model.py) is that header's arithmetic bit for bit, its table the library's.
 `-m gpu`: the audio of every receiver, bit for bit, against the CPU restatement of the engine (oracle_lib.OracleEngine) run
 on the restated tuned row -- which is the image's arithmetic (tests/test_engine_kat.py) -- across call splits, retunes, mode
 changes, regroupings, state moved between objects, and the refusals."""
-import math
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-M32 = (1 << 32) - 1
-TUNING_OFFSET = {0: 8390.0, 1: 5390.0, 2: 7390.0, 3: 6390.0, 4: 6890.0, 5: 6890.0, 6: 5390.0}   # setDemodMode's answers
-
-
-# ---- the restatement in numpy ---------------------------------------------------------------------------------------------
-def dphi_of(tuning_offset, station_hz):
-    """round((TuningOffset - station) 2^32 / 44100), half away from zero, mod 2^32"""
-    x = (float(np.float32(tuning_offset)) - float(station_hz)) * 4294967296.0 / 44100.0
-    a = abs(x)
-    r = math.floor(a)
-    if a - r >= 0.5:
-        r += 1
-    return (r if x >= 0 else -r) & M32
-
-
-def fmaf(a, b, c):
-    """float32 fused multiply-add, exact: a b is exact in double; the double sum's rounding error (TwoSum) decides the
-    one case where rounding that sum to float32 differs from rounding the exact value -- the sum landing on a midpoint"""
-    a, b, c = (np.asarray(v, np.float32) for v in (a, b, c))
-    p = a.astype(np.float64) * b.astype(np.float64)
-    cd = c.astype(np.float64)
-    s = p + cd
-    bv = s - p
-    err = (p - (s - bv)) + (cd - bv)
-    r = s.astype(np.float32)
-    rd = r.astype(np.float64)
-    other = np.where(s > rd, np.nextafter(r, np.float32(np.inf)), np.nextafter(r, np.float32(-np.inf)))
-    od = other.astype(np.float64)
-    tie = (s != rd) & ((rd + od) * 0.5 == s) & (err != 0)
-    return np.where(tie & (np.sign(err) == np.sign(od - rd)), other, r)
-
-
-def phasor(tab, ph):
-    ph = np.asarray(ph, np.uint32)
-    t = tab[(ph >> 22).astype(np.int64)]
-    f = (ph & 0x3FFFFF).astype(np.float32) * np.float32(2.0 ** -22)
-    return fmaf(f, t[:, 2], t[:, 0]), fmaf(f, t[:, 3], t[:, 1])
-
-
-def tune_pairs(iq, ph, tab):
-    """int16 [n, 2] pairs times e^{+j 2 pi ph / 2^32}: I' = fmaf(I, c, -(Q s)), Q' = fmaf(Q, c, I s), rne, saturate"""
-    c, s = phasor(tab, ph)
-    i, q = iq[:, 0].astype(np.float32), iq[:, 1].astype(np.float32)
-    sat = lambda v: np.clip(np.rint(v), -32768, 32767).astype(np.int16)
-    return np.stack([sat(fmaf(i, c, -(q * s))), sat(fmaf(q, c, i * s))], 1)
-
-
-def tuned_row(src, dphi_blocks, tab, phase0=0):
-    """a receiver's row: block b of its source row at steps dphi_blocks[b], the phase continuous from phase0"""
-    d = np.asarray(dphi_blocks, np.uint64)
-    starts = (np.uint64(phase0) + np.concatenate([np.zeros(1, np.uint64), np.cumsum(d * np.uint64(128))[:-1]])) & np.uint64(M32)
-    ph = (starts[:, None] + np.arange(128, dtype=np.uint64)[None, :] * d[:, None]) & np.uint64(M32)
-    ph = ph.astype(np.uint32).reshape(-1)
-    return tune_pairs(src[:len(ph)], ph, tab)
+from engine_sources_model import HERE, TUNING_OFFSET, Rx, _band, dphi_of, engine, host_program, tune_pairs, tuned_row
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host_check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("tune") / "host_tune_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-I",
-                           os.path.join(ROOT, "radiodsp_sdr_rx_amd", "csrc"), os.path.join(HERE, "host", "host_tune_check.cpp"),
-                           "-o", exe])
-    return exe
+def host_check():
+    return host_program()
 
 
 def test_tuning_arithmetic_on_the_host(host_check):
@@ -88,7 +28,7 @@ def test_tuning_arithmetic_on_the_host(host_check):
     million random phases; shift 0 the identity on the edge pairs (+-32767, -32768, 0, ...) and a million random pairs; the
     full-scale pairs saturate at every rotation; the accumulator after calls of 1 ... 128 blocks is ph0 + total dphi; a tone
     at +5000 Hz tuned for USB comes out at the USB tuning offset, 5390 Hz"""
-    out = subprocess.run([host_check], capture_output=True, text=True)
+    out = subprocess.run([host_check, "check"], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.rstrip().endswith("OK"), out.stdout + out.stderr
 
 
@@ -128,95 +68,6 @@ def test_numpy_restatement_is_the_headers_arithmetic(host_check, tmp_path, rdsp)
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _engine(n_channels, max_blocks):
-    from radiodsp_sdr_rx_amd.engine import Engine
-    import oracle_lib
-    return Engine(n_channels, max_blocks_per_call=max_blocks, tables=oracle_lib.engine_tables())
-
-
-def _band(seed, n_sources, n_blocks):
-    """int16 [n_sources, n, 2]: in each, a dozen carriers and tones anywhere in the band, some keyed, and noise"""
-    r = np.random.default_rng(seed)
-    t = np.arange(n_blocks * 128)
-    out = np.zeros((n_sources, len(t), 2), np.int16)
-    for s in range(n_sources):
-        z = np.zeros(len(t), np.complex128)
-        for _ in range(12):
-            f = r.uniform(-21000, 21000)
-            env = 1 + 0.5 * np.sin(2 * np.pi * r.uniform(100, 800) / 44100.0 * t) if r.random() < 0.5 else (np.sin(2 * np.pi * r.uniform(2, 9) / 44100.0 * t) > 0)
-            z += r.uniform(0.01, 0.12) * env * np.exp(2j * np.pi * f / 44100.0 * t + 1j * r.uniform(0, 6))
-        z += 0.02 * (r.standard_normal(len(t)) + 1j * r.standard_normal(len(t)))
-        out[s, :, 0] = np.clip(np.round(z.real * 32767), -32768, 32767)
-        out[s, :, 1] = np.clip(np.round(z.imag * 32767), -32768, 32767)
-    out[0, :64] = [[-32768, 32767], [32767, -32768]] * 32                               # full-scale pairs: saturation
-    return out
-
-
-class _Rx:
-    """an engine on shared sources, and what the CPU needs to restate each receiver: per block the step its group's mode
-    and its station gave it, and the setter calls that reached it (as OracleEngine.run takes them).  The engine has had
-    sketch_setup(): every group starts in LSB."""
-
-    def __init__(self, eng, src, source_of, firsts, stations):
-        import torch
-        self.eng, self.src, self.n = eng, src, eng.n_channels
-        self.source_of = [int(s) for s in source_of]
-        eng.set_sources(src.shape[0], self.source_of)
-        self.firsts, self.modes = [0], [0]
-        self.set_groups(firsts)
-        self.station = np.zeros(self.n)
-        self.tune(0, stations)
-        self.calls = [[] for _ in range(self.n)]
-        self.steps = [[] for _ in range(self.n)]
-        self.d = torch.from_numpy(src).cuda()
-        self.outs = []
-        self.tab = eng.tune_table()
-
-    def group_of(self, c):
-        return max(g for g, f in enumerate(self.firsts) if f <= c)
-
-    def set_groups(self, firsts):
-        self.modes = [self.modes[self.group_of(f)] for f in firsts]
-        self.eng.set_groups(firsts)
-        self.firsts = list(firsts)
-
-    def tune(self, first, stations):
-        self.eng.tune(first, stations)
-        self.station[first:first + len(stations)] = stations
-
-    def call(self, block, group, name, *args):
-        self.eng.select_group(group)
-        getattr(self.eng, name)(*args)
-        self.eng.select_group(-1)
-        groups = range(len(self.firsts)) if group < 0 else [group]
-        for g in groups:
-            if name == "setDemodMode" and args[0] in TUNING_OFFSET:
-                self.modes[g] = args[0]
-            for c in range(self.firsts[g], (self.firsts + [self.n])[g + 1]):
-                self.calls[c].append([block, name] + list(args))
-
-    def run(self, a, b, split):
-        for u in range(a, b, split):
-            v = min(b, u + split)
-            for c in range(self.n):
-                self.steps[c] += [dphi_of(TUNING_OFFSET[self.modes[self.group_of(c)]], self.station[c])] * (v - u)
-            self.outs.append(self.eng.update_sources(self.d[:, u * 128:v * 128].contiguous()))
-
-    def result(self):
-        import torch
-        y = torch.cat(self.outs, 1).cpu().numpy()
-        assert np.array_equal(y[..., 0], y[..., 1])
-        return y[..., 0]
-
-    def want(self, c):
-        import oracle_lib
-        row = tuned_row(self.src[self.source_of[c]], self.steps[c], self.tab)
-        return oracle_lib.OracleEngine().run(row, self.calls[c])
-
-    def check(self, y, channels=None):
-        for c in (range(self.n) if channels is None else channels):
-            w = self.want(c)
-            assert np.array_equal(y[c], w), (c, int(np.argmax(y[c] != w)))
 
 
 @pytest.mark.gpu
@@ -230,7 +81,7 @@ def test_gpu_tuning_shift_zero_is_update_on_the_fixture(rdsp):
     for name in [str(n) for n in kat["case_names"]]:
         iq, calls, want = kat[name + "_iq"], json.loads(str(kat[name + "_calls"])), kat[name + "_out"]
         nb = len(iq) // 128
-        eng = _engine(2, 16)
+        eng = engine(2, 16)
         to = eng.sketch_setup()
         eng.set_sources(1, [0, 0])
         eng.tune(0, [to, to])
@@ -261,9 +112,9 @@ def test_gpu_tuning_against_the_restatement(rdsp, split):
     src = _band(40, 3, nb)
     source_of = r.integers(0, 3, nch)
     firsts = [0, 19, 40, 58, 77]
-    eng = _engine(nch, 64)
+    eng = engine(nch, 64)
     eng.sketch_setup()
-    R = _Rx(eng, src, source_of, firsts, r.uniform(-21500, 21500, nch))
+    R = Rx(eng, src, source_of, firsts, r.uniform(-21500, 21500, nch))
     for g, m in enumerate([0, 1, 2, 4, 5]):
         R.call(0, g, "setDemodMode", m)
     R.run(0, 90, split)
@@ -284,9 +135,9 @@ def test_gpu_tuning_sign_convention(rdsp):
     t = np.arange(96 * 128)
     z = 0.2 * np.exp(2j * np.pi * 6000.0 / 44100.0 * t) + 0.2 * np.exp(2j * np.pi * -7400.0 / 44100.0 * t + 1.0)
     src = np.stack([np.round(z.real * 32767), np.round(z.imag * 32767)], 1).astype(np.int16)[None]
-    eng = _engine(2, 32)
+    eng = engine(2, 32)
     eng.sketch_setup()
-    R = _Rx(eng, src, [0, 0], [0], [5000.0, -8000.0])
+    R = Rx(eng, src, [0, 0], [0], [5000.0, -8000.0])
     R.call(0, -1, "setDemodMode", 1)
     R.run(0, 96, 32)
     y = R.result()
@@ -308,9 +159,9 @@ def test_gpu_tuning_at_the_bench_shape(rdsp):
     from radiodsp_sdr_rx_amd.chain import synth_iq
     nch, nblk, nsrc = 4096, 32, 256
     src = synth_iq(nsrc, 2 * nblk * 128, n_threads=8)
-    eng = _engine(nch, nblk)
+    eng = engine(nch, nblk)
     eng.sketch_setup()
-    R = _Rx(eng, src, np.arange(nch) % nsrc, [0], np.random.default_rng(5).uniform(-21000, 21000, nch))
+    R = Rx(eng, src, np.arange(nch) % nsrc, [0], np.random.default_rng(5).uniform(-21000, 21000, nch))
     R.run(0, 2 * nblk, nblk)
     y = R.result()
     by_source = lambda p: (p % 16) * nsrc + p // 16        # the receiver at position p of the pass's order (4 per workgroup)
@@ -327,9 +178,9 @@ def test_gpu_tuning_regroup_keeps_every_receiver_on_its_station(rdsp):
     nch, nb = 20, 160
     r = np.random.default_rng(8)
     src = _band(50, 2, nb)
-    eng = _engine(nch, 8)
+    eng = engine(nch, 8)
     eng.sketch_setup()
-    R = _Rx(eng, src, r.integers(0, 2, nch), [0], r.uniform(-21000, 21000, nch))
+    R = Rx(eng, src, r.integers(0, 2, nch), [0], r.uniform(-21000, 21000, nch))
     R.run(0, 12, 8)
     R.set_groups([0, 7, 13])
     for g, m in ((1, 1), (2, 4)):
@@ -357,16 +208,16 @@ def test_gpu_tuning_state_as_data(rdsp):
     nb, k = 60, 21
     r = np.random.default_rng(9)
     src = _band(60, 2, nb)
-    a = _engine(6, 8)
+    a = engine(6, 8)
     a.sketch_setup()
-    A = _Rx(a, src, [0, 1, 1, 0, 1, 0], [0], r.uniform(-21000, 21000, 6))
+    A = Rx(a, src, [0, 1, 1, 0, 1, 0], [0], r.uniform(-21000, 21000, 6))
     A.run(0, k, 8)
     blob = a.save_state(2, 2)
     assert blob.size == a.lib.rdsp_engine_state_bytes(a.h, 2) == 16 + 2 * (10368 + 4)
     assert list(blob[:16].view(np.uint32)) == [0x45534452, 1, 2, 1]
-    b = _engine(9, 16)
+    b = engine(9, 16)
     b.sketch_setup()
-    B = _Rx(b, src, [0] * 5 + [1, 0] + [1] * 2, [0], r.uniform(-21000, 21000, 9))
+    B = Rx(b, src, [0] * 5 + [1, 0] + [1] * 2, [0], r.uniform(-21000, 21000, 9))
     B.tune(5, A.station[2:4])
     b.update_sources(torch.zeros((2, 128, 2), dtype=torch.int16, device="cuda"))        # b has a past of its own
     b.load_state(5, blob)
@@ -378,15 +229,15 @@ def test_gpu_tuning_state_as_data(rdsp):
         w = oracle_lib.OracleEngine().run(tuned_row(src[A.source_of[ca]], steps, A.tab), [])
         assert np.array_equal(y[cb], w[k * 128:]), cb
     # a blob without phases (an engine that never had sources) into an engine with them: the phase starts at 0
-    u = _engine(1, 32)
+    u = engine(1, 32)
     u.sketch_setup()
     x0 = _band(70, 1, k)[0]
     u.update(torch.from_numpy(x0[None].copy()).cuda())
     ublob = u.save_state(0, 1)
     assert ublob.size == 16 + 10368 and list(ublob[:16].view(np.uint32)) == [0x45534452, 1, 1, 0]
-    c = _engine(3, 8)
+    c = engine(3, 8)
     c.sketch_setup()
-    C_ = _Rx(c, src, [1, 1, 0], [0], r.uniform(-21000, 21000, 3))
+    C_ = Rx(c, src, [1, 1, 0], [0], r.uniform(-21000, 21000, 3))
     C_.run(0, 5, 8)
     c.load_state(1, ublob)
     C_.steps = [[] for _ in range(3)]
@@ -410,7 +261,7 @@ def test_gpu_tuning_untuned_state_is_unchanged(rdsp):
     x = _band(80, 3, 8)
     blobs = []
     for tune in (False, True):
-        e = _engine(3, 8)
+        e = engine(3, 8)
         e.sketch_setup()
         if tune:
             e.tune(0, [100.0, 200.0, 300.0])
@@ -426,7 +277,7 @@ def test_gpu_tuning_reset_zeroes_phases_and_keeps_stations(rdsp):
     """reset, then the same source rows again: the same audio as the first time (phases from 0, stations as tuned)"""
     import torch
     src = _band(90, 2, 24)
-    eng = _engine(5, 8)
+    eng = engine(5, 8)
     eng.sketch_setup()
     eng.set_sources(2, [0, 1, 0, 1, 1])
     eng.tune(0, [-15000.0, 3000.0, 12345.6, -700.0, 20000.0])
@@ -451,7 +302,7 @@ def test_gpu_tuning_refusals(rdsp):
     from radiodsp_sdr_rx_amd._lib import RdspError
     src = torch.from_numpy(_band(95, 2, 16)).cuda()
     out = torch.empty((4, 8 * 128, 2), dtype=torch.int16, device="cuda")
-    eng, twin = _engine(4, 8), _engine(4, 8)
+    eng, twin = engine(4, 8), engine(4, 8)
     for e in (eng, twin):
         e.sketch_setup()
     with pytest.raises(RdspError) as ex:
