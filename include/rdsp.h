@@ -590,6 +590,60 @@ float rdsp_spectrum_node_read(rdsp_node_t *n, int ch, unsigned int binNumber);  
 float rdsp_spectrum_node_read_range(rdsp_node_t *n, int ch, unsigned int binFirst, unsigned int binLast); /* FFTIQ.h:75 */
 int rdsp_spectrum_node_status(rdsp_node_t *n);
 
+/* ---- band survey: averaged power spectra of shared IQ sources, station finder ---------------------------------------------
+ * rdsp_engine_tune wants every receiver's station in Hz from its source's centre; rdsp_survey_t finds them.  An object of its
+ * own (several engines, or a chain, may share one band and one survey) that takes the rows of
+ * rdsp_engine_update_source_samples -- the four formats RDSP_SRC_* (declared with the engine below), the same value per
+ * element, the same stride in pairs -- and returns Welch-averaged power spectra per source as float rows on the device.
+ *
+ * Definition.  N = fft_n (1024 or 4096), H = N / 2, navg a power of two 1 ... 256, fs = 44100 P / Q.  v[n] = (value of I_n,
+ * value of Q_n) for pair n of a source, counted from the last reset (the table of values of the engine's source formats).
+ * - Window: w[n] = 0.35875 - 0.48829 cos(2 pi n / N) + 0.14128 cos(4 pi n / N) - 0.01168 cos(6 pi n / N) (the periodic 4-term
+ *   Blackman-Harris window), evaluated in double, divided by its double sum and rounded to float: a complex exponential of A
+ *   counts on a bin centre reads A^2.  rdsp_survey_window returns these floats; the kernel uses exactly them.
+ * - Frame f covers pairs [f H, f H + N): x_f[n] = (w[n] v_I, w[n] v_Q), one rounded float product each; X_f the forward
+ *   N-point DFT in float; p_f[k] = |X_f[k]|^2.  No leading zeros: frame 0 is the first N pairs.  A frame's arithmetic is a
+ *   function of its N values only.
+ * - Row r covers frames r navg ... r navg + navg - 1: acc = 0, acc += p_f[k] in ascending f (float adds), out = acc / navg
+ *   (exact).  Output index j = (k + N / 2) mod N lies (j - N / 2) fs / N Hz from the band centre (rdsp_survey_bin_hz);
+ *   positive frequency is I + jQ, the sign of rdsp_engine_tune.
+ * - Delivery: row r is delivered by the call in which pair (r navg + navg - 1) H + N - 1 arrives.  With T pairs before a
+ *   call it completes rows(T + pairs) - rows(T) rows per source, rows(T) = T < N ? 0 : ((T - N) / H + 1) / navg
+ *   (rdsp_survey_rows_between; rdsp_survey_rows_for for the object's T).  A stream gives the SAME BITS however it is cut into
+ *   calls, calls of 0 pairs and calls that complete no frame included.
+ *
+ * Rules: source rows aligned to one pair (2 / 2 / 4 / 8 bytes for U8 / S8 / S16 / F32), src_stride >= pairs (a host may walk
+ * a pointer through a recording); d_rows 16-byte aligned, rows_stride a multiple of 4 and at least rows_for(pairs) fft_n;
+ * pairs <= max_pairs_per_call; 1 ... 4096 sources.  A bad fft_n, navg, format, stride, alignment or size is refused
+ * (RDSP_ERR_INVALID, rdsp_last_error) with nothing changed in the object.  Everything is launched on the caller's stream;
+ * update does not synchronise.
+ *
+ * rdsp_survey_find_stations (host, double): db[j] = 10 log10(max(row[j], 1e-30)); the floor is the median of db (the mean of
+ * the two middle values); candidates are 1 <= j <= N - 2 with db[j] >= floor + min_db_over_floor, row[j] >= row[j - 1] and
+ * row[j] > row[j + 1]; a candidate's frequency is its bin's plus the vertex of the parabola through db[j - 1 ... j + 1];
+ * candidates are taken in descending power (equal powers: ascending j), one closer than min_spacing_hz to one already taken
+ * is dropped, at most max_out are written (power may be NULL).  Returns the number written, or RDSP_ERR_INVALID. */
+typedef struct rdsp_survey rdsp_survey_t;
+int rdsp_survey_create(int n_sources, int device, int fft_n, int navg, int format /* RDSP_SRC_* */, size_t max_pairs_per_call,
+                       rdsp_survey_t **out);
+void rdsp_survey_destroy(rdsp_survey_t *s);
+int rdsp_survey_reset(rdsp_survey_t *s, void *stream);          /* T = 0, histories and partial rows zero */
+int rdsp_survey_rows_for(const rdsp_survey_t *s, size_t pairs); /* rows per source the NEXT update(pairs) completes */
+/* d_src [source][src_stride] pairs; d_rows float [source][row][fft_n], rows_stride floats between sources */
+int rdsp_survey_update(rdsp_survey_t *s, const void *d_src, size_t src_stride /* pairs */, size_t pairs, float *d_rows,
+                       size_t rows_stride, int *rows_out, void *stream);
+int rdsp_survey_sources(const rdsp_survey_t *s);
+int rdsp_survey_fft_n(const rdsp_survey_t *s);
+int rdsp_survey_navg(const rdsp_survey_t *s);
+int rdsp_survey_format(const rdsp_survey_t *s);
+int rdsp_survey_device(const rdsp_survey_t *s);
+/* host only, no device */
+int rdsp_survey_window(int fft_n, float *out /* [fft_n] */);
+int rdsp_survey_rows_between(int fft_n, int navg, uint64_t pairs_before, size_t pairs);
+double rdsp_survey_bin_hz(int fft_n, int P, int Q, int j);
+int rdsp_survey_find_stations(const float *row, int fft_n, int P, int Q, double min_db_over_floor, double min_spacing_hz,
+                              int max_out, double *station_hz, float *power);
+
 /* ---- F3: biquad cascades ----------------------------------------------------------------------------------------
  * Two different routines of two different libraries, neither in the reference tree, both restated from their published
  * sources and both confirmed in structure by the code of the reference's firmware image (tests/test_firmware_tables.py):

@@ -9,4 +9,7 @@ def __getattr__(name):
     if name in ("Chain", "synth_iq", "calc_cplx_FIR_coeffs", "init_filter_mask"):
         from . import chain
         return getattr(chain, name)
+    if name == "Survey":
+        from . import survey
+        return survey.Survey
     raise AttributeError(name)

@@ -328,6 +328,20 @@ SYMBOLS = [
     ("rdsp_sdr_load_engine_tables", _i, [_vp, _f32p, _f32p]),
     ("rdsp_chain_engine", _vp, [_vp]),
     ("rdsp_chain_preproc", _vp, [_vp]),
+    ("rdsp_survey_create", _i, [_i, _i, _i, _i, _i, _sz, C.POINTER(_vp)]),
+    ("rdsp_survey_destroy", None, [_vp]),
+    ("rdsp_survey_reset", _i, [_vp, _vp]),
+    ("rdsp_survey_rows_for", _i, [_vp, _sz]),
+    ("rdsp_survey_update", _i, [_vp, _vp, _sz, _sz, _vp, _sz, C.POINTER(C.c_int), _vp]),
+    ("rdsp_survey_sources", _i, [_vp]),
+    ("rdsp_survey_fft_n", _i, [_vp]),
+    ("rdsp_survey_navg", _i, [_vp]),
+    ("rdsp_survey_format", _i, [_vp]),
+    ("rdsp_survey_device", _i, [_vp]),
+    ("rdsp_survey_window", _i, [_i, _f32p]),
+    ("rdsp_survey_rows_between", _i, [_i, _i, C.c_uint64, _sz]),
+    ("rdsp_survey_bin_hz", _d, [_i, _i, _i, _i]),
+    ("rdsp_survey_find_stations", _i, [_f32p, _i, _i, _i, _d, _d, _i, _f64p, _f32p]),
     ("rdsp_synth_iq", None, [_i16p, _i, _i, C.c_uint64, _i, C.POINTER(SynthConfig), _i]),
 ]
 
