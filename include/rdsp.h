@@ -912,6 +912,64 @@ int rdsp_engine_set_source_format(rdsp_engine_t *e, int format);
 int rdsp_engine_source_format(const rdsp_engine_t *e);
 int rdsp_engine_update_source_samples(rdsp_engine_t *e, const void *d_src, size_t src_stride /* pairs */, int n_blocks,
                                       int16_t *d_lr, size_t out_stride, void *stream);
+/* Signal meter, squelch and active-receiver list.  The engine writes audio for every receiver on every call; the meter says
+ * which receivers hear something.  Off until rdsp_engine_enable_meter: an engine that never calls it allocates, launches,
+ * returns and saves exactly what it did before the meter existed.  Everything runs on the device inside rdsp_engine_update,
+ * rdsp_engine_update_sources and rdsp_engine_update_source_samples, stream-ordered behind the call's audio.
+ * What is measured: the float row of demodulated audio per channel -- behind the IF band-pass and the detector (so in-band),
+ *   in front of the audio filter, the AGC and the ALS filter (so it still carries the level); full scale is +-1.0.
+ * Per channel and per block of 128 samples a[0..127] of that row, in block order (arithmetic: csrc/rdsp_meter.h, float32, no
+ *   contraction):
+ *   - mean square: q[t] = a[t] a[t], one rounded product each; the q are summed by the balanced binary tree over adjacent
+ *     pairs in index order (q[0] + q[1], q[2] + q[3], ...; seven levels); ms = sum x 0.0078125f (exact).  The tree is the
+ *     definition: it is what a wave computes by an exchange reduction, and float addition being commutative an xor butterfly
+ *     with strides 1, 2, 4, ... gives the same bits.
+ *   - peak: pk = max over t of fabsf(a[t]) by fmaxf (a NaN sample is passed over; the order does not matter).
+ *   - level: d = ms - L; L <- fmaf(d > 0 ? attack : decay, d, L).  L is 0 at create and after rdsp_engine_reset.  attack and
+ *     decay lie in (0, 1]; the defaults 0.5f and 0.0625f rise within two blocks and fall over about 16 (46 ms).
+ *   - gate, evaluated after the level, with integer state open and hang (both 0 at create and after reset):
+ *       squelch off (the default): open = 1, hang = hang_blocks;
+ *       squelch on: if L >= open_ms: open = 1, hang = hang_blocks; else if open and L >= close_ms: hang = hang_blocks;
+ *       else if open and hang > 0: hang--; otherwise open = 0.
+ *     0 <= close_ms <= open_ms, both finite; 0 <= hang_blocks <= 65535.  Thresholds are mean squares: a sine at x dB re full
+ *     scale has ms = 0.5 x 10^(x / 10).
+ *   - audio: a block whose gate is closed leaves as 128 zero words (what rdsp_engine_setMute writes); an open block leaves
+ *     exactly as without the meter.  The engine's own signal state (filters, AGC, ALS) runs on regardless: opening restarts
+ *     nothing.
+ *   - active list: after a call, the channels whose gate was open in at least one block of that call, ascending, and their
+ *     count (an ordered scan on the device; no atomics).
+ *   Everything is a function of whole blocks and calls are whole blocks: levels, gates, audio and the union of the lists do
+ *   not depend on how the stream is cut into calls.
+ * - rdsp_engine_enable_meter allocates (per channel 32 bytes, 9 bytes per block of max_blocks_per_call, one list entry); it
+ *   takes no stream and waits for everything queued on the engine's device, as rdsp_engine_set_sources does.  Again: a no-op.
+ * - rdsp_engine_set_meter, rdsp_engine_set_squelch, rdsp_engine_disable_squelch are settings of the selected group
+ *   (rdsp_engine_select_group): a new group copies them, rdsp_engine_reset keeps them, no blob carries them.  They may
+ *   precede rdsp_engine_enable_meter and are in force once it is on.
+ * - rdsp_engine_read_meter copies the last call's per-block L, pk and open, [ch][n_blocks] with the given strides (elements),
+ *   into the caller's DEVICE buffers, stream-ordered; any pointer may be NULL; n_blocks may not exceed the last call's.
+ *   rdsp_engine_active copies the list (room for n_channels entries; the entries behind the count are unspecified) and the
+ *   count likewise.  rdsp_engine_get_meter reads through the host: host_out[ch][4] = level, the last call's last block's ms,
+ *   its pk, open (0.0 / 1.0).
+ * - rdsp_engine_read_demod copies the last call's rows of demodulated float audio -- what the meter measured -- into d_out
+ *   [ch][out_stride], n_blocks x 128 floats a row; it works without the meter (float audio in front of the AGC).
+ * - L, open and hang are signal state: they stay with the channel through regroupings, are zeroed by rdsp_engine_reset, and
+ *   travel in rdsp_engine_save_state / load_state as the tuning phases do: an engine with the meter sets header flag 2 and
+ *   appends three words per channel (level, open, hang), behind the phase words if there are any; rdsp_engine_state_bytes
+ *   says so.  The blob of an engine without the meter is unchanged.  Loading a blob with meter words needs the meter
+ *   (RDSP_ERR_NOT_READY); loading one without them into an engine with the meter zeroes those channels' meter state.
+ * - Refused with nothing changed: RDSP_ERR_INVALID for a NaN or out-of-range parameter, close_ms > open_ms, a stride below
+ *   n_blocks (n_blocks x 128 for read_demod), n_blocks above the last call's; RDSP_ERR_NOT_READY for rdsp_engine_read_meter,
+ *   rdsp_engine_active and rdsp_engine_get_meter before rdsp_engine_enable_meter. */
+int rdsp_engine_enable_meter(rdsp_engine_t *e);
+int rdsp_engine_meter_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_meter(rdsp_engine_t *e, float attack, float decay);
+int rdsp_engine_set_squelch(rdsp_engine_t *e, float open_ms, float close_ms, int hang_blocks);
+int rdsp_engine_disable_squelch(rdsp_engine_t *e);
+int rdsp_engine_read_meter(rdsp_engine_t *e, int n_blocks, float *d_level, size_t level_stride, float *d_peak, size_t peak_stride,
+                           uint8_t *d_open, size_t open_stride, void *stream);
+int rdsp_engine_active(rdsp_engine_t *e, int32_t *d_list, int32_t *d_count, void *stream);
+int rdsp_engine_get_meter(rdsp_engine_t *e, float *host_out /* [n_channels][4] */, void *stream);
+int rdsp_engine_read_demod(rdsp_engine_t *e, int n_blocks, float *d_out, size_t out_stride, void *stream);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -300,6 +300,15 @@ SYMBOLS = [
     ("rdsp_engine_update_source_samples", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     ("rdsp_engine_rate_of_hz", _i, [_d, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("rdsp_engine_rate_taps", _i, [_i, _i, C.c_float, _f32p]),
+    ("rdsp_engine_enable_meter", _i, [_vp]),
+    ("rdsp_engine_meter_enabled", _i, [_vp]),
+    ("rdsp_engine_set_meter", _i, [_vp, C.c_float, C.c_float]),
+    ("rdsp_engine_set_squelch", _i, [_vp, C.c_float, C.c_float, _i]),
+    ("rdsp_engine_disable_squelch", _i, [_vp]),
+    ("rdsp_engine_read_meter", _i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    ("rdsp_engine_active", _i, [_vp, _vp, _vp, _vp]),
+    ("rdsp_engine_get_meter", _i, [_vp, _f32p, _vp]),
+    ("rdsp_engine_read_demod", _i, [_vp, _i, _vp, _sz, _vp]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

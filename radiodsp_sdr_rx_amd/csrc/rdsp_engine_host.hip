@@ -15,6 +15,7 @@
 
 #include "rdsp_engine_int.h"
 #include "rdsp_engine_laws.h"
+#include "rdsp_engine_meter.h"
 #include "rdsp_engine_sources.h"
 
 using namespace rdsp_eng;
@@ -24,10 +25,18 @@ struct EngSettings {
   float input_gain, gain_i, gain_q, iq_balance, output_gain, tuning_offset;
   int mode, mute, audio_on, audio_id, audio_set, pre_set, agc_on, als_on, als_notch, als_adaptive, nb_on, resets;
   EngineAgcSet agc;
+  rdsp_meter::MeterSet meter; /* rdsp_engine_set_meter / set_squelch: in force once rdsp_engine_enable_meter was called */
   uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
 };
 /* the planes of a channel's signal state: create allocates them, reset fills them, save_state / load_state move them */
 enum { PL_ST, PL_RING_I, PL_RING_Q, PL_NB, PL_ALS, N_PLANES };
+/* what rdsp_engine_enable_meter allocates: every channel's meter words, the last call's records [ch][max_blocks], its list */
+struct EngMeter {
+  DevBuf<float> words, level, peak;
+  DevBuf<uint8_t> open;
+  DevBuf<int32_t> list, count;
+  int blocks = 0; /* of the last call that left records */
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -43,6 +52,8 @@ struct rdsp_engine {
   int sel = -1;                 /* the group the setters address; -1: all of them */
   /* shared IQ streams (rdsp_engine_set_sources / tune / update_sources): the front end, from the first set_sources on */
   std::unique_ptr<EngFrontEnd> src;
+  std::unique_ptr<EngMeter> meter; /* the signal meter, from rdsp_engine_enable_meter on */
+  int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
   std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
 };
 
@@ -92,6 +103,7 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.audio_set = 3; s.nb_on = 1; s.als_notch = 1; s.als_adaptive = 1;
   s.agc = engine_agc_set(0); /* 0xdf14: the medium attack with the slow decay and the fast hang time */
   s.agc_on = 1;
+  s.meter.attack = rdsp_meter::ATTACK_DEFAULT; s.meter.decay = rdsp_meter::DECAY_DEFAULT; /* squelch off, thresholds and hang 0 */
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -248,6 +260,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
     err = fill[k].empty() ? hipMemsetAsync(e->plane[k], 0, n * e->plane_words[k] * 4, s)
                           : hipMemcpyAsync(e->plane[k], fill[k].data(), fill[k].size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess && e->src) err = e->src->reset(s);
+  if (err == hipSuccess && e->meter) err = hipMemsetAsync(e->meter->words, 0, n * MT_WORDS * 4, s); /* level 0, gate closed, hang 0 */
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -350,11 +363,147 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     p.gain_i = q.gain_i; p.gain_q = q.gain_q; p.output_gain = q.output_gain; p.tuning_offset = q.tuning_offset;
     p.agc = q.agc;
     err = rdsp_engine_launch(p, q.nb_on != 0, q.als_on != 0, s);
+    if (err == hipSuccess && e->meter) { /* behind the group's tail kernel: it measures p.audio and gates p.out */
+      const EngMeter &m = *e->meter;
+      MeterParams mp;
+      mp.audio = p.audio; mp.audio_stride = p.audio_stride; mp.out = p.out; mp.out_stride = out_stride;
+      mp.out_vec = ((uintptr_t)d_lr & 15) == 0 && out_stride % 4 == 0;
+      mp.n_channels = p.n_channels; mp.n_blocks = n_blocks; mp.words = m.words + c0 * MT_WORDS;
+      mp.rec_stride = (size_t)e->max_blocks;
+      mp.level = m.level + c0 * mp.rec_stride; mp.peak = m.peak + c0 * mp.rec_stride; mp.open = m.open + c0 * mp.rec_stride;
+      mp.set = q.meter;
+      err = rdsp_engine_meter_launch(mp, s);
+    }
     if (err != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
     if (q.mode <= 3 || q.mode == 6) q.pos = (q.pos + (uint32_t)n_blocks * BS) & (e->ring_size - 1); /* the lines only move when the SSB / CW path runs */
     q.resets = 0;
   }
+  e->last_blocks = n_blocks;
+  if (e->meter) {
+    e->meter->blocks = n_blocks;
+    err = rdsp_engine_active_launch(ActiveParams{e->meter->words, e->n_channels, e->meter->list, e->meter->count}, s);
+    if (err != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
+  }
   return RDSP_OK;
+}
+
+/* ---- the signal meter, the squelch and the active-receiver list (include/rdsp.h has the definition; the kernels are
+ * rdsp_engine_meter.hip's, the arithmetic rdsp_meter.h's) ----------------------------------------------------------------- */
+namespace {
+bool no_meter(const rdsp_engine_t *e, const char *who) {
+  if (!e->meter) rdsp_set_error("%s: the meter is off; call rdsp_engine_enable_meter first", who);
+  return !e->meter;
+}
+/* n_blocks of the last call's max_blocks-wide rows into the caller's rows, stream-ordered; a NULL destination is skipped */
+hipError_t copy_rows(void *dst, size_t dst_stride, const void *src, size_t src_stride, size_t width, size_t rows, size_t size, hipStream_t s) {
+  if (!dst || width == 0) return hipSuccess;
+  return hipMemcpy2DAsync(dst, dst_stride * size, src, src_stride * size, width * size, rows, hipMemcpyDeviceToDevice, s);
+}
+}  // namespace
+
+int rdsp_engine_enable_meter(rdsp_engine_t *e) {
+  if (!e) return RDSP_ERR_INVALID;
+  if (e->meter) return RDSP_OK;
+  const size_t n = (size_t)e->n_channels, rec = n * (size_t)e->max_blocks;
+  auto m = std::make_unique<EngMeter>(); /* the object stays without a meter unless all of it exists */
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = hipDeviceSynchronize(); /* the next call of every stream runs with the meter */
+  if (err == hipSuccess) err = m->words.alloc(n * MT_WORDS);
+  if (err == hipSuccess) err = m->level.alloc(rec);
+  if (err == hipSuccess) err = m->peak.alloc(rec);
+  if (err == hipSuccess) err = m->open.alloc(rec);
+  if (err == hipSuccess) err = m->list.alloc(n);
+  if (err == hipSuccess) err = m->count.alloc(1);
+  if (err == hipSuccess) err = hipMemset(m->words, 0, n * MT_WORDS * 4);
+  if (err == hipSuccess) err = hipMemset(m->level, 0, rec * 4);
+  if (err == hipSuccess) err = hipMemset(m->peak, 0, rec * 4);
+  if (err == hipSuccess) err = hipMemset(m->open, 0, rec);
+  if (err == hipSuccess) err = hipMemset(m->list, 0, n * 4);
+  if (err == hipSuccess) err = hipMemset(m->count, 0, 4);
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  if (err != hipSuccess) {
+    rdsp_set_error("rdsp_engine_enable_meter: %s", hipGetErrorString(err));
+    return RDSP_ERR_NOMEM;
+  }
+  e->meter = std::move(m);
+  return RDSP_OK;
+}
+int rdsp_engine_meter_enabled(const rdsp_engine_t *e) { return e && e->meter ? 1 : 0; }
+
+int rdsp_engine_set_meter(rdsp_engine_t *e, float attack, float decay) {
+  if (!e || !rdsp_meter::coefficients_ok(attack, decay)) {
+    rdsp_set_error("rdsp_engine_set_meter: bad argument (attack %g and decay %g must lie in (0, 1])", (double)attack, (double)decay);
+    return RDSP_ERR_INVALID;
+  }
+  return for_selected(e, [&](EngSettings &s) { s.meter.attack = attack; s.meter.decay = decay; });
+}
+int rdsp_engine_set_squelch(rdsp_engine_t *e, float open_ms, float close_ms, int hang_blocks) {
+  if (!e || !rdsp_meter::squelch_ok(open_ms, close_ms, hang_blocks)) {
+    rdsp_set_error("rdsp_engine_set_squelch: bad argument (0 <= close_ms %g <= open_ms %g, both finite; hang_blocks %d of 0 .. %d)",
+                   (double)close_ms, (double)open_ms, hang_blocks, rdsp_meter::HANG_MAX);
+    return RDSP_ERR_INVALID;
+  }
+  return for_selected(e, [&](EngSettings &s) {
+    s.meter.squelch = 1; s.meter.open_ms = open_ms; s.meter.close_ms = close_ms; s.meter.hang_blocks = hang_blocks;
+  });
+}
+int rdsp_engine_disable_squelch(rdsp_engine_t *e) { return for_selected(e, [](EngSettings &s) { s.meter.squelch = 0; }); }
+
+int rdsp_engine_read_meter(rdsp_engine_t *e, int n_blocks, float *d_level, size_t level_stride, float *d_peak, size_t peak_stride,
+                           uint8_t *d_open, size_t open_stride, void *stream) {
+  if (!e) return RDSP_ERR_INVALID;
+  if (no_meter(e, "rdsp_engine_read_meter")) return RDSP_ERR_NOT_READY;
+  const size_t w = (size_t)std::max(n_blocks, 0);
+  if (n_blocks < 0 || n_blocks > e->meter->blocks || (d_level && level_stride < w) || (d_peak && peak_stride < w) || (d_open && open_stride < w)) {
+    rdsp_set_error("rdsp_engine_read_meter: bad argument (n_blocks %d of the last call's %d; strides at least n_blocks)", n_blocks, e->meter->blocks);
+    return RDSP_ERR_INVALID;
+  }
+  const EngMeter &m = *e->meter;
+  const size_t n = (size_t)e->n_channels, rs = (size_t)e->max_blocks;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = copy_rows(d_level, level_stride, m.level, rs, w, n, 4, s);
+  if (err == hipSuccess) err = copy_rows(d_peak, peak_stride, m.peak, rs, w, n, 4, s);
+  if (err == hipSuccess) err = copy_rows(d_open, open_stride, m.open, rs, w, n, 1, s);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_read_meter", err);
+}
+
+int rdsp_engine_active(rdsp_engine_t *e, int32_t *d_list, int32_t *d_count, void *stream) {
+  if (!e) return RDSP_ERR_INVALID;
+  if (no_meter(e, "rdsp_engine_active")) return RDSP_ERR_NOT_READY;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess && d_list) err = hipMemcpyAsync(d_list, e->meter->list, (size_t)e->n_channels * 4, hipMemcpyDeviceToDevice, s);
+  if (err == hipSuccess && d_count) err = hipMemcpyAsync(d_count, e->meter->count, 4, hipMemcpyDeviceToDevice, s);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_active", err);
+}
+
+int rdsp_engine_get_meter(rdsp_engine_t *e, float *host_out, void *stream) {
+  if (!e || !host_out) return RDSP_ERR_INVALID;
+  if (no_meter(e, "rdsp_engine_get_meter")) return RDSP_ERR_NOT_READY;
+  std::vector<float> w((size_t)e->n_channels * MT_WORDS);
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess) err = hipMemcpyAsync(w.data(), e->meter->words, w.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)stream);
+  if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
+  if (err != hipSuccess) return engine_fail("rdsp_engine_get_meter", err);
+  for (int c = 0; c < e->n_channels; c++) {
+    const float *m = &w[(size_t)c * MT_WORDS];
+    float *o = host_out + (size_t)c * 4;
+    o[0] = m[MT_LEVEL]; o[1] = m[MT_LAST_MS]; o[2] = m[MT_LAST_PK]; o[3] = (float)f_bits(m[MT_OPEN]);
+  }
+  return RDSP_OK;
+}
+
+int rdsp_engine_read_demod(rdsp_engine_t *e, int n_blocks, float *d_out, size_t out_stride, void *stream) {
+  if (!e || !d_out || n_blocks < 0 || n_blocks > e->last_blocks || out_stride < (size_t)n_blocks * BS) {
+    rdsp_set_error("rdsp_engine_read_demod: bad argument (n_blocks %d of the last call's %d; out_stride at least n_blocks * 128)",
+                   n_blocks, e ? e->last_blocks : 0);
+    return RDSP_ERR_INVALID;
+  }
+  hipError_t err = hipSetDevice(e->device);
+  if (err == hipSuccess)
+    err = copy_rows(d_out, out_stride, e->d_audio, (size_t)e->max_blocks * BS, (size_t)n_blocks * BS, (size_t)e->n_channels, 4, (hipStream_t)stream);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_read_demod", err);
 }
 
 /* ---- shared IQ streams: receivers tuned to stations inside source rows (the front end, rdsp_engine_sources.hip) ---------- */
@@ -574,6 +723,7 @@ int rdsp_engine_update_sources(rdsp_engine_t *e, const int16_t *d_src, size_t sr
 namespace {
 constexpr uint32_t STATE_MAGIC = 0x45534452u; /* "RDSE" */
 constexpr uint32_t STATE_PHASES = 1u;
+constexpr uint32_t STATE_METER = 2u; /* an engine with the meter appends {level, open, hang} per channel, behind the phases */
 /* where a channel's planes lie in its blob words: whole, but of a ring its last RING_KEPT samples in time order */
 constexpr size_t RING_KEPT = 512;
 constexpr size_t BLOB_OFF[N_PLANES] = {0, NF, NF + RING_KEPT, NF + 2 * RING_KEPT, NF + 2 * RING_KEPT + NB_WORDS};
@@ -581,7 +731,8 @@ constexpr size_t STATE_CH_WORDS = BLOB_OFF[PL_ALS] + ALS_WORDS;
 struct StateImage { /* host images of the planes of n channels */
   std::vector<float> plane[N_PLANES];
   std::vector<uint32_t> ph; /* tuning phases, of an engine with sources */
-  StateImage(const rdsp_engine_t *e, size_t n) : ph(e->src ? n : 0, 0u) {
+  std::vector<float> mt;    /* meter words, of an engine with the meter */
+  StateImage(const rdsp_engine_t *e, size_t n) : ph(e->src ? n : 0, 0u), mt(e->meter ? n * MT_WORDS : 0, 0.0f) {
     for (int k = 0; k < N_PLANES; k++) plane[k].assign(n * e->plane_words[k], 0.0f);
   }
 };
@@ -591,6 +742,7 @@ hipError_t image_copy(rdsp_engine_t *e, StateImage &im, bool save, size_t c0, si
   auto copy = [&](void *dev, void *host, size_t bytes) { return hipMemcpyAsync(save ? host : dev, save ? dev : host, bytes, kind, s); };
   hipError_t err = hipSetDevice(e->device);
   if (err == hipSuccess && e->src) err = copy(e->src->phase + c0, im.ph.data(), n * 4);
+  if (err == hipSuccess && e->meter) err = copy(e->meter->words + c0 * MT_WORDS, im.mt.data(), n * MT_WORDS * 4);
   for (int k = 0; k < N_PLANES && err == hipSuccess; k++) err = copy(e->plane[k] + c0 * e->plane_words[k], im.plane[k].data(), im.plane[k].size() * 4);
   if (err == hipSuccess) err = hipStreamSynchronize(s);
   return err;
@@ -613,7 +765,7 @@ float *blob_move(const rdsp_engine_t *e, StateImage &im, bool save, int first_ch
 }
 }  // namespace
 size_t rdsp_engine_state_bytes(const rdsp_engine_t *e, int n_channels) {
-  return (e && n_channels > 0) ? 16 + (size_t)n_channels * (STATE_CH_WORDS + (e->src ? 1 : 0)) * 4 : 0;
+  return (e && n_channels > 0) ? 16 + (size_t)n_channels * (STATE_CH_WORDS + (e->src ? 1 : 0) + (e->meter ? MT_STATE_WORDS : 0)) * 4 : 0;
 }
 int rdsp_engine_save_state(rdsp_engine_t *e, int first_channel, int n_channels, void *host_buf, size_t bytes, void *stream) {
   if (!e || !host_buf || first_channel < 0 || n_channels < 1 || first_channel + n_channels > e->n_channels ||
@@ -626,20 +778,21 @@ int rdsp_engine_save_state(rdsp_engine_t *e, int first_channel, int n_channels, 
   const hipError_t err = image_copy(e, im, true, (size_t)first_channel, n, (hipStream_t)stream);
   if (err != hipSuccess) return engine_fail("rdsp_engine_save_state", err);
   uint32_t *hdr = (uint32_t *)host_buf;
-  hdr[0] = STATE_MAGIC; hdr[1] = 1; hdr[2] = (uint32_t)n_channels; hdr[3] = e->src ? STATE_PHASES : 0;
+  hdr[0] = STATE_MAGIC; hdr[1] = 1; hdr[2] = (uint32_t)n_channels; hdr[3] = (e->src ? STATE_PHASES : 0) | (e->meter ? STATE_METER : 0);
   float *end = blob_move(e, im, true, first_channel, n, (float *)(hdr + 4));
-  if (e->src) memcpy(end, im.ph.data(), n * 4); /* after the last channel's words */
+  if (e->src) { memcpy(end, im.ph.data(), n * 4); end += n; } /* after the last channel's words */
+  for (size_t c = 0; e->meter && c < n; c++) memcpy(end + c * MT_STATE_WORDS, &im.mt[c * MT_WORDS], MT_STATE_WORDS * 4);
   return RDSP_OK;
 }
 int rdsp_engine_load_state(rdsp_engine_t *e, int first_channel, const void *host_buf, size_t bytes, void *stream) {
   const uint32_t *hdr = (const uint32_t *)host_buf;
-  if (!e || !host_buf || bytes < 16 || hdr[0] != STATE_MAGIC || hdr[1] != 1 || (hdr[3] & ~STATE_PHASES) != 0) {
+  if (!e || !host_buf || bytes < 16 || hdr[0] != STATE_MAGIC || hdr[1] != 1 || (hdr[3] & ~(STATE_PHASES | STATE_METER)) != 0) {
     rdsp_set_error("rdsp_engine_load_state: not an engine state blob of this version");
     return RDSP_ERR_INVALID;
   }
-  const bool phases = (hdr[3] & STATE_PHASES) != 0;
+  const bool phases = (hdr[3] & STATE_PHASES) != 0, meter = (hdr[3] & STATE_METER) != 0;
   const size_t n = hdr[2], c0 = (size_t)first_channel;
-  if (first_channel < 0 || n < 1 || c0 + n > (size_t)e->n_channels || bytes < 16 + n * (STATE_CH_WORDS + (phases ? 1 : 0)) * 4) {
+  if (first_channel < 0 || n < 1 || c0 + n > (size_t)e->n_channels || bytes < 16 + n * (STATE_CH_WORDS + (phases ? 1 : 0) + (meter ? MT_STATE_WORDS : 0)) * 4) {
     rdsp_set_error("rdsp_engine_load_state: %zu channels at %d do not fit", n, first_channel);
     return RDSP_ERR_INVALID;
   }
@@ -647,9 +800,16 @@ int rdsp_engine_load_state(rdsp_engine_t *e, int first_channel, const void *host
     rdsp_set_error("rdsp_engine_load_state: the blob carries tuning phases; call rdsp_engine_set_sources first");
     return RDSP_ERR_NOT_READY;
   }
-  StateImage im(e, n); /* zeros: the rings outside the kept samples, and the phases of a blob from an engine that never tuned */
+  if (meter && !e->meter) {
+    rdsp_set_error("rdsp_engine_load_state: the blob carries meter state; call rdsp_engine_enable_meter first");
+    return RDSP_ERR_NOT_READY;
+  }
+  /* zeros: the rings outside the kept samples, the phases of a blob from an engine that never tuned, the meter words of one
+   * that never metered (and always those of the last call: they are no state) */
+  StateImage im(e, n);
   const float *end = blob_move(e, im, false, first_channel, n, (float *)(hdr + 4)); /* read only: save is false */
-  if (phases) memcpy(im.ph.data(), end, n * 4);
+  if (phases) { memcpy(im.ph.data(), end, n * 4); end += n; }
+  for (size_t c = 0; meter && c < n; c++) memcpy(&im.mt[c * MT_WORDS], end + c * MT_STATE_WORDS, MT_STATE_WORDS * 4);
   const hipError_t err = image_copy(e, im, false, c0, n, (hipStream_t)stream);
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_load_state", err);
 }

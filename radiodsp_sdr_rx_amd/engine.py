@@ -143,6 +143,68 @@ class Engine:
         check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), n_in, n // 128, out.data_ptr(), n, C.c_void_p(s)))
         return out
 
+    def _stream(self, stream):
+        import torch
+        return C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+
+    def enable_meter(self):
+        """the signal meter from the next update on (include/rdsp.h, "signal meter and squelch"); again: a no-op.  Takes no
+        stream and waits for the device."""
+        check(self.lib.rdsp_engine_enable_meter(self.h))
+
+    def meter_enabled(self):
+        return bool(self.lib.rdsp_engine_meter_enabled(self.h))
+
+    def set_meter(self, attack=0.5, decay=0.0625):
+        """the level's coefficients of the selected group, each in (0, 1]"""
+        check(self.lib.rdsp_engine_set_meter(self.h, float(attack), float(decay)))
+
+    def set_squelch(self, open_ms, close_ms, hang_blocks=0):
+        """the selected group's gate: opens at a level >= open_ms, stays open while >= close_ms and for hang_blocks blocks
+        after; mean squares of the demodulated audio (ms_of_db gives them from dB re a full-scale sine)"""
+        check(self.lib.rdsp_engine_set_squelch(self.h, float(open_ms), float(close_ms), int(hang_blocks)))
+
+    def disable_squelch(self):
+        check(self.lib.rdsp_engine_disable_squelch(self.h))
+
+    def read_meter(self, n_blocks, stream=None):
+        """the last call's records -> (level float32, peak float32, open uint8), each [n_channels, n_blocks] on the device"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        level, peak = (torch.empty((self.n_channels, n), dtype=torch.float32, device=dev) for _ in range(2))
+        gate = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        check(self.lib.rdsp_engine_read_meter(self.h, n, level.data_ptr(), n, peak.data_ptr(), n, gate.data_ptr(), n, self._stream(stream)))
+        return level, peak, gate
+
+    def active(self, stream=None):
+        """the receivers whose gate was open in a block of the last call -> (int32 tensor on the device, ascending, count)"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        lst = torch.empty(self.n_channels, dtype=torch.int32, device=dev)
+        cnt = torch.empty(1, dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_active(self.h, lst.data_ptr(), cnt.data_ptr(), self._stream(stream)))
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize()
+        n = int(cnt.item())
+        return lst[:n], n
+
+    def meter(self):
+        """[n_channels, 4] on the host: level, the last block's mean square, the last block's peak, open"""
+        o = np.zeros((self.n_channels, 4), np.float32)
+        check(self.lib.rdsp_engine_get_meter(self.h, o.ctypes.data_as(_F32P), None))
+        return o
+
+    def read_demod(self, n_blocks, stream=None):
+        """the last call's demodulated float rows (behind the IF filter and the detector, in front of the audio filter, AGC
+        and ALS: what the meter measures) -> float32 [n_channels, n_blocks x 128] on the device.  Works without the meter."""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks) * 128
+        out = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_demod(self.h, int(n_blocks), out.data_ptr(), n, self._stream(stream)))
+        return out
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -204,6 +266,17 @@ def rate_of_hz(fs_hz):
     p, q = C.c_int(), C.c_int()
     check(load().rdsp_engine_rate_of_hz(float(fs_hz), C.byref(p), C.byref(q)))
     return p.value, q.value
+
+
+def ms_of_db(db):
+    """the mean square of a sine at db dB re full scale (amplitude 1.0): 0.5 x 10^(db / 10); host only"""
+    return 0.5 * 10.0 ** (float(db) / 10.0)
+
+
+def db_of_ms(ms):
+    """ms_of_db's inverse: 10 log10(2 ms), -inf for 0; host only"""
+    import math
+    return 10.0 * math.log10(2.0 * float(ms)) if ms > 0 else -math.inf
 
 
 def _setter(name):
