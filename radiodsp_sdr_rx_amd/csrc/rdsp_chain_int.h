@@ -31,10 +31,6 @@ int chain_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 
 static inline int launch_failed(const char *what, int e) {
   return chain_fail(RDSP_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)e));
 }
-template <typename T> static inline hipError_t alloc_zero(DevBuf<T> &b, size_t n) {
-  const hipError_t e = b.alloc(n);
-  return e != hipSuccess ? e : hipMemset(b.p, 0, n * sizeof(T));
-}
 /* one more created event at the back of a pool; a failure leaves the pool as it was */
 static inline hipError_t push_event(std::deque<Event> &pool, unsigned flags) {
   pool.emplace_back();

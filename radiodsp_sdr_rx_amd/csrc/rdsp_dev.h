@@ -23,6 +23,11 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; }
   operator T *() const { return p; }
 };
+/* n zeroed elements (hipMemset: the caller's device is current, nothing of the buffer is queued yet) */
+template <typename T> static inline hipError_t alloc_zero(DevBuf<T> &b, size_t n) {
+  const hipError_t e = b.alloc(n);
+  return e != hipSuccess ? e : hipMemset(b.p, 0, n * sizeof(T));
+}
 
 template <typename T>
 struct PinnedBuf { /* hipHostMalloc */

@@ -1,0 +1,94 @@
+/*
+ * rdsp_engine_host.h -- what the host files of rdsp_engine_t (include/rdsp.h) share: the object, a group's settings, the
+ * meter as an owner, the walk over groups.  rdsp_engine_host.hip holds the sketch's settings and setters and creates, resets
+ * and runs the object; rdsp_engine_groups.hip the receiver groups; rdsp_engine_meter_host.hip the signal meter's owner and
+ * entry points; rdsp_engine_sources_host.hip the entry points of the shared IQ sources; rdsp_engine_state.hip the state
+ * blob.  Host logic only: the kernels are rdsp_engine.hip's and rdsp_engine_meter.hip's, the front end is
+ * rdsp_engine_sources.h's.  All five are compiled with the kernels' flags (-ffp-contract=off).
+ */
+#ifndef RDSP_ENGINE_HOST_H
+#define RDSP_ENGINE_HOST_H
+
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "rdsp_engine_int.h"
+#include "rdsp_engine_laws.h"
+#include "rdsp_engine_meter.h"
+#include "rdsp_engine_sources.h"
+
+using namespace rdsp_eng;
+
+/* what the sketch's calls set: one set per receiver group (one group = the whole object unless rdsp_engine_set_groups cut it) */
+struct EngSettings {
+  float input_gain, gain_i, gain_q, iq_balance, output_gain, tuning_offset;
+  int mode, mute, audio_on, audio_id, audio_set, pre_set, agc_on, als_on, als_notch, als_adaptive, nb_on, resets;
+  EngineAgcSet agc;
+  rdsp_meter::MeterSet meter; /* rdsp_engine_set_meter / set_squelch: in force once rdsp_engine_enable_meter was called */
+  uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
+};
+/* the planes of a channel's signal state: create allocates them, reset fills them, save_state / load_state move them */
+enum { PL_ST, PL_RING_I, PL_RING_Q, PL_NB, PL_ALS, N_PLANES };
+/* the signal meter (rdsp_engine_meter_host.hip): every channel's meter words, the last call's records [ch][max_blocks], its list */
+struct EngMeter {
+  DevBuf<float> words, level, peak;
+  DevBuf<uint8_t> open;
+  DevBuf<int32_t> list, count;
+  size_t n_channels = 0, max_blocks = 0;
+  int blocks = 0; /* of the last call that left records */
+  hipError_t init(size_t n_channels, size_t max_blocks); /* every buffer, zeroed */
+  hipError_t reset(hipStream_t s);                       /* level 0, gate closed, hang 0 */
+  /* behind the tail kernel of the group p launched (channels c0 on): it measures p.audio and gates p.out, rows of the caller's d_lr */
+  hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_meter::MeterSet &set, const int16_t *d_lr, hipStream_t s) const;
+  hipError_t launch_list(int n_blocks, hipStream_t s); /* once behind every group's meter: the list of a call of n_blocks */
+};
+struct rdsp_engine {
+  int n_channels, device, max_blocks;
+  uint32_t ring_size;
+  bool tables;
+  DevBuf<float> plane[N_PLANES], d_audio, d_tab;
+  size_t plane_words[N_PLANES]; /* per channel */
+  EngParams base;               /* the kernels' arguments that belong to the object (rdsp_engine_load_tables) */
+  float curve[130], sine[257];
+  /* constants of the object (docs/engine.md has their places in the image's AudioSDR) */
+  float if_centre, ssb_band, cw_band, agc_knee_db, agc_slope, agc_threshold_db, sam_ga, sam_gb;
+  std::vector<EngSettings> grp; /* at least one */
+  std::vector<int> first;       /* first channel of each group, ascending; first[0] = 0 */
+  int sel = -1;                 /* the group the setters address; -1: all of them */
+  /* shared IQ streams (rdsp_engine_set_sources / tune / update_sources): the front end, from the first set_sources on */
+  std::unique_ptr<EngFrontEnd> src;
+  std::unique_ptr<EngMeter> meter; /* the signal meter, from rdsp_engine_enable_meter on */
+  int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
+  std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
+};
+
+/* the setters address the selected group, or all of them */
+template <typename F>
+static inline int for_selected(rdsp_engine_t *e, F f) {
+  if (!e) return RDSP_ERR_INVALID;
+  for (size_t g = 0; g < e->grp.size(); g++)
+    if (e->sel < 0 || (size_t)e->sel == g) f(e->grp[g]);
+  return RDSP_OK;
+}
+static inline int group_of(const std::vector<int> &first, int ch) {
+  size_t g = 0;
+  while (g + 1 < first.size() && first[g + 1] <= ch) g++;
+  return (int)g;
+}
+/* where range g of `first` ends: the channels of group g are first[g] .. range_end(first, g, n_channels) - 1 */
+static inline int range_end(const std::vector<int> &first, size_t g, int n_channels) { return g + 1 < first.size() ? first[g + 1] : n_channels; }
+/* the refusals of everything that needs rdsp_engine_enable_meter / rdsp_engine_set_sources first */
+static inline bool no_meter(const rdsp_engine_t *e, const char *who) {
+  if (!e->meter) rdsp_set_error("%s: the meter is off; call rdsp_engine_enable_meter first", who);
+  return !e->meter;
+}
+static inline bool no_sources(const rdsp_engine_t *e, const char *who) {
+  if (!e->src) rdsp_set_error("%s: no sources; call rdsp_engine_set_sources first", who);
+  return !e->src;
+}
+
+#endif

@@ -1,5 +1,5 @@
 /*
- * rdsp_engine_int.h -- what rdsp_engine_t's kernels (rdsp_engine.hip) and its host object (rdsp_engine_host.hip) share: the
+ * rdsp_engine_int.h -- what rdsp_engine_t's kernels (rdsp_engine.hip) and its host object (rdsp_engine_host.h) share: the
  * kernels' arguments, a channel's state words, the launch of one group's kernels; and what the engine's and the
  * pre-processor's (rdsp_preproc.hip) host sides share: the owner of a device allocation (rdsp_dev.h), the HIP error return. */
 #ifndef RDSP_ENGINE_INT_H

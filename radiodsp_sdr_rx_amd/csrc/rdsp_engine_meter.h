@@ -1,6 +1,6 @@
 /*
- * rdsp_engine_meter.h -- what the meter's kernels (rdsp_engine_meter.hip) and the engine's host object (rdsp_engine_host.hip)
- * share: the kernels' arguments, a channel's meter words, the two launches.  The arithmetic is rdsp_meter.h's.
+ * rdsp_engine_meter.h -- what the meter's kernels (rdsp_engine_meter.hip) and their owner on the host (EngMeter,
+ * rdsp_engine_meter_host.hip) share: the kernels' arguments, a channel's meter words, the two launches.  The arithmetic is rdsp_meter.h's.
  */
 #ifndef RDSP_ENGINE_METER_H
 #define RDSP_ENGINE_METER_H

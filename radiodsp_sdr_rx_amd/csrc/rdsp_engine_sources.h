@@ -1,7 +1,7 @@
 /*
  * rdsp_engine_sources.h -- the source front end of rdsp_engine_t (rdsp_engine_sources.hip): receivers tuned to stations inside
- * shared IQ rows.  The engine's host object (rdsp_engine_host.hip) holds one, from the first rdsp_engine_set_sources on,
- * validates the arguments of the entry points and hands them over; the arithmetic and the kernels' arguments are rdsp_tune.h's.
+ * shared IQ rows.  The engine's host object (rdsp_engine_host.h) holds one, from the first rdsp_engine_set_sources on; the entry
+ * points (rdsp_engine_sources_host.hip) validate their arguments and hand them over; the arithmetic is rdsp_tune.h's.
  */
 #ifndef RDSP_ENGINE_SOURCES_H
 #define RDSP_ENGINE_SOURCES_H

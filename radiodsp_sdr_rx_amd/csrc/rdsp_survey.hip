@@ -214,8 +214,7 @@ extern "C" int rdsp_survey_create(int n_sources, int device, int fft_n, int navg
   bool ok = hipSetDevice(device) == hipSuccess && s->d_window.alloc((size_t)fft_n) == hipSuccess &&
             hipMemcpy(s->d_window, w.data(), (size_t)fft_n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
   for (int i = 0; ok && i < 2; i++)
-    ok = s->d_hist[i].alloc(n) == hipSuccess && s->d_part[i].alloc(n) == hipSuccess &&
-         hipMemset(s->d_hist[i], 0, n * sizeof(float2)) == hipSuccess && hipMemset(s->d_part[i], 0, n * sizeof(float)) == hipSuccess;
+    ok = rdsp_dev::alloc_zero(s->d_hist[i], n) == hipSuccess && rdsp_dev::alloc_zero(s->d_part[i], n) == hipSuccess;
   if (!ok) {
     rdsp_set_error("rdsp_survey_create: device set-up failed");
     rdsp_survey_destroy(s);

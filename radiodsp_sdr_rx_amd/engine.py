@@ -19,6 +19,12 @@ def _src_dtype(fmt):
     return (torch.int16, torch.uint8, torch.int8, torch.float32)[fmt]
 
 
+def _stream(stream):
+    """the void * the library takes: the caller's stream handle, or torch's current stream"""
+    import torch
+    return C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+
+
 class Engine:
     def __init__(self, n_channels, max_blocks_per_call=64, device=0, tables=None):
         self.lib = load()
@@ -58,8 +64,7 @@ class Engine:
         assert nch == self.n_channels and two == 2 and n % 128 == 0 and d_iq.dtype == torch.int16 and d_iq.is_contiguous()
         if out is None:
             out = torch.empty_like(d_iq)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(self.lib.rdsp_engine_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, C.c_void_p(s)))
+        check(self.lib.rdsp_engine_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, _stream(stream)))
         return out
 
     def set_sources(self, n_sources, source_of_channel):
@@ -73,7 +78,6 @@ class Engine:
         """the source rows are at D x 44100 Hz (D = 1 ... 64): update_sources() tunes, low-passes (16 D taps, times gain) and
         decimates by D.  After set_sources()."""
         check(self.lib.rdsp_engine_set_source_decimation(self.h, int(D), float(gain)))
-        self.D = int(D)
 
     def source_decimation(self):
         return int(self.lib.rdsp_engine_source_decimation(self.h))
@@ -83,7 +87,6 @@ class Engine:
         tunes, low-passes and resamples by Q / P.  Q = 1 after reduction is set_source_decimation(P, gain).  After
         set_sources()."""
         check(self.lib.rdsp_engine_set_source_rate(self.h, int(P), int(Q), float(gain)))
-        self.D = self.source_decimation()                    # 0 while the rate is rational
 
     def source_rate(self):
         """(P, Q) in lowest terms; (D, 1) for an integer rate"""
@@ -117,35 +120,27 @@ class Engine:
         every row of d_src, which may be a view into a longer buffer (rows any whole number of pairs apart); required with a
         rational rate (set_source_rate)."""
         nsrc, n_in, two = d_src.shape
-        D = getattr(self, "D", 1)
         import torch
         fmt = self.source_format()
         dtype = _src_dtype(fmt)
         assert d_src.dtype == dtype, f"the engine's source format {fmt} takes {dtype} rows, not {d_src.dtype}"
         if n_blocks is not None:
-            n, need = int(n_blocks) * 128, self.source_pairs(n_blocks)
+            n_blocks, need = int(n_blocks), self.source_pairs(n_blocks)
             assert two == 2 and n_in >= need, "d_src holds fewer pairs than source_pairs(n_blocks)"
             assert d_src.stride(2) == 1 and d_src.stride(1) == 2 and d_src.stride(0) % 2 == 0
-            assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
-            if out is None:
-                out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
-            s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
             stride = d_src.stride(0) // 2 if nsrc > 1 else max(n_in, need)
-            check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), stride, int(n_blocks), out.data_ptr(), n, C.c_void_p(s)))
-            return out
-        assert D >= 1, "a rational source rate is set: pass n_blocks"
-        n = n_in // D
-        assert two == 2 and n_in == n * D and n % 128 == 0 and d_src.is_contiguous()
+        else:
+            D = self.source_decimation()                     # 0 while the rate is rational
+            assert D >= 1, "a rational source rate is set: pass n_blocks"
+            n = n_in // D
+            assert two == 2 and n_in == n * D and n % 128 == 0 and d_src.is_contiguous()
+            n_blocks, stride = n // 128, n_in
         assert nsrc >= getattr(self, "n_sources", 0), "fewer source rows than set_sources named"
+        n = n_blocks * 128
         if out is None:
             out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), n_in, n // 128, out.data_ptr(), n, C.c_void_p(s)))
+        check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), stride, n_blocks, out.data_ptr(), n, _stream(stream)))
         return out
-
-    def _stream(self, stream):
-        import torch
-        return C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
 
     def enable_meter(self):
         """the signal meter from the next update on (include/rdsp.h, "signal meter and squelch"); again: a no-op.  Takes no
@@ -174,7 +169,7 @@ class Engine:
         n = int(n_blocks)
         level, peak = (torch.empty((self.n_channels, n), dtype=torch.float32, device=dev) for _ in range(2))
         gate = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
-        check(self.lib.rdsp_engine_read_meter(self.h, n, level.data_ptr(), n, peak.data_ptr(), n, gate.data_ptr(), n, self._stream(stream)))
+        check(self.lib.rdsp_engine_read_meter(self.h, n, level.data_ptr(), n, peak.data_ptr(), n, gate.data_ptr(), n, _stream(stream)))
         return level, peak, gate
 
     def active(self, stream=None):
@@ -183,7 +178,7 @@ class Engine:
         dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
         lst = torch.empty(self.n_channels, dtype=torch.int32, device=dev)
         cnt = torch.empty(1, dtype=torch.int32, device=dev)
-        check(self.lib.rdsp_engine_active(self.h, lst.data_ptr(), cnt.data_ptr(), self._stream(stream)))
+        check(self.lib.rdsp_engine_active(self.h, lst.data_ptr(), cnt.data_ptr(), _stream(stream)))
         if stream is not None:
             torch.cuda.ExternalStream(stream).synchronize()
         n = int(cnt.item())
@@ -202,7 +197,7 @@ class Engine:
         dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
         n = int(n_blocks) * 128
         out = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
-        check(self.lib.rdsp_engine_read_demod(self.h, int(n_blocks), out.data_ptr(), n, self._stream(stream)))
+        check(self.lib.rdsp_engine_read_demod(self.h, int(n_blocks), out.data_ptr(), n, _stream(stream)))
         return out
 
     def set_groups(self, first_channels):
@@ -324,8 +319,7 @@ class PreProcessor:
         assert nch == self.n_channels and two == 2 and n % 128 == 0 and d_iq.dtype == torch.int16 and d_iq.is_contiguous()
         if out is None:
             out = torch.empty_like(d_iq)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(self.lib.rdsp_preproc_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, C.c_void_p(s)))
+        check(self.lib.rdsp_preproc_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, _stream(stream)))
         return out
 
     def state(self):

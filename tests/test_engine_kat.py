@@ -6,7 +6,7 @@ and menus, on seeded int16 IQ (tests/golden/make_engine_kat.py; `--check` reprod
 
 `-m "not gpu"`: oracle/rdsp_engine_oracle.c, the restatement written from the image's code, against every case -- the
 int16 audio and the float buffers after each stage, BIT FOR BIT -- and the tables it generates against the object's.
-`-m gpu`: rdsp_engine_t (csrc/rdsp_engine.hip, host object csrc/rdsp_engine_host.hip) through the C-ABI against the same int16 audio, bit for bit as well: the
+`-m gpu`: rdsp_engine_t (csrc/rdsp_engine.hip, host object csrc/rdsp_engine_host.h and the host files it names) through the C-ABI against the same int16 audio, bit for bit as well: the
 kernels evaluate the same operations in the same order (the north-star's tolerance for float work is 1e-5; nothing of it
 is used here), on one channel per case, on all cases as channels of the same engine where the settings allow, and with
 the blocks cut into calls of different sizes."""

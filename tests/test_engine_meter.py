@@ -6,8 +6,10 @@ csrc/rdsp_meter.h as the kernel is compiled (-ffp-contract=off) -- plain and und
 directly -- bit for bit; and the gate model through every transition.
 `-m gpu`: the engine against the restatement applied to the rows rdsp_engine_read_demod returns, bit for bit: levels, peaks,
 gates, the gated audio, the active list; independent of the call split, of groups and regroupings, of the path the rows came
-by, and carried by a state blob.  Engines of 97 channels (a ragged last workgroup of the meter's four channels) and
-max_blocks 64 unless a test says otherwise."""
+by, and carried by a state blob -- also one with both optional parts, tuning phases and meter words, between engines on two
+sources at D = 2.  Engines of 97 channels (a ragged last workgroup of the meter's four channels) and max_blocks 64 unless a
+test says otherwise."""
+import functools
 import os
 import subprocess
 
@@ -545,3 +547,110 @@ def test_gpu_meter_refusals(rdsp):
     e.update(d); twin.update(d)
     for v, w in zip(e.read_meter(6), twin.read_meter(6)):
         assert torch.equal(v, w)
+
+
+# ---- state blobs with both optional parts: tuning phases and meter words ---------------------------------------------------
+SRC_D, SRC_NB, SRC_CUT = 2, 12, 6                                 # sources at 88 200 Hz, 12 blocks, saved after 6
+
+
+def _on_sources(x, stations, source_of, D):
+    """the rows of x (int16 [n, t, 2] at 44 100 Hz, as update takes them) as int16 source rows at D x 44 100 Hz: every row held
+    D times at an eighth of its size, moved from the LSB tuning offset, where update expects it, to its receiver's station, and
+    summed into its receiver's source"""
+    from engine_sources_model import TUNING_OFFSET
+    z = np.repeat(x[..., 0] + 1j * x[..., 1], D, 1) / 8.0
+    z = z * np.exp(2j * np.pi * ((np.asarray(stations)[:, None] - TUNING_OFFSET[0]) / (D * 44100.0)) * np.arange(z.shape[1]))
+    src = np.stack([z[[c for c in range(len(z)) if source_of[c] == k]].sum(0) for k in range(max(source_of) + 1)])
+    return np.stack([np.round(src.real), np.round(src.imag)], -1).astype(np.int16)
+
+
+def _sourced(n, max_blocks, stations, s=None, meter=True):
+    """an engine of n receivers, receiver c on source c % 2 of two int16 sources at D = 2, tuned to `stations`, with squelch s"""
+    e = _engine(n, max_blocks, meter)
+    e.set_meter(0.5, 0.5)
+    if s is not None:
+        e.set_squelch(s.open_ms, s.close_ms, s.hang_blocks)
+    e.set_sources(2, [c % 2 for c in range(n)])
+    e.set_source_decimation(SRC_D)
+    e.tune(0, stations)
+    return e
+
+
+def _play_sources(e, src, a, b, split):
+    """blocks a ... b - 1 of the source rows in calls of `split` -> audio [n, t]; level and gate [n, b - a] of an engine with the meter"""
+    import torch
+    audio, level, gate = [], [], []
+    for k in range(a, b, split):
+        m = min(b, k + split)
+        y = e.update_sources(torch.from_numpy(np.ascontiguousarray(src[:, k * 128 * SRC_D:m * 128 * SRC_D])).cuda()).cpu().numpy()
+        assert np.array_equal(y[..., 0], y[..., 1])
+        audio.append(y[..., 0])
+        if e.meter_enabled():
+            lv, _, g = (v.cpu().numpy() for v in e.read_meter(m - k))
+            level.append(lv); gate.append(g)
+    return np.concatenate(audio, 1), (np.concatenate(level, 1) if level else None), (np.concatenate(gate, 1) if gate else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _source_case():
+    """-> source rows int16 [2, 12 x 256, 2], the 12 stations, the squelch.  The bursts of _bursts at distinct stations, 6 kHz
+    apart, of two sources; a hang of 6 blocks and thresholds between the loud and the quiet levels an engine with the squelch
+    off measures on these rows.  The last 32 pairs in front of the cut are zero: a source's last 15 D pairs are its history,
+    which is in no blob, so an engine that takes the receivers over from a past of zero rows holds the same history."""
+    stations = -33000.0 + 6000.0 * np.arange(12)
+    src = _on_sources(_bursts(27, 12, SRC_NB, quiet=(9, 10, 12)), stations, [c % 2 for c in range(12)], SRC_D)
+    cut = SRC_CUT * 128 * SRC_D
+    src[:, cut - 32:cut] = 0
+    level = _play_sources(_sourced(12, 8, stations), src, 0, SRC_NB, SRC_CUT)[1]
+    open_ms, close_ms = _thresholds(level)
+    return src, stations, Squelch(open_ms, close_ms, 6, attack=0.5, decay=0.5)
+
+
+def _tail(blob, n):
+    """the words of a blob of n channels behind its channel words: the phases, then the meter words"""
+    return blob[16 + n * STATE_CH_BYTES:].view(np.uint32)
+
+
+@pytest.mark.gpu
+def test_gpu_state_with_phases_and_meter_continues(rdsp):
+    """engine A (12 receivers, max_blocks 8, two sources at D = 2, meter and squelch) plays 6 blocks and saves receivers 3 ... 6:
+    flags 3, a phase word and three meter words per channel behind the channel words.  Engine B (20 receivers, max_blocks 4, a
+    past of two zero blocks) takes them at 9 ... 12: the blob it saves there carries A's phase and meter words, and over the next
+    6 blocks -- A in one call, B in calls of 3 -- audio, level and gate of the four receivers agree bit for bit"""
+    src, stations, s = _source_case()
+    a = _sourced(12, 8, stations, s)
+    first = _play_sources(a, src, 0, SRC_CUT, SRC_CUT)
+    assert 0 < first[2].mean() < 1                                                       # gates open and closed
+    blob = a.save_state(3, 4)
+    assert len(blob) == 16 + 4 * (STATE_CH_BYTES + 4 + 12) == a.lib.rdsp_engine_state_bytes(a.h, 4)
+    assert list(blob[:16].view(np.uint32)) == [0x45534452, 1, 4, 3]
+    assert _tail(blob, 4)[:4].all() and _tail(blob, 4)[4::3].all()                       # phases that moved, levels above zero
+    b = _sourced(20, 4, np.zeros(20), s)
+    _play_sources(b, np.zeros((2, 2 * 128 * SRC_D, 2), np.int16), 0, 2, 2)              # a past of its own
+    b.tune(9, stations[3:7])
+    b.load_state(9, blob)
+    assert np.array_equal(_tail(b.save_state(9, 4), 4), _tail(blob, 4))
+    ra, rb = _play_sources(a, src, SRC_CUT, SRC_NB, SRC_NB - SRC_CUT), _play_sources(b, src, SRC_CUT, SRC_NB, 3)
+    assert np.array_equal(ra[0][3:7], rb[0][9:13]) and ra[0][3:7].any()
+    assert same_bits(ra[1][3:7], rb[1][9:13]) and np.array_equal(ra[2][3:7], rb[2][9:13])
+
+
+@pytest.mark.gpu
+def test_gpu_state_without_meter_words_zeroes_them(rdsp):
+    """receivers 3 ... 6 of an engine with sources and no meter, saved after 6 blocks (flags 1: phases only), loaded into engine A
+    at channel 0: A's meter state of channels 0 ... 3 is zero, that of 4 ... 11 as it was, and the blob A saves of 0 ... 3 carries
+    the loaded phase words and zero meter words"""
+    src, stations, s = _source_case()
+    a, u = _sourced(12, 8, stations, s), _sourced(12, 8, stations, s, meter=False)
+    for e in (a, u):
+        _play_sources(e, src, 0, SRC_CUT, SRC_CUT)
+    bu = u.save_state(3, 4)
+    assert len(bu) == 16 + 4 * (STATE_CH_BYTES + 4) == u.lib.rdsp_engine_state_bytes(u.h, 4)
+    assert list(bu[:16].view(np.uint32)) == [0x45534452, 1, 4, 1]
+    before, own = a.meter(), a.save_state(0, 4)
+    assert before[:4, 0].all() and before[4:, 0].all()
+    a.load_state(0, bu)
+    after, got = a.meter(), a.save_state(0, 4)
+    assert not after[:4].any() and np.array_equal(after[4:], before[4:])
+    assert np.array_equal(_tail(got, 4)[:4], _tail(bu, 4)) and not np.array_equal(_tail(got, 4)[:4], _tail(own, 4)[:4])
+    assert not _tail(got, 4)[4:].any() and _tail(own, 4)[4:].any()
