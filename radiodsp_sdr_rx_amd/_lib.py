@@ -393,3 +393,39 @@ def check(rc):
     if rc != RDSP_OK:
         raise RdspError(rc, load().rdsp_last_error().decode())
     return rc
+
+
+def stream_ptr(stream=None):
+    """The `void *` the library takes for a stream: None is torch's current stream, an int a raw hipStream_t handle, anything
+    else an object with `.cuda_stream` (a torch stream)."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream()
+    return C.c_void_p(getattr(stream, "cuda_stream", stream))
+
+
+class Handle:
+    """Owner of one library object: `lib` and the handle `h`, None until a create call succeeded and again after close().
+    A subclass names its destroy symbol; a refused create leaves an object whose finaliser has nothing to do."""
+    lib = h = None
+    _destroy = None
+
+    def _create(self, create, *args):
+        """`h` from a create symbol whose last argument receives the handle"""
+        self.lib = load()
+        h = C.c_void_p()
+        check(getattr(self.lib, create)(*args, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        h, self.h = self.h, None
+        if h:
+            rc = getattr(self.lib, self._destroy)(h)
+            if rc is not None:   # rdsp_audio_writer_close reports what the last write to the file came to
+                check(rc)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

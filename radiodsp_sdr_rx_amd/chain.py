@@ -15,29 +15,21 @@ from . import _lib
 from .config import make_config, synth_config
 
 
-def _stream_ptr(stream=None):
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return C.c_void_p(s.cuda_stream)
-
-
-class Chain:
+class Chain(_lib.Handle):
     # stage A3 of chains made without an explicit choice: None = the library's default (frequency domain with
     # frames of one granule: the bits do not depend on the call split); 0 = the direct form; 2 = the
     # frequency-domain decimator with 448-sample frames (what bench.py runs).  The GPU test modules run under
     # all three (tests/conftest.py `front_form`); the default itself is one of two kernels (set_fir_variant).
     default_fir_variant = None
+    _destroy = "rdsp_chain_destroy"
 
     def __init__(self, n_channels, max_blocks_per_call=512, device=0, fir_variant=None, **cfg):
-        self.lib = _lib.load()
         self.cfg = make_config(**cfg)
         self.n_channels = int(n_channels)
         self.device = int(device)
         self.decim = max(1, self.cfg.decim)
         self.fft_l = self.cfg.fft_l
-        h = C.c_void_p()
-        _lib.check(self.lib.rdsp_chain_create(C.byref(self.cfg), self.n_channels, self.device,
-                                              int(max_blocks_per_call), C.byref(h)))
-        self.h = h
+        self._create("rdsp_chain_create", C.byref(self.cfg), self.n_channels, self.device, int(max_blocks_per_call))
         if fir_variant is None and self.decim == 4:
             fir_variant = self.default_fir_variant
         if fir_variant is not None:
@@ -53,17 +45,6 @@ class Chain:
         """cut a stream in multiples of this and the bits do not depend on the cut: the call unit, but with 448-sample
         decimator frames (fir_variant 2) lcm(14, call unit) -- whole frames"""
         return self.lib.rdsp_chain_granule_blocks(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.rdsp_chain_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- the hot path ------------------------------------------------------
     def process(self, iq, out=None, out_f32=None, want_f32=False, stream=None):
@@ -84,24 +65,24 @@ class Chain:
         f32p = C.c_void_p(out_f32.data_ptr()) if out_f32 is not None else C.c_void_p(0)
         _lib.check(self.lib.rdsp_chain_process(
             self.h, C.c_void_p(iq.data_ptr()), iq.stride(0) // 2, n // 128,
-            C.c_void_p(out.data_ptr()), out.stride(0) // 2, f32p, _stream_ptr(stream)))
+            C.c_void_p(out.data_ptr()), out.stride(0) // 2, f32p, _lib.stream_ptr(stream)))
         return (out, out_f32) if want_f32 else out
 
     # ---- reference-named stage calls ----------------------------------------
     def doConvolutionalInitialize(self, stream=None):
-        _lib.check(self.lib.rdsp_doConvolutionalInitialize(self.h, _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_doConvolutionalInitialize(self.h, _lib.stream_ptr(stream)))
 
     def reInitializeFilter(self, dFLoCut, dFHiCut, stream=None):
-        _lib.check(self.lib.rdsp_reInitializeFilter(self.h, dFLoCut, dFHiCut, _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_reInitializeFilter(self.h, dFLoCut, dFHiCut, _lib.stream_ptr(stream)))
 
     def Init_LMS_NR(self, strength, stream=None):
-        _lib.check(self.lib.rdsp_Init_LMS_NR(self.h, int(strength), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_Init_LMS_NR(self.h, int(strength), _lib.stream_ptr(stream)))
 
     def LMS_NoiseReduction(self, nrbuffer, stream=None):
         """NR:66 in isolation: float32 cuda tensor [n_channels, n] processed in place."""
         assert nrbuffer.is_cuda and nrbuffer.dtype == torch.float32 and nrbuffer.is_contiguous()
         _lib.check(self.lib.rdsp_LMS_NoiseReduction(self.h, nrbuffer.shape[1], C.c_void_p(nrbuffer.data_ptr()),
-                                                   nrbuffer.stride(0), _stream_ptr(stream)))
+                                                   nrbuffer.stride(0), _lib.stream_ptr(stream)))
         return nrbuffer
 
     # ---- the law of the tail stage (A8 ALS, A9 AGC): include/rdsp.h rdsp_chain_set_tail_law ----------------------
@@ -123,7 +104,7 @@ class Chain:
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2 and audio.stride(1) == 1
         assert audio.shape[0] == self.n_channels
         _lib.check(self.lib.rdsp_chain_run_tail_f32(self.h, C.c_void_p(audio.data_ptr()), audio.stride(0), audio.shape[1],
-                                                   _stream_ptr(stream)))
+                                                   _lib.stream_ptr(stream)))
         return audio
 
     def doConvolutionalProcessing(self, iNRLevel, bFilterEnabled, dFLoCut, dFHiCut, iq, out=None,
@@ -135,7 +116,7 @@ class Chain:
         _lib.check(self.lib.rdsp_doConvolutionalProcessing(
             self.h, float(iNRLevel), int(bool(bFilterEnabled)), dFLoCut, dFHiCut,
             C.c_void_p(iq.data_ptr()), iq.stride(0) // 2, n // 128, C.c_void_p(out.data_ptr()),
-            out.stride(0) // 2, _stream_ptr(stream)))
+            out.stride(0) // 2, _lib.stream_ptr(stream)))
         return out
 
     def set_engine_literal(self, on, tables=None):
@@ -148,7 +129,7 @@ class Chain:
             _lib.check(self.lib.rdsp_sdr_load_engine_tables(self.h, b.ctypes.data_as(_lib._f32p), h.ctypes.data_as(_lib._f32p)))
 
     def reset(self, stream=None):
-        _lib.check(self.lib.rdsp_chain_reset(self.h, _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_chain_reset(self.h, _lib.stream_ptr(stream)))
 
     # ---- AudioSDR-style setters (INO:117-139, CTL:149-423) -------------------
     def enableAGC(self): _lib.check(self.lib.rdsp_sdr_enableAGC(self.h))
@@ -170,10 +151,10 @@ class Chain:
     def setIQgainBalance(self, g): _lib.check(self.lib.rdsp_sdr_setIQgainBalance(self.h, float(g)))
     def enableAudioFilter(self): _lib.check(self.lib.rdsp_sdr_enableAudioFilter(self.h))
     def setAudioFilter(self, f, stream=None):
-        _lib.check(self.lib.rdsp_sdr_setAudioFilter(self.h, int(f), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_sdr_setAudioFilter(self.h, int(f), _lib.stream_ptr(stream)))
     def setAudioFilterKind(self, kind, stream=None):
         """0: SDR.setAudioFilter() filters are overlap-save masks; 1: 8th-order IIR band-passes (biquads)"""
-        _lib.check(self.lib.rdsp_sdr_setAudioFilterKind(self.h, int(kind), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_sdr_setAudioFilterKind(self.h, int(kind), _lib.stream_ptr(stream)))
 
     def setAudioIIRCoefficients(self, coef20, group=None):
         """four sections {b0, b1, b2, a1, a2} (CMSIS order, feedback added) instead of the designed cascade"""
@@ -189,7 +170,7 @@ class Chain:
         return a
 
     def setDemodMode(self, mode, stream=None):
-        return int(self.lib.rdsp_sdr_setDemodMode(self.h, int(mode), _stream_ptr(stream)))
+        return int(self.lib.rdsp_sdr_setDemodMode(self.h, int(mode), _lib.stream_ptr(stream)))
     def setMute(self, m): _lib.check(self.lib.rdsp_sdr_setMute(self.h, int(bool(m))))
     def setTuningOffsetHz(self, hz): _lib.check(self.lib.rdsp_sdr_setTuningOffsetHz(self.h, float(hz)))
     def set_nr_level(self, lvl): _lib.check(self.lib.rdsp_set_nr_level(self.h, int(lvl)))
@@ -213,22 +194,22 @@ class Chain:
         return int(self.lib.rdsp_chain_groups(self.h))
 
     def group_reInitializeFilter(self, group, lo, hi, stream=None):
-        _lib.check(self.lib.rdsp_group_reInitializeFilter(self.h, int(group), float(lo), float(hi), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_group_reInitializeFilter(self.h, int(group), float(lo), float(hi), _lib.stream_ptr(stream)))
 
     def group_setAudioFilter(self, group, f, stream=None):
-        _lib.check(self.lib.rdsp_group_setAudioFilter(self.h, int(group), int(f), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_group_setAudioFilter(self.h, int(group), int(f), _lib.stream_ptr(stream)))
 
     def group_setDemodMode(self, group, mode, stream=None):
-        return int(self.lib.rdsp_group_setDemodMode(self.h, int(group), int(mode), _stream_ptr(stream)))
+        return int(self.lib.rdsp_group_setDemodMode(self.h, int(group), int(mode), _lib.stream_ptr(stream)))
 
     def group_setTuningOffsetHz(self, group, hz):
         _lib.check(self.lib.rdsp_group_setTuningOffsetHz(self.h, int(group), float(hz)))
 
     def group_pbt(self, group, edge, direction, stream=None):
-        _lib.check(self.lib.rdsp_group_pbt(self.h, int(group), int(edge), int(direction), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_group_pbt(self.h, int(group), int(edge), int(direction), _lib.stream_ptr(stream)))
 
     def group_tuningMode(self, group, mndx, vfo_hz, stream=None):
-        return int(self.lib.rdsp_group_tuningMode(self.h, int(group), int(mndx), float(vfo_hz), _stream_ptr(stream)))
+        return int(self.lib.rdsp_group_tuningMode(self.h, int(group), int(mndx), float(vfo_hz), _lib.stream_ptr(stream)))
 
     def group_mask(self, group):
         a = np.zeros(2 * self.fft_l, np.float32)
@@ -260,7 +241,7 @@ class Chain:
         _lib.check(self.lib.rdsp_chain_set_tail_variant(self.h, int(lanes_per_channel), int(matrix_reduce)))
 
     def flush(self, stream=None):
-        _lib.check(self.lib.rdsp_chain_flush(self.h, _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_chain_flush(self.h, _lib.stream_ptr(stream)))
 
     # ---- per-kernel timing (HIP events on the launch stream) -------------------
     def set_timing(self, on):
@@ -287,23 +268,23 @@ class Chain:
         size = self.lib.rdsp_chain_state_bytes(self.h, n)
         buf = np.zeros(size, np.uint8)
         _lib.check(self.lib.rdsp_chain_save_state(self.h, first_channel, n, buf.ctypes.data_as(C.c_void_p), size,
-                                                  _stream_ptr(stream)))
+                                                  _lib.stream_ptr(stream)))
         return buf
 
     def load_state(self, blob, first_channel=0, stream=None):
         blob = np.ascontiguousarray(blob, np.uint8)
         _lib.check(self.lib.rdsp_chain_load_state(self.h, first_channel, blob.ctypes.data_as(C.c_void_p), blob.size,
-                                                  _stream_ptr(stream)))
+                                                  _lib.stream_ptr(stream)))
 
     # ---- state read-back ------------------------------------------------------
     def scalars(self, stream=None):
         a = np.zeros((self.n_channels, 4), np.float32)
-        _lib.check(self.lib.rdsp_chain_get_scalars(self.h, a.ctypes.data_as(_lib._f32p), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_chain_get_scalars(self.h, a.ctypes.data_as(_lib._f32p), _lib.stream_ptr(stream)))
         return a
 
     def lms_coeffs(self, which=0, stream=None):
         a = np.zeros((self.n_channels, 96), np.float32)
-        _lib.check(self.lib.rdsp_chain_get_lms_coeffs(self.h, which, a.ctypes.data_as(_lib._f32p), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_chain_get_lms_coeffs(self.h, which, a.ctypes.data_as(_lib._f32p), _lib.stream_ptr(stream)))
         return a
 
     STATUS_NR_ENERGY, STATUS_NR_NONFINITE, STATUS_ALS_ENERGY, STATUS_ALS_NONFINITE = 0x01, 0x02, 0x10, 0x20
@@ -312,13 +293,13 @@ class Chain:
         """per-channel NLMS health words (include/rdsp.h RDSP_STATUS_*), uint32 [n_channels]"""
         import ctypes as C
         a = np.zeros(self.n_channels, np.uint32)
-        _lib.check(self.lib.rdsp_chain_get_status(self.h, a.ctypes.data_as(C.POINTER(C.c_uint32)), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_chain_get_status(self.h, a.ctypes.data_as(C.POINTER(C.c_uint32)), _lib.stream_ptr(stream)))
         return a
 
     def reset_nlms_channels(self, which, first_channel, n_channels=1, stream=None):
         """boot values for the NLMS instance (0 DSP-NR, 1 ALS) of a range of channels: the cure for a channel
         the health words name (include/rdsp.h rdsp_chain_reset_nlms_channels)"""
-        _lib.check(self.lib.rdsp_chain_reset_nlms_channels(self.h, int(which), int(first_channel), int(n_channels), _stream_ptr(stream)))
+        _lib.check(self.lib.rdsp_chain_reset_nlms_channels(self.h, int(which), int(first_channel), int(n_channels), _lib.stream_ptr(stream)))
 
     def mask(self):
         a = np.zeros(2 * self.fft_l, np.float32)

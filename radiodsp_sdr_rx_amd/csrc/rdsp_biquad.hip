@@ -302,10 +302,7 @@ extern "C" int rdsp_biquad_create(int n_channels, int device, double fs, rdsp_bi
     rdsp_set_error("rdsp_biquad_create: bad argument");
     return RDSP_ERR_INVALID;
   }
-  if (rdsp_device_count() <= 0) {
-    rdsp_set_error("no HIP device: the rdsp product path has no CPU fallback");
-    return RDSP_ERR_NO_DEVICE;
-  }
+  RC_TRY(rdsp_dev::need_device());
   rdsp_biquad_t *b = new rdsp_biquad();
   b->n_channels = n_channels;
   b->device = device;
@@ -419,19 +416,18 @@ extern "C" int rdsp_biquad_update(rdsp_biquad_t *b, const int16_t *d_in, size_t 
 
 /* ---- the node: `AudioFilterBiquad biquad1;` (INO:58), one input, one output ------------------- */
 namespace {
-struct BiquadNode {
+struct BiquadNode : rdsp_node_dev::NodeDev<> { /* on the object's device (a process may drive several GPUs) */
   rdsp_biquad_t *bq;
   int n_channels;
-  rdsp_node_dev::NodeDev<> dev; /* on the object's device (a process may drive several GPUs) */
 };
 void biquad_node_update(rdsp_node_t *n, void *u) {
-  BiquadNode *s = static_cast<BiquadNode *>(u);
+  BiquadNode *s = rdsp_node_dev::node_of<BiquadNode>(u);
   rdsp_block_t *in = rdsp_receive_readonly(n, 0);
   if (!in) return; /* no input this tick: nothing is transmitted */
   rdsp_block_t *out = rdsp_allocate(n); /* before the upload: the download goes straight into it */
   if (!out) { rdsp_release(in); return; }
   const size_t len = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES;
-  const bool ok = s->dev.run("biquad node", rdsp_block_data(in), len, [&](int16_t *d_in, int16_t *d_out, hipStream_t st) {
+  const bool ok = s->run("biquad node", rdsp_block_data(in), len, [&](int16_t *d_in, int16_t *d_out, hipStream_t st) {
     return rdsp_biquad_update(s->bq, d_in, RDSP_BLOCK_SAMPLES, 1, 1, d_out, RDSP_BLOCK_SAMPLES, 1, st);
   }, rdsp_block_data(out), len);
   if (ok) rdsp_transmit(n, out, 0);
@@ -451,7 +447,4 @@ extern "C" rdsp_node_t *rdsp_biquad_node_create(rdsp_graph_t *g, rdsp_biquad_t *
   const size_t len = (size_t)s->n_channels * RDSP_BLOCK_SAMPLES;
   return rdsp_node_dev::make_node(g, 1, biquad_node_update, s, "rdsp_biquad_node_create", bq->device, len, len);
 }
-extern "C" int rdsp_biquad_node_status(rdsp_node_t *n) {
-  BiquadNode *s = static_cast<BiquadNode *>(rdsp_node_user(n));
-  return s ? s->dev.status : RDSP_ERR_INVALID;
-}
+extern "C" int rdsp_biquad_node_status(rdsp_node_t *n) { return rdsp_node_dev::node_status(n); }

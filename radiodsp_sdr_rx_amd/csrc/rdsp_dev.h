@@ -63,6 +63,13 @@ static inline int hip_fail(const char *expr, hipError_t e, const char *file, int
   return RDSP_ERR_HIP;
 }
 
+/* in front of every create that has no wording of its own for it: RDSP_OK, or the refusal on a machine without a device */
+static inline int need_device() {
+  if (rdsp_device_count() > 0) return RDSP_OK;
+  rdsp_set_error("no HIP device: the rdsp product path has no CPU fallback");
+  return RDSP_ERR_NO_DEVICE;
+}
+
 }  // namespace rdsp_dev
 
 /* the try macros of every host file: a failed HIP call sets the error text and returns RDSP_ERR_HIP, a failed rdsp call

@@ -8,7 +8,7 @@
  * output[i] = sqrt_uint32_approx(re^2 + im^2) for bins 0..511; window (AudioWindowHanning1024,
  * INO:147), twiddles and the square root's guess table are those of the reference's firmware
  * image (rdsp_q15_tables.c).  Integer arithmetic: bit-exact against the CPU restatement kept
- * with the tests.
+ * with the tests.  The object's node is the analyser node of rdsp_graph_sdr.hip.
  *
  * One wave per channel.  Lane t runs the four butterflies b = t + 64 m of each of the five
  * stages (span L = 256, 64, 16, 4, 1); the packed int16 pairs go through a 4 KiB LDS buffer
@@ -18,11 +18,9 @@
 #include <math.h>
 #include <string.h>
 
-#include <vector>
-
 #include "rdsp_host.h"
-#include "rdsp_node_dev.h"
 #include "rdsp_q15.h"
+#include "rdsp_q15_host.h"
 #include "rdsp_sync.h"
 
 struct RdspFft1024Params {
@@ -132,77 +130,24 @@ __global__ void __launch_bounds__(64) rdsp_fft1024_kernel(RdspFft1024Params p) {
 }
 }  // namespace
 
-struct rdsp_fft1024 {
-  int n_channels, device;
-  int has_window = 0;
-  int have = 0; /* samples buffered per channel */
-  rdsp_dev::DevBuf<int16_t> d_window, d_hist;
-  rdsp_dev::DevBuf<uint16_t> d_guess;
-  rdsp_dev::DevBuf<uint32_t> d_twid;
-};
-
-static int fft1024_upload_window(rdsp_fft1024_t *s, const int16_t *w1024) {
-  s->has_window = w1024 != nullptr;
-  if (w1024) HIP_TRY(hipMemcpy(s->d_window, w1024, 1024 * sizeof(int16_t), hipMemcpyHostToDevice));
-  return RDSP_OK;
-}
-static int fft1024_upload_window_id(rdsp_fft1024_t *s, int window_id) {
-  if (window_id == RDSP_WINDOW_NONE) return fft1024_upload_window(s, nullptr);
-  if (window_id < 0 || window_id > RDSP_WINDOW_TUKEY) {
-    rdsp_set_error("unknown window id %d", window_id);
-    return RDSP_ERR_INVALID;
-  }
-  std::vector<int16_t> w(1024);
-  rdsp_window_q15_n(window_id, 1024, w.data());
-  return fft1024_upload_window(s, w.data());
-}
-
+/* ---- host side: struct rdsp_fft1024 and the tables' half are rdsp_q15_host.h's ------------- */
 extern "C" int rdsp_fft1024_create(int n_channels, int device, int window_id, rdsp_fft1024_t **out) {
   if (!out || n_channels <= 0) {
     rdsp_set_error("rdsp_fft1024_create: bad argument");
     return RDSP_ERR_INVALID;
   }
-  if (rdsp_device_count() <= 0) {
-    rdsp_set_error("no HIP device: the rdsp product path has no CPU fallback");
-    return RDSP_ERR_NO_DEVICE;
-  }
-  rdsp_fft1024_t *s = new rdsp_fft1024();
-  s->n_channels = n_channels;
-  s->device = device;
-  std::vector<uint32_t> tw(768);
-  rdsp_q15_twiddles(1024, tw.data());
-  if (hipSetDevice(device) != hipSuccess || s->d_window.alloc(1024) != hipSuccess || s->d_twid.alloc(768) != hipSuccess ||
-      s->d_guess.alloc(33) != hipSuccess || s->d_hist.alloc((size_t)n_channels * 896) != hipSuccess ||
-      hipMemset(s->d_hist, 0, (size_t)n_channels * 896 * sizeof(int16_t)) != hipSuccess ||
-      hipMemcpy(s->d_twid, tw.data(), 768 * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s->d_guess, rdsp_sqrt_guess_table(), 33 * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess ||
-      fft1024_upload_window_id(s, window_id) != RDSP_OK) {
-    rdsp_set_error("rdsp_fft1024_create: device set-up failed");
-    rdsp_fft1024_destroy(s);
-    return RDSP_ERR_HIP;
-  }
-  *out = s;
-  return RDSP_OK;
+  RC_TRY(rdsp_dev::need_device());
+  return rdsp_q15_host::create(out, [&](rdsp_fft1024_t *s) {
+    RC_TRY(s->init(n_channels, device, 1024, window_id));
+    HIP_TRY(rdsp_dev::alloc_zero(s->d_hist, (size_t)n_channels * 896));
+    return (int)RDSP_OK;
+  });
 }
-extern "C" void rdsp_fft1024_destroy(rdsp_fft1024_t *s) {
-  if (!s) return;
-  (void)hipSetDevice(s->device);
-  delete s;
-}
-extern "C" int rdsp_fft1024_windowFunction(rdsp_fft1024_t *s, int window_id) {
-  if (!s) return RDSP_ERR_INVALID;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  return fft1024_upload_window_id(s, window_id);
-}
-/* windowFunction(const int16_t *w) with the library's own argument: a host pointer to 1024 q15 taps
- * (AudioWindowHanning1024, INO:147) or NULL */
-extern "C" int rdsp_fft1024_windowFunction_table(rdsp_fft1024_t *s, const int16_t *w1024) {
-  if (!s) return RDSP_ERR_INVALID;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  return fft1024_upload_window(s, w1024);
-}
+extern "C" void rdsp_fft1024_destroy(rdsp_fft1024_t *s) { rdsp_q15_host::destroy(s); }
+/* windowFunction by table name (INO:147), and windowFunction(const int16_t *w) with the library's own argument: a host
+ * pointer to 1024 q15 taps (AudioWindowHanning1024) or NULL */
+extern "C" int rdsp_fft1024_windowFunction(rdsp_fft1024_t *s, int window_id) { return rdsp_q15_host::public_set_window_id(s, window_id); }
+extern "C" int rdsp_fft1024_windowFunction_table(rdsp_fft1024_t *s, const int16_t *w1024) { return rdsp_q15_host::public_set_window(s, w1024); }
 /* AudioFFT.averageTogether(30) (INO:148): the library's 1024-point analyser declares it and does
  * nothing with it ("not implemented yet"); accepted and ignored here too */
 extern "C" int rdsp_fft1024_averageTogether(rdsp_fft1024_t *s, int n) {
@@ -245,73 +190,8 @@ extern "C" int rdsp_fft1024_update(rdsp_fft1024_t *s, const int16_t *d_audio, si
   p.out_stride = out_stride;
   p.keep = nf > 0 ? total - 512 * nf : total; /* 4..7 blocks once frames run, everything before */
   hipLaunchKernelGGL(rdsp_fft1024_kernel, dim3(s->n_channels), dim3(64), 0, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    rdsp_set_error("fft1024 kernel launch failed: %s", hipGetErrorString(e));
-    return RDSP_ERR_HIP;
-  }
+  RC_TRY(rdsp_q15_host::launched("fft1024"));
   s->have = p.keep;
   if (n_outputs) *n_outputs = nf;
   return RDSP_OK;
-}
-
-/* ---- the node: one input (Q_out_L in the sketch), no outputs ------------------------------ */
-namespace {
-struct Fft1024Node {
-  rdsp_fft1024_t *an;
-  int n_channels;
-  std::vector<uint16_t> h_out; /* [ch][512] */
-  rdsp_node_dev::NodeDev<uint16_t> dev; /* on the object's device (a process may drive several GPUs) */
-  int outputflag = 0;
-};
-void fft1024_node_update(rdsp_node_t *n, void *u) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(u);
-  rdsp_block_t *b = rdsp_receive_readonly(n, 0);
-  if (!b) return;
-  int n_out = 0;
-  const bool ok = s->dev.run("fft1024 node", rdsp_block_data(b), (size_t)s->n_channels * RDSP_BLOCK_SAMPLES,
-                             [&](int16_t *d_in, uint16_t *d_out, hipStream_t st) {
-                               return rdsp_fft1024_update(s->an, d_in, RDSP_BLOCK_SAMPLES, 1, 1, d_out, 1, &n_out, st);
-                             }, s->h_out.data(), s->h_out.size(), &n_out);
-  rdsp_release(b); /* after the synchronize: the upload read it */
-  if (ok && n_out > 0) s->outputflag = 1;
-}
-}  // namespace
-
-extern "C" rdsp_node_t *rdsp_fft1024_node_create(rdsp_graph_t *g, rdsp_fft1024_t *an) {
-  if (!g || !an || an->n_channels != rdsp_graph_channels(g)) {
-    rdsp_set_error("rdsp_fft1024_node_create: bad argument (the analyser needs the graph's channel count)");
-    return nullptr;
-  }
-  Fft1024Node *s = new Fft1024Node();
-  s->an = an;
-  s->n_channels = an->n_channels;
-  s->h_out.assign((size_t)s->n_channels * 512, 0);
-  return rdsp_node_dev::make_node(g, 1, fft1024_node_update, s, "rdsp_fft1024_node_create", an->device,
-                                  (size_t)s->n_channels * RDSP_BLOCK_SAMPLES, s->h_out.size());
-}
-extern "C" int rdsp_fft1024_node_available(rdsp_node_t *n) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
-  if (!s) return 0;
-  const int f = s->outputflag;
-  s->outputflag = 0;
-  return f;
-}
-extern "C" const uint16_t *rdsp_fft1024_node_output(rdsp_node_t *n) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
-  return s ? s->h_out.data() : nullptr;
-}
-extern "C" float rdsp_fft1024_node_read(rdsp_node_t *n, int ch, unsigned int binNumber) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
-  if (!s || ch < 0 || ch >= s->n_channels) return 0.0f;
-  return rdsp_fft1024_read(s->h_out.data() + (size_t)ch * 512, binNumber);
-}
-extern "C" float rdsp_fft1024_node_read_range(rdsp_node_t *n, int ch, unsigned int binFirst, unsigned int binLast) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
-  if (!s || ch < 0 || ch >= s->n_channels) return 0.0f;
-  return rdsp_fft1024_read_range(s->h_out.data() + (size_t)ch * 512, binFirst, binLast);
-}
-extern "C" int rdsp_fft1024_node_status(rdsp_node_t *n) {
-  Fft1024Node *s = static_cast<Fft1024Node *>(rdsp_node_user(n));
-  return s ? s->dev.status : RDSP_ERR_INVALID;
 }

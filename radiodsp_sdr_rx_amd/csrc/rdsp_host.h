@@ -25,6 +25,9 @@ void rdsp_set_error(const char *fmt, ...);
 void rdsp_arm_sin_table(float *tab513);          /* sinTable_f32 of arm_sin_f32 / arm_cos_f32 */
 void rdsp_q15_twiddles(int n, uint32_t *out);   /* [3n/4] cos | sin << 16 of 2 pi m / n, twiddleCoef_4096_q15's rule */
 const uint16_t *rdsp_sqrt_guess_table(void);   /* [33] */
+/* read(bin) / read(first, last) of an analyser's output row of `bins` magnitudes; inclusive: binLast is added too */
+float rdsp_q15_read(const uint16_t *output, unsigned int bins, unsigned int binNumber);
+float rdsp_q15_read_range(const uint16_t *output, unsigned int bins, unsigned int binFirst, unsigned int binLast, int inclusive);
 void rdsp_host_fft(double *re, double *im, int n); /* in-place radix-2 forward transform, n a power of two */
 
 #ifdef __cplusplus

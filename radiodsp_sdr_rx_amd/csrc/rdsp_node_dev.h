@@ -1,7 +1,9 @@
 /*
- * rdsp_node_dev.h -- what the graph nodes that run a device object have in common: an input and an output buffer and a
- * stream on the object's device (NodeDev), one tile's round trip through them (NodeDev::run), the node made of a user
- * struct that holds a NodeDev as `dev` (make_node), and the planar tiles <-> interleaved pairs copies.
+ * rdsp_node_dev.h -- what the graph nodes that run a device object have in common: the device and the status word
+ * (NodeBase: the node's user pointer points at it, whatever the kind of node, so that destroy_node and every *_node_status
+ * read it without knowing the kind), an input and an output buffer and a stream on the object's device (NodeDev), one
+ * tile's round trip through them (NodeDev::run), the node made of a user struct derived from a NodeDev (make_node), and the
+ * planar tiles <-> interleaved pairs copies.
  */
 #ifndef RDSP_NODE_DEV_H
 #define RDSP_NODE_DEV_H
@@ -10,9 +12,18 @@
 
 namespace rdsp_node_dev {
 
-template <typename Out = int16_t>
-struct NodeDev {
+struct NodeBase {
   int device = 0, status = RDSP_OK;
+};
+/* the user struct of kind T behind a node's user pointer; the status of any device node */
+template <typename T> T *node_of(void *u) { return static_cast<T *>(static_cast<NodeBase *>(u)); }
+static inline int node_status(rdsp_node_t *n) {
+  const NodeBase *b = static_cast<NodeBase *>(rdsp_node_user(n));
+  return b ? b->status : RDSP_ERR_INVALID;
+}
+
+template <typename Out = int16_t>
+struct NodeDev : NodeBase {
   rdsp_dev::Stream stream;
   rdsp_dev::DevBuf<int16_t> d_in;
   rdsp_dev::DevBuf<Out> d_out;
@@ -43,8 +54,8 @@ struct NodeDev {
 
 template <typename T>
 void destroy_node(void *u) {
-  T *s = static_cast<T *>(u);
-  (void)hipSetDevice(s->dev.device);
+  T *s = node_of<T>(u);
+  (void)hipSetDevice(s->device);
   delete s;
 }
 /* the node of the freshly made *s, which it owns from here on: nullptr (and *s deleted) when the device or the graph refuses */
@@ -52,10 +63,11 @@ template <typename T>
 rdsp_node_t *make_node(rdsp_graph_t *g, int ninputs, rdsp_update_fn update, T *s, const char *who, int device, size_t n_in,
                        size_t n_out) {
   rdsp_node_t *n = nullptr;
-  if (!s->dev.create(device, n_in, n_out)) rdsp_set_error("%s: device allocation failed", who);
-  else n = rdsp_node_create(g, ninputs, update, s);
+  NodeBase *u = s;
+  if (!s->create(device, n_in, n_out)) rdsp_set_error("%s: device allocation failed", who);
+  else n = rdsp_node_create(g, ninputs, update, u);
   if (n) rdsp_node_set_destructor(n, destroy_node<T>);
-  else destroy_node<T>(s);
+  else destroy_node<T>(u);
   return n;
 }
 

@@ -88,45 +88,34 @@ uint32_t rdsp_sqrt_uint32_approx(uint32_t in) {
   return n;
 }
 
-/* float read(unsigned int binNumber), FFTIQ.h:70-73 */
-float rdsp_spectrum_read(const uint16_t *output, unsigned int binNumber) {
-  if (binNumber > 255) return 0.0f;
+/* float read(unsigned int binNumber), FFTIQ.h:70-73, over a row of `bins` magnitudes */
+float rdsp_q15_read(const uint16_t *output, unsigned int bins, unsigned int binNumber) {
+  if (binNumber >= bins) return 0.0f;
   return (float)(output[binNumber]) * (float)(1.0 / 16384.0);
 }
-/* float read(unsigned int binFirst, unsigned int binLast), FFTIQ.h:75-86, with its loop as written:
- * `do { sum += output[binFirst++]; } while (binFirst < binLast);` adds bins binFirst .. binLast - 1,
- * and the single bin binFirst when the two are equal -- binLast itself is never added. */
+/* float read(unsigned int binFirst, unsigned int binLast) with its loop as written.  FFTIQ.h:75-86 has
+ * `do { sum += output[binFirst++]; } while (binFirst < binLast);`: bins binFirst .. binLast - 1, and the single bin
+ * binFirst when the two are equal -- binLast itself is never added.  AudioAnalyzeFFT1024::read of the Teensy Audio
+ * library (the display's reader of AudioFFT, INO:57) has `<=`: binLast is added (`inclusive`). */
+float rdsp_q15_read_range(const uint16_t *output, unsigned int bins, unsigned int binFirst, unsigned int binLast, int inclusive) {
+  if (binFirst > binLast) {
+    const unsigned int tmp = binLast;
+    binLast = binFirst;
+    binFirst = tmp;
+  }
+  if (binFirst >= bins) return 0.0f;
+  if (binLast >= bins) binLast = bins - 1;
+  uint32_t sum = 0;
+  do {
+    sum += output[binFirst++];
+  } while (binFirst < binLast + (inclusive ? 1u : 0u));
+  return (float)sum * (float)(1.0 / 16384.0);
+}
+float rdsp_spectrum_read(const uint16_t *output, unsigned int binNumber) { return rdsp_q15_read(output, 256, binNumber); }
 float rdsp_spectrum_read_range(const uint16_t *output, unsigned int binFirst, unsigned int binLast) {
-  if (binFirst > binLast) {
-    const unsigned int tmp = binLast;
-    binLast = binFirst;
-    binFirst = tmp;
-  }
-  if (binFirst > 255) return 0.0f;
-  if (binLast > 255) binLast = 255;
-  uint32_t sum = 0;
-  do {
-    sum += output[binFirst++];
-  } while (binFirst < binLast);
-  return (float)sum * (float)(1.0 / 16384.0);
+  return rdsp_q15_read_range(output, 256, binFirst, binLast, 0);
 }
-/* AudioAnalyzeFFT1024::read of the Teensy Audio library (the display's reader of AudioFFT, INO:57):
- * same shape over 512 bins */
-float rdsp_fft1024_read(const uint16_t *output, unsigned int binNumber) {
-  if (binNumber > 511) return 0.0f;
-  return (float)(output[binNumber]) * (float)(1.0 / 16384.0);
-}
+float rdsp_fft1024_read(const uint16_t *output, unsigned int binNumber) { return rdsp_q15_read(output, 512, binNumber); }
 float rdsp_fft1024_read_range(const uint16_t *output, unsigned int binFirst, unsigned int binLast) {
-  if (binFirst > binLast) {
-    const unsigned int tmp = binLast;
-    binLast = binFirst;
-    binFirst = tmp;
-  }
-  if (binFirst > 511) return 0.0f;
-  if (binLast > 511) binLast = 511;
-  uint32_t sum = 0;
-  do {
-    sum += output[binFirst++];
-  } while (binFirst <= binLast);
-  return (float)sum * (float)(1.0 / 16384.0);
+  return rdsp_q15_read_range(output, 512, binFirst, binLast, 1);
 }

@@ -22,9 +22,9 @@
 
 #include <vector>
 
-#include "rdsp_dev.h"
 #include "rdsp_host.h"
 #include "rdsp_q15.h"
+#include "rdsp_q15_host.h"
 #include "rdsp_sync.h"
 
 struct RdspSpecParams {
@@ -169,51 +169,7 @@ __global__ void __launch_bounds__(64) rdsp_spectrum_kernel(RdspSpecParams p) {
 }
 }  // namespace
 
-/* ---- host side -------------------------------------------------------------- */
-struct rdsp_spectrum {
-  int n_channels, device;
-  int naverage;
-  int has_window; /* `const int16_t *window` non-NULL, FFTIQ.h:101, FFTIQ.cpp:81 */
-  int have_prev, count;
-  rdsp_dev::DevBuf<int16_t> d_window;
-  rdsp_dev::DevBuf<uint16_t> d_guess;
-  rdsp_dev::DevBuf<uint32_t> d_twid, d_prev, d_sum;
-};
-
-/* windowFunction(const int16_t *w), FFTIQ.h:93-95: the analyser keeps the caller's table (a copy
- * here: the table lives in device memory); NULL switches the window off (FFTIQ.cpp:81) */
-static int upload_window(rdsp_spectrum_t *s, const int16_t *w256) {
-  s->has_window = w256 != nullptr;
-  if (w256) HIP_TRY(hipMemcpy(s->d_window, w256, 256 * sizeof(int16_t), hipMemcpyHostToDevice));
-  return RDSP_OK;
-}
-static int upload_window_id(rdsp_spectrum_t *s, int window_id) {
-  int16_t w[256];
-  if (window_id == RDSP_WINDOW_NONE) return upload_window(s, nullptr);
-  if (window_id < 0 || window_id > RDSP_WINDOW_TUKEY) {
-    rdsp_set_error("unknown window id %d", window_id);
-    return RDSP_ERR_INVALID;
-  }
-  rdsp_window_q15(window_id, w);
-  return upload_window(s, w);
-}
-static int spectrum_setup(rdsp_spectrum_t *s, int window_id) {
-  const size_t nch = (size_t)s->n_channels;
-  uint32_t tw[192];
-  rdsp_q15_twiddles(256, tw);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(s->d_window.alloc(256));
-  HIP_TRY(s->d_twid.alloc(192));
-  HIP_TRY(s->d_guess.alloc(33));
-  HIP_TRY(s->d_prev.alloc(nch * 128));
-  HIP_TRY(s->d_sum.alloc(nch * 256));
-  HIP_TRY(hipMemset(s->d_prev, 0, nch * 128 * sizeof(uint32_t)));
-  HIP_TRY(hipMemset(s->d_sum, 0, nch * 256 * sizeof(uint32_t)));
-  HIP_TRY(hipMemcpy(s->d_twid, tw, sizeof(tw), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->d_guess, rdsp_sqrt_guess_table(), 33 * sizeof(uint16_t), hipMemcpyHostToDevice));
-  return upload_window_id(s, window_id);
-}
-
+/* ---- host side: struct rdsp_spectrum and the tables' half are rdsp_q15_host.h's ------------- */
 /* AudioAnalyzeFFT256IQ() with explicit settings (the constructor's own are rdsp_spectrum_create_default) */
 extern "C" int rdsp_spectrum_create(int n_channels, int device, int naverage, int window_id,
                                     rdsp_spectrum_t **out) {
@@ -221,24 +177,15 @@ extern "C" int rdsp_spectrum_create(int n_channels, int device, int naverage, in
     rdsp_set_error("rdsp_spectrum_create: bad argument");
     return RDSP_ERR_INVALID;
   }
-  if (rdsp_device_count() <= 0) {
-    rdsp_set_error("no HIP device: the rdsp product path has no CPU fallback");
-    return RDSP_ERR_NO_DEVICE;
-  }
-  rdsp_spectrum_t *s = new rdsp_spectrum();
-  s->n_channels = n_channels;
-  s->device = device;
-  s->naverage = naverage <= 0 ? 1 : naverage; /* averageTogether, FFTIQ.h:88-91 */
-  s->has_window = 0;
-  s->have_prev = 0;
-  s->count = 0;
-  const int rc = spectrum_setup(s, window_id);
-  if (rc != RDSP_OK) { /* the half-made object is destroyed, not leaked */
-    rdsp_spectrum_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return RDSP_OK;
+  RC_TRY(rdsp_dev::need_device());
+  return rdsp_q15_host::create(out, [&](rdsp_spectrum_t *s) {
+    const size_t nch = (size_t)n_channels;
+    s->naverage = naverage <= 0 ? 1 : naverage; /* averageTogether, FFTIQ.h:88-91 */
+    RC_TRY(s->init(n_channels, device, 256, window_id));
+    HIP_TRY(rdsp_dev::alloc_zero(s->d_prev, nch * 128));
+    HIP_TRY(rdsp_dev::alloc_zero(s->d_sum, nch * 256));
+    return (int)RDSP_OK;
+  });
 }
 /* AudioAnalyzeFFT256IQ(), FFTIQ.h:55-60: window(AudioWindowBlackmanNuttall256), naverage(8) */
 extern "C" int rdsp_spectrum_create_default(int n_channels, int device, rdsp_spectrum_t **out) {
@@ -246,31 +193,17 @@ extern "C" int rdsp_spectrum_create_default(int n_channels, int device, rdsp_spe
 }
 
 extern "C" int rdsp_spectrum_device(const rdsp_spectrum_t *s) { return s ? s->device : -1; }
-extern "C" void rdsp_spectrum_destroy(rdsp_spectrum_t *s) {
-  if (!s) return;
-  (void)hipSetDevice(s->device);
-  delete s;
-}
+extern "C" void rdsp_spectrum_destroy(rdsp_spectrum_t *s) { rdsp_q15_host::destroy(s); }
 
 extern "C" int rdsp_spectrum_averageTogether(rdsp_spectrum_t *s, int n) { /* FFTIQ.h:88-91 */
   if (!s || n > 255) return RDSP_ERR_INVALID;
   s->naverage = n <= 0 ? 1 : n;
   return RDSP_OK;
 }
-extern "C" int rdsp_spectrum_windowFunction(rdsp_spectrum_t *s, int window_id) { /* FFTIQ.h:93-95 */
-  if (!s) return RDSP_ERR_INVALID;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  return upload_window_id(s, window_id);
-}
-/* void windowFunction(const int16_t *w), FFTIQ.h:93-95, with the reference's own argument: a
- * host pointer to 256 q15 taps (e.g. AudioWindowHanning256, INO:144), or NULL for no window */
-extern "C" int rdsp_spectrum_windowFunction_table(rdsp_spectrum_t *s, const int16_t *w256) {
-  if (!s) return RDSP_ERR_INVALID;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  return upload_window(s, w256);
-}
+/* windowFunction by table name, and void windowFunction(const int16_t *w), FFTIQ.h:93-95, with the reference's own
+ * argument: a host pointer to 256 q15 taps (e.g. AudioWindowHanning256, INO:144), or NULL for no window */
+extern "C" int rdsp_spectrum_windowFunction(rdsp_spectrum_t *s, int window_id) { return rdsp_q15_host::public_set_window_id(s, window_id); }
+extern "C" int rdsp_spectrum_windowFunction_table(rdsp_spectrum_t *s, const int16_t *w256) { return rdsp_q15_host::public_set_window(s, w256); }
 
 /* the reference's frame counter over `frames` frames: `if (++count == naverage) { output; count = 0; }`
  * with `uint8_t count` (FFTIQ.h:105, FFTIQ.cpp:99-100) -- an averageTogether() below the running count
@@ -351,11 +284,7 @@ extern "C" int rdsp_spectrum_update(rdsp_spectrum_t *s, const int16_t *d_iq, siz
   p.out = d_out;
   p.out_stride = out_stride;
   hipLaunchKernelGGL(rdsp_spectrum_kernel, dim3(s->n_channels), dim3(64), 0, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    rdsp_set_error("spectrum kernel launch failed: %s", hipGetErrorString(e));
-    return RDSP_ERR_HIP;
-  }
+  RC_TRY(rdsp_q15_host::launched("spectrum"));
   const int frames = n_blocks - (s->have_prev ? 0 : 1);
   advance_count(&s->count, s->naverage, frames, nullptr);
   s->have_prev = 1;

@@ -197,10 +197,7 @@ extern "C" int rdsp_survey_create(int n_sources, int device, int fft_n, int navg
                    "max_pairs_per_call at least 1");
     return RDSP_ERR_INVALID;
   }
-  if (rdsp_device_count() <= 0) {
-    rdsp_set_error("no HIP device: the rdsp product path has no CPU fallback");
-    return RDSP_ERR_NO_DEVICE;
-  }
+  RC_TRY(rdsp_dev::need_device());
   std::vector<float> w((size_t)fft_n);
   RC_TRY(rdsp_survey_window(fft_n, w.data()));
   rdsp_survey_t *s = new rdsp_survey();

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, load
+from ._lib import Handle, check, load, stream_ptr
 
 LSBmode, USBmode, CW_LSBmode, CW_USBmode, AMmode, SAMmode = range(6)      # as the compiled tuningMode() passes them
 audioAM, audioCW, audio2100, audio2700, audio3100, audioNone = 0, 1, 3, 6, 8, 10
@@ -19,27 +19,14 @@ def _src_dtype(fmt):
     return (torch.int16, torch.uint8, torch.int8, torch.float32)[fmt]
 
 
-def _stream(stream):
-    """the void * the library takes: the caller's stream handle, or torch's current stream"""
-    import torch
-    return C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+class Engine(Handle):
+    _destroy = "rdsp_engine_destroy"
 
-
-class Engine:
     def __init__(self, n_channels, max_blocks_per_call=64, device=0, tables=None):
-        self.lib = load()
-        h = C.c_void_p()
-        check(self.lib.rdsp_engine_create(n_channels, device, max_blocks_per_call, C.byref(h)))
-        self.h, self.n_channels, self.max_blocks = h, n_channels, max_blocks_per_call
+        self._create("rdsp_engine_create", n_channels, device, max_blocks_per_call)
+        self.n_channels, self.max_blocks = n_channels, max_blocks_per_call
         if tables is not None:
             self.load_tables(*tables)
-
-    def close(self):
-        if self.h:
-            self.lib.rdsp_engine_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def load_tables(self, biquad_sets, hilbert64):
         b = np.ascontiguousarray(biquad_sets, np.float32).reshape(-1)
@@ -64,7 +51,7 @@ class Engine:
         assert nch == self.n_channels and two == 2 and n % 128 == 0 and d_iq.dtype == torch.int16 and d_iq.is_contiguous()
         if out is None:
             out = torch.empty_like(d_iq)
-        check(self.lib.rdsp_engine_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, _stream(stream)))
+        check(self.lib.rdsp_engine_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, stream_ptr(stream)))
         return out
 
     def set_sources(self, n_sources, source_of_channel):
@@ -139,7 +126,7 @@ class Engine:
         n = n_blocks * 128
         if out is None:
             out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
-        check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), stride, n_blocks, out.data_ptr(), n, _stream(stream)))
+        check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), stride, n_blocks, out.data_ptr(), n, stream_ptr(stream)))
         return out
 
     def enable_meter(self):
@@ -169,7 +156,7 @@ class Engine:
         n = int(n_blocks)
         level, peak = (torch.empty((self.n_channels, n), dtype=torch.float32, device=dev) for _ in range(2))
         gate = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
-        check(self.lib.rdsp_engine_read_meter(self.h, n, level.data_ptr(), n, peak.data_ptr(), n, gate.data_ptr(), n, _stream(stream)))
+        check(self.lib.rdsp_engine_read_meter(self.h, n, level.data_ptr(), n, peak.data_ptr(), n, gate.data_ptr(), n, stream_ptr(stream)))
         return level, peak, gate
 
     def active(self, stream=None):
@@ -178,9 +165,9 @@ class Engine:
         dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
         lst = torch.empty(self.n_channels, dtype=torch.int32, device=dev)
         cnt = torch.empty(1, dtype=torch.int32, device=dev)
-        check(self.lib.rdsp_engine_active(self.h, lst.data_ptr(), cnt.data_ptr(), _stream(stream)))
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize()
+        check(self.lib.rdsp_engine_active(self.h, lst.data_ptr(), cnt.data_ptr(), stream_ptr(stream)))
+        if stream is not None:   # the count is read on the host: wait for the caller's stream, whichever form it came in
+            (stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(stream)).synchronize()
         n = int(cnt.item())
         return lst[:n], n
 
@@ -197,7 +184,7 @@ class Engine:
         dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
         n = int(n_blocks) * 128
         out = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
-        check(self.lib.rdsp_engine_read_demod(self.h, int(n_blocks), out.data_ptr(), n, _stream(stream)))
+        check(self.lib.rdsp_engine_read_demod(self.h, int(n_blocks), out.data_ptr(), n, stream_ptr(stream)))
         return out
 
     def set_groups(self, first_channels):
@@ -287,21 +274,13 @@ for _n in ("enableAGC", "setAGCmode", "enableALSfilter", "disableALSfilter", "se
     setattr(Engine, _n, _setter(_n))
 
 
-class PreProcessor:
+class PreProcessor(Handle):
     """`AudioSDRpreProcessor preProcessor;` (INO:53): rdsp_preproc_* of include/rdsp.h"""
+    _destroy = "rdsp_preproc_destroy"
 
     def __init__(self, n_channels, device=0):
-        self.lib = load()
-        h = C.c_void_p()
-        check(self.lib.rdsp_preproc_create(n_channels, device, C.byref(h)))
-        self.h, self.n_channels = h, n_channels
-
-    def close(self):
-        if self.h:
-            self.lib.rdsp_preproc_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create("rdsp_preproc_create", n_channels, device)
+        self.n_channels = n_channels
 
     def startAutoI2SerrorDetection(self):
         check(self.lib.rdsp_preproc_startAutoI2SerrorDetection(self.h))
@@ -319,7 +298,7 @@ class PreProcessor:
         assert nch == self.n_channels and two == 2 and n % 128 == 0 and d_iq.dtype == torch.int16 and d_iq.is_contiguous()
         if out is None:
             out = torch.empty_like(d_iq)
-        check(self.lib.rdsp_preproc_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, _stream(stream)))
+        check(self.lib.rdsp_preproc_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, stream_ptr(stream)))
         return out
 
     def state(self):

@@ -10,24 +10,17 @@ from . import _lib
 BLOCK = 128
 
 
-class Graph:
+class Graph(_lib.Handle):
+    _destroy = "rdsp_graph_destroy"
+
     def __init__(self, n_channels=1):
         self.lib = _lib.load()
         self.n_channels = n_channels
-        self.h = C.c_void_p(self.lib.rdsp_graph_create(n_channels))
-        assert self.h
         self._keep = []  # callbacks / chains must outlive the graph
-
-    def close(self):
-        if self.h:
-            self.lib.rdsp_graph_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        h = self.lib.rdsp_graph_create(n_channels)
+        if not h:
+            raise _lib.RdspError(-1, f"rdsp_graph_create({n_channels}): refused")
+        self.h = C.c_void_p(h)
 
     def AudioMemory(self, n):
         _lib.check(self.lib.rdsp_memory(self.h, n))
@@ -57,53 +50,6 @@ class Graph:
     def play_queue(self):
         return PlayQueue(self, C.c_void_p(self.lib.rdsp_play_queue_create(self.h)))
 
-    def sdr_node(self, chain):
-        h = self.lib.rdsp_sdr_node_create(self.h, chain.h)
-        if not h:
-            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
-        self._keep.append(chain)
-        return Node(self, C.c_void_p(h))
-
-    def engine_node(self, engine):
-        """`AudioSDR SDR;` as the reference's engine computes it (INO:54, wired INO:81-86): radiodsp_sdr_rx_amd.engine.Engine"""
-        h = self.lib.rdsp_engine_node_create(self.h, engine.h)
-        if not h:
-            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
-        self._keep.append(engine)
-        return EngineNode(self, C.c_void_p(h))
-
-    def preproc_node(self, pre):
-        """`AudioSDRpreProcessor preProcessor;` (INO:53, wired INO:71-72): radiodsp_sdr_rx_amd.engine.PreProcessor"""
-        h = self.lib.rdsp_preproc_node_create(self.h, pre.h)
-        if not h:
-            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
-        self._keep.append(pre)
-        return EngineNode(self, C.c_void_p(h))
-
-    def spectrum_node(self, analyser):
-        """AudioAnalyzeFFT256IQ as a node (INO:57,73-74): inputs I, Q; available()/output like FFTIQ.h"""
-        h = self.lib.rdsp_spectrum_node_create(self.h, analyser.h)
-        if not h:
-            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
-        self._keep.append(analyser)
-        return SpectrumNode(self, C.c_void_p(h))
-
-    def biquad_node(self, biquad):
-        """AudioFilterBiquad as a node (INO:58-59,75-78): one input, one output"""
-        h = self.lib.rdsp_biquad_node_create(self.h, biquad.h)
-        if not h:
-            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
-        self._keep.append(biquad)
-        return BiquadNode(self, C.c_void_p(h))
-
-    def fft1024_node(self, analyser):
-        """AudioAnalyzeFFT1024 as a node (INO:57,87): one input; available()/output like the library"""
-        h = self.lib.rdsp_fft1024_node_create(self.h, analyser.h)
-        if not h:
-            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
-        self._keep.append(analyser)
-        return Fft1024Node(self, C.c_void_p(h))
-
     def AudioConnection(self, src, src_port, dst, dst_port):
         _lib.check(self.lib.rdsp_connect(src.h, src_port, dst.h, dst_port))
 
@@ -115,6 +61,18 @@ class Graph:
 
     def AudioInterrupts(self):
         self.lib.rdsp_interrupts(self.h)
+
+
+def _node_creator(kind, cls, doc):
+    """Graph.<kind>_node(obj): the node of a device object, which the graph keeps alive"""
+    def create(self, obj):
+        h = getattr(self.lib, f"rdsp_{kind}_node_create")(self.h, obj.h)
+        if not h:
+            raise _lib.RdspError(-1, self.lib.rdsp_last_error().decode())
+        self._keep.append(obj)
+        return cls(self, C.c_void_p(h))
+    create.__name__, create.__doc__ = f"{kind}_node", doc
+    return create
 
 
 class Block:
@@ -152,52 +110,46 @@ class Node:
         if block is not None:
             self.g.lib.rdsp_release(block.h)
 
+    _kind = "sdr"   # the node's own rdsp_<kind>_node_* symbols; the status word is one for every device node
+
     def status(self):
-        return self.g.lib.rdsp_sdr_node_status(self.h)
+        return getattr(self.g.lib, f"rdsp_{self._kind}_node_status")(self.h)
 
 
 class EngineNode(Node):
-    def status(self):
-        return self.g.lib.rdsp_engine_node_status(self.h)
-
-
-class SpectrumNode(Node):
-    def available(self):  # FFTIQ.h:62-68
-        return bool(self.g.lib.rdsp_spectrum_node_available(self.h))
-
-    def output(self):     # FFTIQ.h:99, uint16 [n_channels, 256]
-        p = self.g.lib.rdsp_spectrum_node_output(self.h)
-        return np.ctypeslib.as_array(p, (self.g.n_channels, 256)).copy()
-
-    def read(self, channel, binFirst, binLast=None):  # FFTIQ.h:70-73 and :75-86 (binLast itself is not added)
-        if binLast is None:
-            return float(self.g.lib.rdsp_spectrum_node_read(self.h, int(channel), int(binFirst)))
-        return float(self.g.lib.rdsp_spectrum_node_read_range(self.h, int(channel), int(binFirst), int(binLast)))
-
-    def status(self):
-        return self.g.lib.rdsp_spectrum_node_status(self.h)
+    _kind = "engine"
 
 
 class BiquadNode(Node):
-    def status(self):
-        return self.g.lib.rdsp_biquad_node_status(self.h)
+    _kind = "biquad"
 
 
-class Fft1024Node(Node):
-    def available(self):
-        return bool(self.g.lib.rdsp_fft1024_node_available(self.h))
+class _AnalyserNode(Node):
+    """an analyser as a node: available() / output / read like FFTIQ.h:62-86,99; a subclass gives the kind and the bins"""
+    _bins = None
 
-    def output(self):     # uint16 [n_channels, 512]
-        p = self.g.lib.rdsp_fft1024_node_output(self.h)
-        return np.ctypeslib.as_array(p, (self.g.n_channels, 512)).copy()
+    def _fn(self, name):
+        return getattr(self.g.lib, f"rdsp_{self._kind}_node_{name}")
 
-    def read(self, channel, binFirst, binLast=None):  # AudioAnalyzeFFT1024::read (the range form includes binLast)
+    def available(self):  # FFTIQ.h:62-68
+        return bool(self._fn("available")(self.h))
+
+    def output(self):     # FFTIQ.h:99, uint16 [n_channels, bins]
+        return np.ctypeslib.as_array(self._fn("output")(self.h), (self.g.n_channels, self._bins)).copy()
+
+    def read(self, channel, binFirst, binLast=None):
+        """FFTIQ.h:70-73 and :75-86 (binLast itself is not added); AudioAnalyzeFFT1024::read (the range form includes binLast)"""
         if binLast is None:
-            return float(self.g.lib.rdsp_fft1024_node_read(self.h, int(channel), int(binFirst)))
-        return float(self.g.lib.rdsp_fft1024_node_read_range(self.h, int(channel), int(binFirst), int(binLast)))
+            return float(self._fn("read")(self.h, int(channel), int(binFirst)))
+        return float(self._fn("read_range")(self.h, int(channel), int(binFirst), int(binLast)))
 
-    def status(self):
-        return self.g.lib.rdsp_fft1024_node_status(self.h)
+
+class SpectrumNode(_AnalyserNode):
+    _kind, _bins = "spectrum", 256
+
+
+class Fft1024Node(_AnalyserNode):
+    _kind, _bins = "fft1024", 512
 
 
 class InputNode(Node):
@@ -233,3 +185,13 @@ class PlayQueue(Node):
 
     def playBuffer(self):
         return self.g.lib.rdsp_play_queue_playBuffer(self.h)
+
+
+for _kind, _cls, _doc in (
+        ("sdr", Node, "the chain (radiodsp_sdr_rx_amd.chain.Chain): inputs I, Q; outputs L, R"),
+        ("engine", EngineNode, "`AudioSDR SDR;` as the reference's engine computes it (INO:54, wired INO:81-86): engine.Engine"),
+        ("preproc", EngineNode, "`AudioSDRpreProcessor preProcessor;` (INO:53, wired INO:71-72): engine.PreProcessor"),
+        ("spectrum", SpectrumNode, "AudioAnalyzeFFT256IQ as a node (INO:57,73-74): inputs I, Q; available()/output like FFTIQ.h"),
+        ("biquad", BiquadNode, "AudioFilterBiquad as a node (INO:58-59,75-78): one input, one output"),
+        ("fft1024", Fft1024Node, "AudioAnalyzeFFT1024 as a node (INO:57,87): one input; available()/output like the library")):
+    setattr(Graph, f"{_kind}_node", _node_creator(_kind, _cls, _doc))

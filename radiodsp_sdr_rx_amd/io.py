@@ -15,19 +15,17 @@ IO_AUTO, IO_RAW, IO_WAV = 0, 1, 2
 _SRC_DTYPE = (np.int16, np.uint8, np.int8, np.float32)
 
 
-class IqReader:
+class IqReader(_lib.Handle):
     """One receiver channel's recording: RAW int16 I,Q pairs or 16-bit stereo WAV (I left, Q right).  With sample_format
     (SRC_*, or -1 for what a WAV header says) also RAW uint8 / int8 / float32 pairs and 8-bit or float32 WAV."""
 
+    _destroy = "rdsp_iq_reader_close"
+
     def __init__(self, path, fmt=IO_AUTO, sample_format=None):
-        self.h = None
-        self.lib = _lib.load()
-        h = C.c_void_p()
         if sample_format is None:
-            _lib.check(self.lib.rdsp_iq_reader_open(str(path).encode(), int(fmt), C.byref(h)))
+            self._create("rdsp_iq_reader_open", str(path).encode(), int(fmt))
         else:
-            _lib.check(self.lib.rdsp_iq_reader_open_samples(str(path).encode(), int(fmt), int(sample_format), C.byref(h)))
-        self.h = h
+            self._create("rdsp_iq_reader_open_samples", str(path).encode(), int(fmt), int(sample_format))
 
     @property
     def sample_rate(self): return float(self.lib.rdsp_iq_reader_sample_rate(self.h))
@@ -50,23 +48,13 @@ class IqReader:
         got = self.lib.rdsp_iq_reader_read_samples(self.h, buf.ctypes.data_as(C.c_void_p), n_pairs)
         return buf[:got]
 
-    def close(self):
-        if self.h:
-            self.lib.rdsp_iq_reader_close(self.h)
-            self.h = None
 
-    __del__ = close
-
-
-class AudioWriter:
-    """int16 L,R pairs to a RAW or WAV file at the decimated rate."""
+class AudioWriter(_lib.Handle):
+    """int16 L,R pairs to a RAW or WAV file at the decimated rate.  close() raises what rdsp_audio_writer_close reports."""
+    _destroy = "rdsp_audio_writer_close"
 
     def __init__(self, path, fmt=IO_WAV, sample_rate=24000.0):
-        self.h = None
-        self.lib = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self.lib.rdsp_audio_writer_open(str(path).encode(), int(fmt), float(sample_rate), C.byref(h)))
-        self.h = h
+        self._create("rdsp_audio_writer_open", str(path).encode(), int(fmt), float(sample_rate))
 
     def write(self, lr):
         lr = np.ascontiguousarray(lr, dtype=np.int16)
@@ -74,17 +62,6 @@ class AudioWriter:
 
     @property
     def frames(self): return int(self.lib.rdsp_audio_writer_frames(self.h))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            _lib.check(self.lib.rdsp_audio_writer_close(h))
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _stats(st):

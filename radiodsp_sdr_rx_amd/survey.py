@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, load
+from ._lib import Handle, check, load, stream_ptr
 from .engine import SRC_F32, SRC_S8, SRC_S16, SRC_U8, _src_dtype  # noqa: F401
 
 _F32P, _F64P = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -43,25 +43,15 @@ def find_stations(row, P, Q, min_db_over_floor=20.0, min_spacing_hz=1000.0, max_
     return hz[:n].copy(), pw[:n].copy()
 
 
-class Survey:
+class Survey(Handle):
+    _destroy = "rdsp_survey_destroy"
+
     def __init__(self, n_sources, fft_n=4096, navg=8, fmt=SRC_S16, max_pairs_per_call=1 << 22, device=0):
-        self.lib = load()
-        self.h = None
-        h = C.c_void_p()
-        check(self.lib.rdsp_survey_create(int(n_sources), int(device), int(fft_n), int(navg), int(fmt), int(max_pairs_per_call), C.byref(h)))
-        self.h, self.n_sources, self.fft_n, self.navg, self.fmt = h, int(n_sources), int(fft_n), int(navg), int(fmt)
-
-    def close(self):
-        if self.h:
-            self.lib.rdsp_survey_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create("rdsp_survey_create", int(n_sources), int(device), int(fft_n), int(navg), int(fmt), int(max_pairs_per_call))
+        self.n_sources, self.fft_n, self.navg, self.fmt = int(n_sources), int(fft_n), int(navg), int(fmt)
 
     def reset(self, stream=None):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(self.lib.rdsp_survey_reset(self.h, C.c_void_p(s)))
+        check(self.lib.rdsp_survey_reset(self.h, stream_ptr(stream)))
 
     def rows_for(self, pairs):
         """rows per source the NEXT update of `pairs` pairs completes"""
@@ -86,11 +76,10 @@ class Survey:
             out = torch.empty((nsrc, rows, self.fft_n), dtype=torch.float32, device=d_src.device)
         assert out.dtype == torch.float32 and out.shape[0] == nsrc and out.shape[1] >= rows and out.shape[2] == self.fft_n
         assert out.stride(2) == 1 and (out.shape[1] == 0 or out.stride(1) == self.fft_n)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         stride = d_src.stride(0) // 2 if nsrc > 1 else max(n, pairs)
         rows_stride = out.stride(0) if nsrc > 1 and out.shape[1] > 0 else out.shape[1] * self.fft_n
         got = C.c_int()
         check(self.lib.rdsp_survey_update(self.h, C.c_void_p(d_src.data_ptr()), stride, pairs, C.c_void_p(out.data_ptr()), rows_stride,
-                                          C.byref(got), C.c_void_p(s)))
+                                          C.byref(got), stream_ptr(stream)))
         assert got.value == rows
         return out[:, :rows]

@@ -12,90 +12,7 @@ import numpy as np
 import pytest
 
 from cases import K1, TOL
-
-F32P, I16P = C.POINTER(C.c_float), C.POINTER(C.c_int16)
-
-
-def _bind(lib):
-    lib.orc_design_butter_bp8.argtypes = [C.c_double, C.c_double, C.c_double, F32P]
-    lib.orc_biquad_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, F32P]
-    lib.orc_cfft_radix4_q15_n.argtypes = [I16P, C.c_int]
-    lib.orc_fft1024_create.restype = C.c_void_p
-    lib.orc_fft1024_create.argtypes = [C.c_int]
-    lib.orc_fft1024_destroy.argtypes = [C.c_void_p]
-    lib.orc_fft1024_update.argtypes = [C.c_void_p, I16P]
-    lib.orc_fft1024_update.restype = C.c_int
-    lib.orc_fft1024_output.argtypes = [C.c_void_p]
-    lib.orc_fft1024_output.restype = C.POINTER(C.c_uint16)
-    lib.orc_set_audio_iir.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
-    lib.orc_chain_iir_coeffs.argtypes = [C.c_void_p]
-    lib.orc_chain_iir_coeffs.restype = F32P
-    return lib
-
-
-class OrcBiquad(C.Structure):
-    _fields_ = [("n_stages", C.c_int), ("coef", C.c_float * 20), ("state", C.c_float * 16)]
-
-
-def oracle_biquad(lib, coef20, x):
-    """float DF1 cascade of the oracle over a float array (fresh state)"""
-    b = OrcBiquad()
-    lib.orc_biquad_init.argtypes = [C.POINTER(OrcBiquad), C.c_int, F32P]
-    lib.orc_biquad_run.argtypes = [C.POINTER(OrcBiquad), F32P, C.c_int]
-    c = np.ascontiguousarray(coef20, np.float32)
-    lib.orc_biquad_init(C.byref(b), 4, c.ctypes.data_as(F32P))
-    y = np.ascontiguousarray(x, np.float32).copy()
-    lib.orc_biquad_run(C.byref(b), y.ctypes.data_as(F32P), len(y))
-    return y
-
-
-class OrcTeensyBiquad(C.Structure):
-    _fields_ = [("chained", C.c_int * 4), ("coef", (C.c_int32 * 5) * 4), ("x1", C.c_int16 * 4), ("x2", C.c_int16 * 4),
-                ("y1", C.c_int16 * 4), ("y2", C.c_int16 * 4), ("sum", C.c_int32 * 4)]
-
-
-class TeensyBiquadOracle:
-    """the oracle's restatement of the Teensy library's AudioFilterBiquad (fixed point), one channel"""
-    KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3}
-
-    def __init__(self, lib, fs=44100.0):
-        self.lib, self.fs, self.o = lib, fs, OrcTeensyBiquad()
-        I32P = C.POINTER(C.c_int32)
-        lib.orc_teensy_biquad_init.argtypes = [C.POINTER(OrcTeensyBiquad)]
-        lib.orc_teensy_biquad_setCoefficients_int.argtypes = [C.POINTER(OrcTeensyBiquad), C.c_int, I32P]
-        lib.orc_teensy_biquad_setCoefficients.argtypes = [C.POINTER(OrcTeensyBiquad), C.c_int, C.POINTER(C.c_double)]
-        lib.orc_teensy_biquad_design.argtypes = [C.c_int, C.c_float, C.c_float, C.c_float, I32P]
-        lib.orc_teensy_biquad_update.argtypes = [C.POINTER(OrcTeensyBiquad), I16P, C.c_int]
-        lib.orc_teensy_biquad_init(C.byref(self.o))
-
-    def set(self, stage, kind, f, q):
-        c5 = np.zeros(5, np.int32)
-        self.lib.orc_teensy_biquad_design(self.KIND[kind], f, q, self.fs, c5.ctypes.data_as(C.POINTER(C.c_int32)))
-        self.lib.orc_teensy_biquad_setCoefficients_int(C.byref(self.o), stage, c5.ctypes.data_as(C.POINTER(C.c_int32)))
-        return c5
-
-    def setCoefficients(self, stage, c5):
-        c = np.ascontiguousarray(c5, np.float64)
-        self.lib.orc_teensy_biquad_setCoefficients(C.byref(self.o), stage, c.ctypes.data_as(C.POINTER(C.c_double)))
-
-    def update(self, x):
-        """x int16 [n] (n a multiple of 128): block by block like the audio interrupt; returns the filtered int16"""
-        y = np.ascontiguousarray(x, np.int16).copy()
-        for b in range(len(y) // 128):
-            blk = y[b * 128:(b + 1) * 128]
-            self.lib.orc_teensy_biquad_update(C.byref(self.o), blk.ctypes.data_as(I16P), 128)
-        return y
-
-
-def oracle_fft1024(lib, x, window):
-    s = lib.orc_fft1024_create(window)
-    outs = []
-    for b in range(len(x) // 128):
-        blk = np.ascontiguousarray(x[b * 128:(b + 1) * 128], np.int16)
-        if lib.orc_fft1024_update(s, blk.ctypes.data_as(I16P)):
-            outs.append(np.ctypeslib.as_array(lib.orc_fft1024_output(s), (512,)).copy())
-    lib.orc_fft1024_destroy(s)
-    return np.stack(outs) if outs else np.zeros((0, 512), np.uint16)
+from nodes_oracle import F32P, I16P, TeensyBiquadOracle, _bind, _olib, oracle_biquad, oracle_fft1024, oracle_spectra
 
 
 # ---- CPU: designs and oracle known answers ------------------------------------------------------
@@ -180,7 +97,6 @@ def test_oracle_fft1024_known_answers(oracle):
     buf = (rng.standard_normal(512) * 4000).astype(np.int16)
     a, b = buf.copy(), buf.copy()
     lib.orc_cfft_radix4_q15_n(a.ctypes.data_as(I16P), 256)
-    lib.orc_cfft_radix4_q15_256.argtypes = [I16P]
     lib.orc_cfft_radix4_q15_256(b.ctypes.data_as(I16P))
     assert np.array_equal(a, b)
 
@@ -224,7 +140,6 @@ def test_gpu_fft1024_with_the_firmware_window_by_pointer(rdsp, oracle):
     from radiodsp_sdr_rx_amd.chain import synth_iq
     from radiodsp_sdr_rx_amd.filters import AnalyzeFFT1024
     lib = _bind(oracle.load())
-    lib.orc_fft1024_windowFunction_table.argtypes = [C.c_void_p, I16P]
     fw = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "firmware_tables.npz"))
     nch, nblk = 3, 28
     audio = synth_iq(nch, nblk * 128)[..., 1].copy()
@@ -416,8 +331,7 @@ def test_iqinput_biquad_fft_wiring_of_the_sketch(rdsp, oracle):
     from radiodsp_sdr_rx_amd.filters import FilterBiquad
     from radiodsp_sdr_rx_amd.graph import Graph
     from radiodsp_sdr_rx_amd.spectrum import AnalyzeFFT256IQ
-    from test_spectrum import _olib, oracle_spectra
-    lib = _bind(_olib(oracle))
+    lib = _olib(oracle)
     nch, nblk = 2, 40
     iq = synth_iq(nch, nblk * 128)
     g = Graph(nch)
@@ -527,7 +441,6 @@ def test_engine_iir_sets_of_the_firmware_image_run_through_the_product(rdsp, ora
     from radiodsp_sdr_rx_amd.chain import Chain, synth_iq
     from radiodsp_sdr_rx_amd.filters import FilterBiquad
     lib = _bind(oracle.load())
-    lib.orc_float_to_q15.argtypes = [F32P, I16P, C.c_uint32]
     fw = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "firmware_tables.npz"))
     sets = fw["biquad_sets"]
     fs = 44100.0
@@ -661,12 +574,7 @@ def _nodes_fixture():
 
 def test_oracle_reproduces_the_node_fixture(oracle):
     """pins the integer analysers and the biquad cascade of the oracle against accidental change"""
-    from test_spectrum import _olib, oracle_spectra
-    lib = _bind(_olib(oracle))
-    lib.orc_biquad_set_stage.argtypes = [C.POINTER(OrcBiquad), C.c_int, F32P]
-    lib.orc_biquad_init.argtypes = [C.POINTER(OrcBiquad), C.c_int, F32P]
-    lib.orc_biquad_run.argtypes = [C.POINTER(OrcBiquad), F32P, C.c_int]
-    lib.orc_float_to_q15.argtypes = [F32P, I16P, C.c_uint32]
+    lib = _olib(oracle)
     g = _nodes_fixture()
     iq = g["iq"]
     for c in range(iq.shape[0]):
@@ -696,3 +604,62 @@ def test_gpu_nodes_match_the_fixture(rdsp):
     bq.setHighpass(0, 500, 0.5)
     bq.setNotch(1, 1000, 4.0)
     assert np.array_equal(bq.update(dev[..., 0]).cpu().numpy(), g["biquad"])
+
+
+# ---- the Python mirrors' common parts: the handle owner and the stream conversion (radiodsp_sdr_rx_amd/_lib.py) ----
+@pytest.mark.gpu
+def test_a_refused_constructor_leaves_nothing_behind(rdsp):
+    """every mirror class that takes a channel or source count: a count of 0 is refused with RdspError, and the finaliser
+    of the half-made object has nothing to do -- nothing reaches sys.unraisablehook"""
+    import gc
+    import sys
+    from radiodsp_sdr_rx_amd import RdspError
+    from radiodsp_sdr_rx_amd.chain import Chain
+    from radiodsp_sdr_rx_amd.engine import Engine, PreProcessor
+    from radiodsp_sdr_rx_amd.filters import AnalyzeFFT1024, FilterBiquad
+    from radiodsp_sdr_rx_amd.graph import Graph
+    from radiodsp_sdr_rx_amd.spectrum import AnalyzeFFT256IQ
+    from radiodsp_sdr_rx_amd.survey import Survey
+    seen, hook = [], sys.unraisablehook
+    sys.unraisablehook = seen.append
+    try:
+        for cls in (Engine, PreProcessor, Survey, FilterBiquad, AnalyzeFFT256IQ, AnalyzeFFT1024, Chain, Graph):
+            with pytest.raises(RdspError):
+                cls(0)
+        gc.collect()
+    finally:
+        sys.unraisablehook = hook
+    assert not seen, [str(u.exc_value) for u in seen]
+
+
+@pytest.mark.gpu
+def test_every_stream_argument_takes_the_three_forms(rdsp):
+    """stream=None (torch's current stream), the torch stream object and its raw handle are one stream to every mirror:
+    fresh objects per form, the results equal bit for bit"""
+    import torch
+    from radiodsp_sdr_rx_amd.chain import synth_iq
+    from radiodsp_sdr_rx_amd.engine import PreProcessor
+    from radiodsp_sdr_rx_amd.filters import AnalyzeFFT1024, FilterBiquad
+    from radiodsp_sdr_rx_amd.spectrum import AnalyzeFFT256IQ
+    from radiodsp_sdr_rx_amd.survey import Survey
+    nch = 2
+    iq = torch.from_numpy(synth_iq(nch, 1024)).cuda()   # 8 blocks, 1024 pairs
+
+    def highpass():
+        bq = FilterBiquad(nch)
+        bq.setHighpass(0, 500, 0.5)
+        return bq
+
+    cases = {
+        "fft256iq": (lambda: AnalyzeFFT256IQ(nch, naverage=1, window="none"), iq[:, :2 * 128].contiguous()),
+        "fft1024": (lambda: AnalyzeFFT1024(nch), iq[:, :, 0].contiguous()),          # the call that completes a frame
+        "biquad": (highpass, iq[:, :128, 0].contiguous()),
+        "preproc": (lambda: PreProcessor(nch), iq[:, :128].contiguous()),
+        "survey": (lambda: Survey(nch, fft_n=1024, navg=1), iq),
+    }
+    cur = torch.cuda.current_stream()
+    for name, (make, x) in cases.items():
+        got = [make().update(x, stream=s) for s in (None, cur, cur.cuda_stream)]
+        torch.cuda.synchronize()
+        assert got[0].numel() > 0, name
+        assert torch.equal(got[0], got[1]) and torch.equal(got[0], got[2]), name

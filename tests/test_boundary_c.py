@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from nodes_oracle import TeensyBiquadOracle, _olib, oracle_spectra
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
 CFG = dict(fft_l=256, demod="LSB", flo_hz=300.0, fhi_hz=4000.0, agc_mode="medium", input_gain=1.0, output_gain=0.5,
@@ -61,9 +63,7 @@ def test_panadapter_side_through_the_c_binding_matches_the_oracle(rdsp, oracle, 
     AudioWindowHanning256 handed over by pointer and averageTogether(30); every spectrum FFT.available() announces,
     FFT.read(80) and FFT.read(75, 85) come back through a file: bit-exact against the oracle's restatements."""
     from radiodsp_sdr_rx_amd.chain import synth_iq
-    from test_audio_nodes import TeensyBiquadOracle, _bind
-    from test_spectrum import _olib, oracle_spectra
-    lib = _bind(_olib(oracle))
+    lib = _olib(oracle)
     nblk = 128
     iq = synth_iq(1, nblk * 128)
     fin, fout, fspec = tmp_path / "iq.raw", tmp_path / "audio.raw", tmp_path / "spec.raw"

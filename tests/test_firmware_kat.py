@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from cases import CONV_LITERAL
+from nodes_oracle import OrcBiquad, TeensyBiquadOracle, _olib, oracle_fft1024, oracle_spectra
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 I16P, F32P, F64P, I32P = (C.POINTER(t) for t in (C.c_int16, C.c_float, C.c_double, C.c_int32))
@@ -106,10 +107,7 @@ def test_oracle_lms_noise_reduction_is_the_images_bit_for_bit(kat, oracle):
 
 def test_oracle_df1_cascade_is_the_images_bit_for_bit(kat, oracle):
     """arm_biquad_cascade_df1_f32 with the engine's own first coefficient set, two calls on one instance"""
-    from test_audio_nodes import OrcBiquad
-    lib = oracle.load()
-    lib.orc_biquad_init.argtypes = [C.POINTER(OrcBiquad), C.c_int, F32P]
-    lib.orc_biquad_run.argtypes = [C.POINTER(OrcBiquad), F32P, C.c_int]
+    lib = _olib(oracle)
     b = OrcBiquad()
     coef = kat["df1_coef"].copy()
     lib.orc_biquad_init(C.byref(b), 4, p(coef))
@@ -262,9 +260,7 @@ def test_oracle_analysers_are_the_images_update_bit_for_bit(kat, oracle):
     transform, |X|^2, averaging, sqrt_uint32_approx, output order and the tick on which the flag comes up -- with the
     sketch's settings (Hanning, averageTogether(30)), the constructor's (BlackmanNuttall, 8), no averaging, no window;
     one block of the input sits on the rails"""
-    from test_audio_nodes import _bind, oracle_fft1024
-    from test_spectrum import _olib, oracle_spectra
-    lib = _bind(_olib(oracle))
+    lib = _olib(oracle)
     for tag, win, navg in (("sketch", 1, 30), ("default", 3, 8), ("avg1", 1, 1), ("adv", 1, 2)):
         iq = kat["fft256iq_adv_iq"] if tag == "adv" else kat["fft256iq_iq"]     # adv: full-scale DC, Nyquist, a bin tone, noise
         want = kat[f"fft256iq_{tag}_out"]
@@ -282,9 +278,7 @@ def test_oracle_panadapter_branch_is_the_images_end_to_end(kat, oracle):
     """IQinput -> biquad1 / biquad2 (setHighpass(0, 500, 0.5)) -> FFT (Hanning, averageTogether(30)), INO:57-60,75-78,
     144-145,155-156, each update() run from the image and chained: 96 blocks, three spectra -- the oracle's fixed-point
     biquad feeding its analyser gives the same words"""
-    from test_audio_nodes import TeensyBiquadOracle, _bind
-    from test_spectrum import _olib, oracle_spectra
-    lib = _bind(_olib(oracle))
+    lib = _olib(oracle)
     iq = kat["panadapter_iq"]
     filt = np.zeros_like(iq)
     for side in (0, 1):
@@ -331,7 +325,6 @@ def test_oracle_teensy_biquad_is_the_images_update_bit_for_bit(kat, oracle, rdsp
     set behind one that never was (update() stops in front of the gap), a fresh object (passes nothing); two blocks
     of full-scale noise drive the saturating path.  The setters' integer coefficients (computed by the published
     formula for the fixture) are what the oracle's and the product's design routines return."""
-    from test_audio_nodes import TeensyBiquadOracle
     lib = oracle.load()
     x = kat["tbq_in"]
     for tag in TBQ:

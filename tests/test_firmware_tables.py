@@ -8,9 +8,9 @@ import os
 import numpy as np
 import pytest
 
+from nodes_oracle import I16P, U16P, TeensyBiquadOracle, _olib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-I16P = C.POINTER(C.c_int16)
-U16P = C.POINTER(C.c_uint16)
 
 
 @pytest.fixture(scope="module")
@@ -24,19 +24,6 @@ def plib(rdsp):
     lib.rdsp_q15_twiddles.argtypes = [C.c_int, C.POINTER(C.c_uint32)]
     lib.rdsp_q15_twiddles.restype = None
     lib.rdsp_sqrt_guess_table.restype = U16P
-    return lib
-
-
-def _olib(oracle):
-    lib = oracle.load()
-    lib.orc_window_q15_n.argtypes = [C.c_int, C.c_int, I16P]
-    lib.orc_twiddle_q15_4096.argtypes = [I16P]
-    lib.orc_sqrt_guess_table.restype = U16P
-    lib.orc_sqrt_uint32_approx.restype = C.c_uint32
-    lib.orc_sqrt_uint32_approx.argtypes = [C.c_uint32]
-    lib.orc_sqrt_uint32.restype = C.c_uint32
-    lib.orc_sqrt_uint32.argtypes = [C.c_uint32]
-    lib.orc_cfft_radix4_q15_n.argtypes = [I16P, C.c_int]
     return lib
 
 
@@ -159,14 +146,7 @@ def test_read_range_keeps_the_loop_as_written(plib, oracle):
     assert plib.rdsp_fft1024_read_range(p2, 10, 14) == float(o2[10:15].sum()) * k
     assert plib.rdsp_fft1024_read(p2, 512) == 0.0
     # oracle's restatement of the same lines
-    olib = oracle.load()
-    olib.orc_fft256iq_create.restype = C.c_void_p
-    olib.orc_fft256iq_create.argtypes = [C.c_int, C.c_int]
-    olib.orc_fft256iq_read_range.restype = C.c_float
-    olib.orc_fft256iq_read_range.argtypes = [C.c_void_p, C.c_uint, C.c_uint]
-    olib.orc_fft256iq_output.restype = U16P
-    olib.orc_fft256iq_output.argtypes = [C.c_void_p]
-    olib.orc_fft256iq_destroy.argtypes = [C.c_void_p]
+    olib = _olib(oracle)
     s = olib.orc_fft256iq_create(1, 0)
     np.ctypeslib.as_array(olib.orc_fft256iq_output(s), (256,))[:] = out
     for a, b in ((10, 14), (14, 10), (7, 7), (250, 400), (300, 400), (0, 255)):
@@ -429,7 +409,6 @@ def test_audio_filter_biquad_of_the_image_is_the_fixed_point_routine(fw, oracle)
 
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from test_audio_nodes import TeensyBiquadOracle
     lib = oracle.load()
     rng = np.random.default_rng(11)
     for trial, (kind, f, q) in enumerate((("highpass", 500.0, 0.5), ("lowpass", 3000.0, 0.707), ("notch", 1000.0, 8.0), ("bandpass", 700.0, 30.0))):

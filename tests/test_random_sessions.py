@@ -424,7 +424,7 @@ def test_random_nr_and_notch_switching_is_truth_anchored(rdsp, oracle, seed):
     import np_model
     from oracle_lib import AGC, ALS
     from radiodsp_sdr_rx_amd.chain import Chain, synth_iq
-    from test_gpu_parity import assert_truth_anchored
+    from parity_util import assert_truth_anchored
     rng = np.random.default_rng(seed)
     nch = 5
     base = dict(K3, fft_l=int(rng.choice([256, 512])))

@@ -6,48 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-I16P = C.POINTER(C.c_int16)
-
-
-def _olib(oracle):
-    lib = oracle.load()
-    lib.orc_fft256iq_create.restype = C.c_void_p
-    lib.orc_fft256iq_create.argtypes = [C.c_int, C.c_int]
-    lib.orc_fft256iq_destroy.argtypes = [C.c_void_p]
-    lib.orc_fft256iq_update.argtypes = [C.c_void_p, I16P, I16P]
-    lib.orc_fft256iq_update.restype = C.c_int
-    lib.orc_fft256iq_output.restype = C.POINTER(C.c_uint16)
-    lib.orc_fft256iq_output.argtypes = [C.c_void_p]
-    lib.orc_fft256iq_averageTogether.argtypes = [C.c_void_p, C.c_int]
-    lib.orc_fft256iq_windowFunction.argtypes = [C.c_void_p, C.c_int]
-    lib.orc_fft256iq_windowFunction_table.argtypes = [C.c_void_p, I16P]
-    lib.orc_fft256iq_read.restype = C.c_float
-    lib.orc_fft256iq_read.argtypes = [C.c_void_p, C.c_uint]
-    lib.orc_fft256iq_read_range.restype = C.c_float
-    lib.orc_fft256iq_read_range.argtypes = [C.c_void_p, C.c_uint, C.c_uint]
-    lib.orc_cfft_radix4_q15_256.argtypes = [I16P]
-    lib.orc_window_q15.argtypes = [C.c_int, I16P]
-    lib.orc_sqrt_uint32.argtypes = [C.c_uint32]
-    lib.orc_sqrt_uint32.restype = C.c_uint32
-    return lib
-
-
-def oracle_spectra(lib, iq, naverage, window):
-    """iq int16 [n, 2] (n multiple of 128) -> list of uint16[256] spectra, in order.  window: an id, or an int16
-    table handed over the way the reference does (windowFunction(const int16_t *), FFTIQ.h:93)."""
-    if isinstance(window, np.ndarray):
-        s = lib.orc_fft256iq_create(naverage, 0)
-        lib.orc_fft256iq_windowFunction_table(s, np.ascontiguousarray(window, np.int16).ctypes.data_as(I16P))
-    else:
-        s = lib.orc_fft256iq_create(naverage, window)
-    outs = []
-    i = np.ascontiguousarray(iq[:, 0])
-    q = np.ascontiguousarray(iq[:, 1])
-    for b in range(len(iq) // 128):
-        if lib.orc_fft256iq_update(s, i[b * 128:].ctypes.data_as(I16P), q[b * 128:].ctypes.data_as(I16P)):
-            outs.append(np.ctypeslib.as_array(lib.orc_fft256iq_output(s), (256,)).copy())
-    lib.orc_fft256iq_destroy(s)
-    return outs
+from nodes_oracle import I16P, _olib, oracle_spectra
 
 
 def test_fixed_point_fft_tracks_float_dft(oracle):
@@ -69,7 +28,6 @@ def test_fixed_point_fft_tracks_float_dft(oracle):
     assert np.array_equal(buf, _cmsis_radix4_q15_model(x.reshape(-1), 256))
     rails = rng.choice(np.array([-32768, 32767], np.int16), size=2048)
     b2 = rails.copy()
-    lib.orc_cfft_radix4_q15_n.argtypes = [I16P, C.c_int]
     lib.orc_cfft_radix4_q15_n(b2.ctypes.data_as(I16P), 1024)
     assert np.array_equal(b2, _cmsis_radix4_q15_model(rails, 1024))                # saturating paths included
 
