@@ -745,7 +745,7 @@ void rdsp_synth_iq(int16_t *dst, int ch0, int n_ch, uint64_t t0, int n_samples,
  * The engine (Derek Rowell's AudioSDR library) is not in the reference tree; its compiled code is, in
  * pre_compiled/RadioDSP_SDR_RX.ino.hex.  rdsp_engine_t follows that code (AudioSDR::update, ITCM 0xe730, and the setters
  * the sketch calls) for n_channels receivers: on the same int16 IQ blocks it returns the int16 audio the image's update()
- * returns (tests/test_engine_kat.py; csrc/rdsp_engine.hip describes the signal path and the kernels; the host object is csrc/rdsp_engine_host.h and the five host files it names).  Native rate only:
+ * returns (tests/test_engine_kat.py; csrc/rdsp_engine.hip describes the signal path and names the three stage files of the kernels; the host object is csrc/rdsp_engine_host.h and the five host files it names).  Native rate only:
  * 44.1 kHz, one 128-sample block in, one out, no decimation.  The rdsp_sdr_* setters above belong to rdsp_chain_t, this
  * build's own many-channel receiver with a decimator in front; these are the reference's.  Numbers are the engine's
  * (`mode`: 0 LSBmode, 1 USBmode, 2 CW_LSBmode, 3 CW_USBmode, 4 AMmode, 5 SAMmode, as the compiled tuningMode() passes

@@ -3,7 +3,7 @@
  * meter as an owner, the walk over groups.  rdsp_engine_host.hip holds the sketch's settings and setters and creates, resets
  * and runs the object; rdsp_engine_groups.hip the receiver groups; rdsp_engine_meter_host.hip the signal meter's owner and
  * entry points; rdsp_engine_sources_host.hip the entry points of the shared IQ sources; rdsp_engine_state.hip the state
- * blob.  Host logic only: the kernels are rdsp_engine.hip's and rdsp_engine_meter.hip's, the front end is
+ * blob.  Host logic only: the kernels are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip) and rdsp_engine_meter.hip's, the front end is
  * rdsp_engine_sources.h's.  All five are compiled with the kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H

@@ -1,7 +1,7 @@
 /*
  * rdsp_engine_host.hip -- the host object behind rdsp_engine_t (include/rdsp.h): the sketch's settings and setters, and what
  * creates, destroys, resets and runs the object (rdsp_engine_host.h has the object and names the other host files).  The
- * kernels and the signal path are rdsp_engine.hip's; a call hands rdsp_engine_launch (rdsp_engine_int.h) one group's
+ * signal path is rdsp_engine.hip's, the kernels are its stage files' (rdsp_engine_front / _hilbert / _tail.hip); a call hands rdsp_engine_launch (rdsp_engine_int.h) one group's
  * arguments.  Every device buffer has one owner (DevBuf): deleting the object frees them.
  * Compiled with the kernels' flags (-ffp-contract=off): the constants and tables computed here are held bit for bit. */
 #include "rdsp_engine_host.h"

@@ -1,5 +1,5 @@
 /*
- * rdsp_engine_int.h -- what rdsp_engine_t's kernels (rdsp_engine.hip) and its host object (rdsp_engine_host.h) share: the
+ * rdsp_engine_int.h -- what rdsp_engine_t's kernels (rdsp_engine.hip and the stage files it names) and its host object (rdsp_engine_host.h) share: the
  * kernels' arguments, a channel's state words, the launch of one group's kernels; and what the engine's and the
  * pre-processor's (rdsp_preproc.hip) host sides share: the owner of a device allocation (rdsp_dev.h), the HIP error return. */
 #ifndef RDSP_ENGINE_INT_H
@@ -43,10 +43,16 @@ static inline int engine_fail(const char *what, hipError_t err) {
   rdsp_set_error("%s: %s", what, hipGetErrorString(err));
   return RDSP_ERR_HIP;
 }
+
+/* the stages' launch entries, each beside its kernels: rdsp_engine_front.hip (the kernel by blanker and mode),
+ * rdsp_engine_hilbert.hip (SSB / CW only), rdsp_engine_tail.hip (the kernel by ALS) */
+void engine_launch_front(const EngParams &p, bool blanker, hipStream_t s);
+void engine_launch_hilbert(const EngParams &p, hipStream_t s);
+void engine_launch_tail(const EngParams &p, bool als, hipStream_t s);
 }  // namespace rdsp_eng
 
-/* one group's launches of a call, stream-ordered: the front kernel (by blanker and mode), the Hilbert kernel (SSB / CW), the
- * tail kernel (by ALS); p holds the group's channel range and settings */
+/* one group's launches of a call, stream-ordered: the three stages above (rdsp_engine.hip); p holds the group's channel
+ * range and settings */
 hipError_t rdsp_engine_launch(const rdsp_eng::EngParams &p, bool blanker, bool als, hipStream_t s);
 
 #endif

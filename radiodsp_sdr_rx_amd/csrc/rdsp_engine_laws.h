@@ -1,6 +1,6 @@
 /*
  * rdsp_engine_laws.h -- the engine's hang AGC (0xdb58) and ALS line enhancer (0xda24) as the image computes them: the one
- * copy of their stage bodies, for rdsp_engine_t's two tail kernels (rdsp_engine.hip) and the chain's engine-law tail
+ * copy of their stage bodies, for rdsp_engine_t's two tail kernels (rdsp_engine_tail.hip) and the chain's engine-law tail
  * stage (rdsp_tail_engine.hip).  The kernels keep their own lanes, LDS tiles, block loops, barriers and HBM layouts; the
  * pieces here take plain pointers and values.  Also: the truncating conversion, the gain look-up, the output word
  * (0xebfa), the constants of the AGC modes (0xdfe0) and of the constructor (0xdf14), and the host generator of the

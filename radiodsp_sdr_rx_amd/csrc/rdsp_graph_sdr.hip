@@ -215,7 +215,7 @@ extern "C" int rdsp_fft1024_node_status(rdsp_node_t *n) { return node_status(n);
 /* ---- the reference's own engine objects as graph nodes -------------------------------------------------------------------
  * `AudioSDRpreProcessor preProcessor;` and `AudioSDR SDR;` (RadioDSP_SDR_RX.ino:53-54) wired as INO:71-72,81-86: two inputs
  * (I, Q tiles), two outputs, one block per tick like the library's update().  The arithmetic is rdsp_preproc_update /
- * rdsp_engine_update (csrc/rdsp_preproc.hip, csrc/rdsp_engine.hip); the node only carries tiles to the device and back. */
+ * rdsp_engine_update (csrc/rdsp_preproc.hip, csrc/rdsp_engine.hip and its stage files); the node only carries tiles to the device and back. */
 namespace {
 struct PairNode : NodeDev<> {
   rdsp_engine_t *engine = nullptr;

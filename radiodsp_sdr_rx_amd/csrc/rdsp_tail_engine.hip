@@ -15,7 +15,7 @@
  *   - the ALS filter runs on a quad per channel: the four samples between two tap moves see the same taps, so each lane
  *     evaluates one sample's chain of 55 fused multiply-adds (the taps in registers, the same in all four lanes), and
  *     every lane then makes the move with the fourth lane's error (quad_perm DPP).
- * The stage bodies are rdsp_engine_laws.h's, the ones rdsp_engine_t's tail kernels (rdsp_engine.hip) call; this kernel
+ * The stage bodies are rdsp_engine_laws.h's, the ones rdsp_engine_t's tail kernels (rdsp_engine_tail.hip) call; this kernel
  * runs them on the chain's buffers: float rows at any stride in, int16 L = R pairs (arm_float_to_q15 rounding) and float
  * pairs out, channel sub-batches by ch_base.
  * 180 VGPRs, no scratch.  (Holding the next block in registers through the current one took the kernel to 256 VGPRs

@@ -1,6 +1,6 @@
 """`AudioSDR SDR;` of the reference sketch (RadioDSP_SDR_RX.ino:54) for many receivers on one GPU: a ctypes mirror of
 the rdsp_engine_* entry points of include/rdsp.h.  Method names, argument meaning and numbering are the engine's
-(INO:117-139, RDSP_controls.h:149-423); the arithmetic is csrc/rdsp_engine.hip's."""
+(INO:117-139, RDSP_controls.h:149-423); the arithmetic is csrc/rdsp_engine.hip's (its stage files rdsp_engine_front / _hilbert / _tail.hip)."""
 import ctypes as C
 
 import numpy as np

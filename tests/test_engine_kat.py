@@ -6,7 +6,7 @@ and menus, on seeded int16 IQ (tests/golden/make_engine_kat.py; `--check` reprod
 
 `-m "not gpu"`: oracle/rdsp_engine_oracle.c, the restatement written from the image's code, against every case -- the
 int16 audio and the float buffers after each stage, BIT FOR BIT -- and the tables it generates against the object's.
-`-m gpu`: rdsp_engine_t (csrc/rdsp_engine.hip, host object csrc/rdsp_engine_host.h and the host files it names) through the C-ABI against the same int16 audio, bit for bit as well: the
+`-m gpu`: rdsp_engine_t (csrc/rdsp_engine.hip and the stage files rdsp_engine_front / _hilbert / _tail.hip, host object csrc/rdsp_engine_host.h and the host files it names) through the C-ABI against the same int16 audio, bit for bit as well: the
 kernels evaluate the same operations in the same order (the north-star's tolerance for float work is 1e-5; nothing of it
 is used here), on one channel per case, on all cases as channels of the same engine where the settings allow, and with
 the blocks cut into calls of different sizes."""
@@ -308,6 +308,57 @@ def test_gpu_engine_drawn_sessions_against_the_restatement(rdsp):
         for c in range(5):
             assert np.array_equal(out[c], oracle_lib.OracleEngine().run(x[c], calls)), (s, c)
         eng.close()
+
+
+_SAM_ALS_CACHE = {}
+
+
+def _sam_als_19_channels(blanker):
+    """19 drawn signals through the restatement in SAM with the ALS filter (notch, adaptive), with or without the blanker:
+    the input, the setter calls, each channel's audio and final scalars, and its lock flag after every block"""
+    if blanker not in _SAM_ALS_CACHE:
+        import oracle_lib
+        nch, nb = 19, 48
+        x = np.stack([_drawn_session(700 + c, nb)[0] for c in range(nch)])
+        calls = [[0, "setDemodMode", 5], [0, "enableALSfilter"], [0, "setALSfilterNotch"], [0, "setALSfilterAdaptive"]]
+        if blanker:
+            calls.append([0, "enableNoiseBlanker"])
+        want, final, lock = np.zeros((nch, nb * 128), np.int16), [], np.zeros((nch, nb))
+        for c in range(nch):
+            e = oracle_lib.OracleEngine()
+            for k in calls:
+                e.call(*k[1:])
+            for b in range(nb):
+                want[c, b * 128:(b + 1) * 128] = e.update(x[c, b * 128:(b + 1) * 128, 0], x[c, b * 128:(b + 1) * 128, 1])
+                lock[c, b] = e.final()[6]
+            final.append(e.final())
+        _SAM_ALS_CACHE[blanker] = (x, calls, want, final, lock)
+    return _SAM_ALS_CACHE[blanker]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("blanker", [False, True])
+def test_gpu_engine_sam_blanker_als_across_workgroups(rdsp, blanker):
+    """SAM with the ALS filter (notch, adaptive), without and with the blanker, on 19 receivers with a signal each: three
+    front workgroups (8 + 8 + 3 channels) and two ALS tail workgroups (16 + 3), 48 blocks in calls of 6 -- the audio and
+    the final scalars of every channel against the CPU restatement, bit for bit.  The input is checked first, on the
+    restatement with the blanker on, for what it is there for: in every front workgroup two channels differ in their lock
+    flag after some block (the workgroup runs the PLL's rotation and the out-of-lock detector side by side, next to the
+    blanker), and the blanker's final hit flag is set on some channels and clear on others"""
+    _, _, _, final_nb, lock_nb = _sam_als_19_channels(True)
+    for lo, hi in ((0, 8), (8, 16), (16, 19)):
+        assert any(len(set(lock_nb[lo:hi, b])) > 1 for b in range(lock_nb.shape[1])), (lo, hi)
+    assert {float(f[7]) for f in final_nb} == {0.0, 1.0}
+    x, calls, want, final, _ = _sam_als_19_channels(blanker)
+    nch = len(x)
+    eng = _engine(rdsp, nch, 8)
+    eng.sketch_setup()
+    out = _run_product(eng, x, calls, 6)
+    got = eng.scalars()
+    for c in range(nch):
+        assert np.array_equal(out[c], want[c]), (c, int(np.argmax(out[c] != want[c])))
+        assert np.array_equal(got[c].view(np.uint32), final[c].view(np.uint32)), (c, got[c], final[c])
+    eng.close()
 
 
 @pytest.mark.gpu

@@ -260,7 +260,7 @@ def test_register_budget_of_the_engine_law_tail_kernels(tmp_path):
             ent[k] = v.strip()
             if k == ".name":
                 notes[ent[k]] = ent
-    budget = {"rdsp_engine_tail_kernelILb1E": 209, "rdsp_engine_tail_pipe_kernel": 209, "rdsp_tail_engine_kernel": 180}
+    budget = {"rdsp_engine_tail_kernelE": 209, "rdsp_engine_tail_pipe_kernel": 209, "rdsp_tail_engine_kernel": 180}
     for key, vgpr in budget.items():
         hit = [e for n, e in notes.items() if key in n]
         assert len(hit) == 1, (key, sorted(notes)[:5])
@@ -508,7 +508,7 @@ def test_as_written_resynthesis_in_closed_form_is_the_tables_own_arithmetic():
 
 
 def test_engine_kernels_division_free_forms_are_the_quotients():
-    """csrc/rdsp_engine.hip replaces two IEEE double divisions of the engine's arithmetic by forms without one and claims
+    """csrc/rdsp_engine_dev.h replaces two IEEE double divisions of the engine's arithmetic by forms without one and claims
     the same bits: v / 32767.0 for every int16 v (q0 = v y, r = fma(-q0, 32767, v), q = fma(r, y, q0), y = RN(1 / 32767)),
     and trunc(a / d) for the table index (d = the double of the float 2 pi; the estimate a (1 / d) corrected by two exact
     comparisons with k d).  Both are checked here in exact rational arithmetic: all 65 536 int16 values; every index k with
