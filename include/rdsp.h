@@ -970,6 +970,41 @@ int rdsp_engine_read_meter(rdsp_engine_t *e, int n_blocks, float *d_level, size_
 int rdsp_engine_active(rdsp_engine_t *e, int32_t *d_list, int32_t *d_count, void *stream);
 int rdsp_engine_get_meter(rdsp_engine_t *e, float *host_out /* [n_channels][4] */, void *stream);
 int rdsp_engine_read_demod(rdsp_engine_t *e, int n_blocks, float *d_out, size_t out_stride, void *stream);
+/* Packed audio of the open receivers.  The engine hands back every receiver's stereo row on every call; with a squelch in
+ * force most of it is zero words, and the right word always repeats the left.  rdsp_engine_pack_active gathers, after a call,
+ * the blocks whose gate was open into dense mono blocks with a record each.  Opt-in, and needs rdsp_engine_enable_meter: an
+ * engine that never calls it launches and allocates what it did before.  On the device, no atomics, the same bytes every time.
+ *   - open[ch][b] are the last call's gate records (what rdsp_engine_read_meter returns).  The packed sequence is every
+ *     (ch, b) with b < n_blocks and open[ch][b] != 0, by channel ascending, then block ascending.  needed = its length,
+ *     written = min(needed, capacity_blocks); d_counts[0] = needed, d_counts[1] = written.
+ *   - for k < written: d_records[k] = {ch, b} of the k-th element (b: the block's index inside the call), and
+ *     d_audio[k * 128 + t] = the LEFT word d_lr[(ch * out_stride + b * 128 + t) * 2], t = 0 ... 127.  Nothing at or behind
+ *     index `written` is written in either buffer.  Closed blocks of d_lr are never read.
+ *   - d_lr, out_stride are the rows the last update wrote, as passed to it (any of rdsp_engine_update, _update_sources,
+ *     _update_source_samples); n_blocks may be less than the call's.  The call is stream-ordered on `stream` behind whatever
+ *     that update left; it modifies neither d_lr nor the meter's state or records, and may be repeated, also with another
+ *     capacity.  d_audio must be 16-byte aligned; d_lr rows that are not take 4-byte loads.
+ *   - sizing call: capacity_blocks == 0 with d_audio == d_records == NULL writes the counts only.
+ *   - squelch off: every block is open, and the call is the stereo-to-mono transpose of the whole output.
+ *   - n_blocks == 0, or no update made yet: counts {0, 0}.
+ *   - the first call allocates the scratch (4 bytes per channel), not rdsp_engine_enable_meter; if that fails the call
+ *     returns RDSP_ERR_NOMEM and the engine is as it was.
+ *   - Refused with nothing written: RDSP_ERR_NOT_READY before rdsp_engine_enable_meter; RDSP_ERR_INVALID for d_lr or d_counts
+ *     NULL, n_blocks < 0 or above the last call's, out_stride < n_blocks x 128, capacity_blocks > 0 with a NULL d_audio or
+ *     d_records, d_audio not 16-byte aligned, capacity_blocks above INT32_MAX (and n_channels x n_blocks above INT32_MAX,
+ *     which the counts could not hold).
+ * rdsp_pack_runs (host only) merges records of one channel with consecutive blocks into runs: block = first_block + the
+ *   first record's block (the run's absolute first block, first_block being the call's), record = the index of its first
+ *   packed block, n_blocks its length: "receiver c, blocks B ... B + n - 1, audio at offset r".  It returns the number of runs,
+ *   also when max_runs is too small (then the first max_runs are written), or RDSP_ERR_INVALID -- nothing written -- for
+ *   records that are negative or not strictly ascending in (channel, block), negative counts or a NULL array with a count above
+ *   0.  Runs that touch a call boundary are joined by the caller, with first_block. */
+typedef struct { int32_t channel, block; } rdsp_pack_record_t;
+typedef struct { int32_t channel, n_blocks, record; int64_t block; } rdsp_pack_run_t;
+int rdsp_engine_pack_active(rdsp_engine_t *e, const int16_t *d_lr, size_t out_stride, int n_blocks,
+                            int16_t *d_audio /* [capacity_blocks][128] */, rdsp_pack_record_t *d_records /* [capacity_blocks] */,
+                            size_t capacity_blocks, int32_t *d_counts /* [2]: needed, written */, void *stream);
+int rdsp_pack_runs(const rdsp_pack_record_t *records, int n_records, int64_t first_block, rdsp_pack_run_t *runs, int max_runs);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -2,8 +2,9 @@
  * rdsp_engine_host.h -- what the host files of rdsp_engine_t (include/rdsp.h) share: the object, a group's settings, the
  * meter as an owner, the walk over groups.  rdsp_engine_host.hip holds the sketch's settings and setters and creates, resets
  * and runs the object; rdsp_engine_groups.hip the receiver groups; rdsp_engine_meter_host.hip the signal meter's owner and
- * entry points; rdsp_engine_sources_host.hip the entry points of the shared IQ sources; rdsp_engine_state.hip the state
- * blob.  Host logic only: the kernels are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip) and rdsp_engine_meter.hip's, the front end is
+ * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
+ * rdsp_engine_state.hip the state blob.  Host logic only: the kernels are rdsp_engine.hip's stage files' (rdsp_engine_front /
+ * _hilbert / _tail.hip), rdsp_engine_meter.hip's and rdsp_engine_pack.hip's, the front end is
  * rdsp_engine_sources.h's.  All five are compiled with the kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
@@ -19,6 +20,7 @@
 #include "rdsp_engine_int.h"
 #include "rdsp_engine_laws.h"
 #include "rdsp_engine_meter.h"
+#include "rdsp_engine_pack.h"
 #include "rdsp_engine_sources.h"
 
 using namespace rdsp_eng;
@@ -38,6 +40,7 @@ struct EngMeter {
   DevBuf<float> words, level, peak;
   DevBuf<uint8_t> open;
   DevBuf<int32_t> list, count;
+  DevBuf<int32_t> pack_offset; /* [ch], rdsp_engine_pack_active's scratch: allocated by its first call, not by init */
   size_t n_channels = 0, max_blocks = 0;
   int blocks = 0; /* of the last call that left records */
   hipError_t init(size_t n_channels, size_t max_blocks); /* every buffer, zeroed */
@@ -45,6 +48,8 @@ struct EngMeter {
   /* behind the tail kernel of the group p launched (channels c0 on): it measures p.audio and gates p.out, rows of the caller's d_lr */
   hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_meter::MeterSet &set, const int16_t *d_lr, hipStream_t s) const;
   hipError_t launch_list(int n_blocks, hipStream_t s); /* once behind every group's meter: the list of a call of n_blocks */
+  /* the open blocks of the last call's first n_blocks, out of the caller's rows: p carries the caller's arguments, the rest is filled in here */
+  hipError_t launch_pack(PackParams p, hipStream_t s) const;
 };
 struct rdsp_engine {
   int n_channels, device, max_blocks;

@@ -1,6 +1,7 @@
-/* rdsp_engine_meter_host.hip -- the signal meter, the squelch and the active-receiver list of rdsp_engine_t on the host:
- * EngMeter (rdsp_engine_host.h) owns the buffers and makes the two launches; the entry points check their arguments.
- * include/rdsp.h has the definition; the kernels are rdsp_engine_meter.hip's, the arithmetic rdsp_meter.h's. */
+/* rdsp_engine_meter_host.hip -- the signal meter, the squelch, the active-receiver list and the packed audio of the open
+ * receivers of rdsp_engine_t on the host: EngMeter (rdsp_engine_host.h) owns the buffers and makes the launches; the entry
+ * points check their arguments.  include/rdsp.h has the definition; the kernels are rdsp_engine_meter.hip's and
+ * rdsp_engine_pack.hip's, the arithmetic rdsp_meter.h's. */
 #include "rdsp_engine_host.h"
 
 hipError_t EngMeter::init(size_t n, size_t blocks_per_call) {
@@ -28,6 +29,10 @@ hipError_t EngMeter::launch_group(const EngParams &p, size_t c0, const rdsp_mete
 hipError_t EngMeter::launch_list(int n_blocks, hipStream_t s) {
   blocks = n_blocks;
   return rdsp_engine_active_launch(ActiveParams{words, (int)n_channels, list, count}, s);
+}
+hipError_t EngMeter::launch_pack(PackParams p, hipStream_t s) const {
+  p.n_channels = (int)n_channels; p.open = open; p.rec_stride = max_blocks; p.offset = pack_offset;
+  return rdsp_engine_pack_launch(p, s);
 }
 
 namespace {
@@ -103,6 +108,42 @@ int rdsp_engine_active(rdsp_engine_t *e, int32_t *d_list, int32_t *d_count, void
   if (err == hipSuccess && d_list) err = hipMemcpyAsync(d_list, e->meter->list, (size_t)e->n_channels * 4, hipMemcpyDeviceToDevice, s);
   if (err == hipSuccess && d_count) err = hipMemcpyAsync(d_count, e->meter->count, 4, hipMemcpyDeviceToDevice, s);
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_active", err);
+}
+
+int rdsp_engine_pack_active(rdsp_engine_t *e, const int16_t *d_lr, size_t out_stride, int n_blocks, int16_t *d_audio,
+                            rdsp_pack_record_t *d_records, size_t capacity_blocks, int32_t *d_counts, void *stream) {
+  if (!e) return RDSP_ERR_INVALID;
+  if (no_meter(e, "rdsp_engine_pack_active")) return RDSP_ERR_NOT_READY;
+  EngMeter &m = *e->meter;
+  if (!d_lr || !d_counts || n_blocks < 0 || n_blocks > m.blocks || out_stride < (size_t)std::max(n_blocks, 0) * BS ||
+      (capacity_blocks > 0 && (!d_audio || !d_records)) || ((uintptr_t)d_audio & 15) != 0 || capacity_blocks > (size_t)INT32_MAX ||
+      (size_t)e->n_channels * (size_t)std::max(n_blocks, 0) > (size_t)INT32_MAX) {
+    rdsp_set_error("rdsp_engine_pack_active: bad argument (d_lr and d_counts not NULL; n_blocks %d of the last call's %d; out_stride at least "
+                   "n_blocks * 128; d_audio 16-byte aligned, and d_records, not NULL with a capacity; capacity_blocks %zu at most INT32_MAX)",
+                   n_blocks, m.blocks, capacity_blocks);
+    return RDSP_ERR_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipSetDevice(e->device);
+  if (err != hipSuccess) return engine_fail("rdsp_engine_pack_active", err);
+  if (n_blocks == 0) { /* also: no call yet */
+    err = hipMemsetAsync(d_counts, 0, 2 * sizeof(int32_t), s);
+    return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_pack_active", err);
+  }
+  if (!m.pack_offset) { /* the first pack call: an engine that meters and never packs allocates nothing for it */
+    DevBuf<int32_t> b;
+    if ((err = b.alloc((size_t)e->n_channels)) != hipSuccess) {
+      b.p = nullptr;
+      rdsp_set_error("rdsp_engine_pack_active: %s", hipGetErrorString(err));
+      return RDSP_ERR_NOMEM;
+    }
+    std::swap(m.pack_offset.p, b.p);
+  }
+  PackParams p{};
+  p.lr = (const int32_t *)d_lr; p.lr_stride = out_stride; p.lr_vec = ((uintptr_t)d_lr & 15) == 0 && out_stride % 4 == 0;
+  p.n_blocks = n_blocks; p.audio = d_audio; p.records = (int2 *)d_records; p.capacity = (int)capacity_blocks; p.counts = d_counts;
+  err = m.launch_pack(p, s);
+  return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_pack_active", err);
 }
 
 int rdsp_engine_get_meter(rdsp_engine_t *e, float *host_out, void *stream) {

@@ -187,6 +187,34 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_demod(self.h, int(n_blocks), out.data_ptr(), n, stream_ptr(stream)))
         return out
 
+    def pack_active(self, lr, n_blocks=None, capacity=None, stream=None):
+        """the open blocks of the last call, dense and mono (include/rdsp.h, "packed audio of the open receivers"): lr is the
+        tensor update() returned or filled -> (audio int16 [written, 128], records int32 [written, 2] = channel, block inside
+        the call, both on the device; needed).  n_blocks: the call's first so many blocks (default: all of lr's); capacity:
+        room for so many blocks (default: a sizing call first, then exactly `needed`)."""
+        import torch
+        assert lr.dtype == torch.int16 and lr.dim() == 3 and lr.shape[0] == self.n_channels and lr.shape[2] == 2
+        assert lr.stride(2) == 1 and lr.stride(1) == 2 and (lr.stride(0) % 2 == 0 or self.n_channels == 1)
+        stride = lr.stride(0) // 2 if self.n_channels > 1 else lr.shape[1]
+        n = lr.shape[1] // 128 if n_blocks is None else int(n_blocks)
+        cnt = torch.empty(2, dtype=torch.int32, device=lr.device)
+        s = stream_ptr(stream)
+
+        def counts():   # read on the host: wait for the caller's stream, whichever form it came in, as active() does
+            if stream is not None:
+                (stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(stream)).synchronize()
+            return [int(v) for v in cnt.tolist()]
+        if capacity is None:
+            check(self.lib.rdsp_engine_pack_active(self.h, lr.data_ptr(), stride, n, None, None, 0, cnt.data_ptr(), s))
+            capacity = counts()[0]
+        capacity = int(capacity)
+        audio = torch.empty((capacity, 128), dtype=torch.int16, device=lr.device)
+        records = torch.empty((capacity, 2), dtype=torch.int32, device=lr.device)
+        check(self.lib.rdsp_engine_pack_active(self.h, lr.data_ptr(), stride, n, audio.data_ptr() if capacity else None,
+                                               records.data_ptr() if capacity else None, capacity, cnt.data_ptr(), s))
+        needed, written = counts()
+        return audio[:written], records[:written], needed
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -248,6 +276,20 @@ def rate_of_hz(fs_hz):
     p, q = C.c_int(), C.c_int()
     check(load().rdsp_engine_rate_of_hz(float(fs_hz), C.byref(p), C.byref(q)))
     return p.value, q.value
+
+
+def pack_runs(records, first_block=0):
+    """the records of a pack_active (host int32 [n, 2]: channel, block inside the call) merged into runs of consecutive blocks
+    of one receiver -> int64 [m, 4]: channel, absolute first block (first_block + block), number of blocks, index of the run's
+    first packed block; host only.  Records that are not strictly ascending in (channel, block) are refused."""
+    rec = np.ascontiguousarray(records, np.int32).reshape(-1, 2)
+    run_t = np.dtype([("channel", np.int32), ("n_blocks", np.int32), ("record", np.int32), ("block", np.int64)], align=True)   # rdsp_pack_run_t
+    runs = np.zeros(max(len(rec), 1), run_t)
+    n = load().rdsp_pack_runs(rec.ctypes.data, len(rec), int(first_block), runs.ctypes.data, len(rec))
+    if n < 0:
+        check(n)
+    r = runs[:n]
+    return np.stack([r["channel"], r["block"], r["n_blocks"], r["record"]], 1).astype(np.int64).reshape(-1, 4)
 
 
 def ms_of_db(db):

@@ -1,0 +1,485 @@
+"""rdsp_engine_pack_active and rdsp_pack_runs (include/rdsp.h "packed audio of the open receivers"; csrc/rdsp_engine_pack.hip,
+csrc/rdsp_pack_host.c).
+
+`-m "not gpu"`: rdsp_pack_runs -- through the library and through tests/host/host_pack_check.c, a program of its own built
+plain and under ASan + UBSan and run directly -- against tests/engine_pack_model.py; the model's own order, count and
+truncation on drawn gates; the exports.
+`-m gpu`: the pack against the model applied to the audio the call returned and the gates rdsp_engine_read_meter returns,
+every comparison exact.  Gate patterns come from receiver groups: squelch off (all open), set_squelch(1e30, 1e30, 0) (never
+open), keyed bursts with thresholds between their loud and quiet levels (mixed rows)."""
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import engine_pack_model as P
+from engine_meter_model import F32, Meter, Squelch
+from test_engine_meter import _bursts, _engine, _on_sources, _thresholds
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+NCH = 97
+
+
+# ---- CPU: rdsp_pack_runs ---------------------------------------------------------------------------------------------------
+def _run_cases():
+    """(name, records, first_block, max_runs or None for "room for all") -- None as the expectation means: refused"""
+    r = np.random.default_rng(3)
+    drawn = np.argwhere(r.random((9, 40)) < 0.55)                       # ascending in (channel, block) by construction
+    return [("empty", np.zeros((0, 2), int), 0, None),
+            ("one", [(4, 7)], 100, None),
+            ("last_block_then_block_0", [(2, 62), (2, 63), (3, 0), (3, 1), (5, 0)], 640, None),   # 2's run ends, 3's begins: no merge
+            ("channel_change_at_consecutive_blocks", [(0, 5), (1, 6), (1, 7)], 0, None),
+            ("max_runs_too_small", [(0, 0), (0, 1), (0, 3), (1, 0), (1, 2), (1, 3), (1, 4), (2, 9)], 5, 2),
+            ("max_runs_zero", [(0, 0), (0, 2)], 0, 0),
+            ("max_runs_cuts_a_growing_run", [(0, 0), (0, 1), (1, 0), (1, 1), (1, 2)], 0, 1),
+            ("negative_first_block", [(1, 0), (1, 1), (1, 5)], -3, None),
+            ("large_first_block", [(0, 1)], 2 ** 40, None),
+            ("drawn", drawn, 12345, None),
+            ("unordered_blocks", [(1, 3), (1, 2)], 0, None),
+            ("unordered_channels", [(2, 0), (1, 5)], 0, None),
+            ("duplicate", [(1, 3), (1, 3)], 0, None),
+            ("negative_record", [(0, -1)], 0, None)]
+
+
+def _want(records, first_block):
+    try:
+        return P.runs(records, first_block)
+    except ValueError:
+        return None
+
+
+def test_pack_runs_model():
+    """the model's runs on the cases: what merges, what does not, what is refused"""
+    want = {name: _want(rec, fb) for name, rec, fb, _ in _run_cases()}
+    assert want["empty"].shape == (0, 4) and want["one"].tolist() == [[4, 107, 1, 0]]
+    assert want["last_block_then_block_0"].tolist() == [[2, 702, 2, 0], [3, 640, 2, 2], [5, 640, 1, 4]]
+    assert want["channel_change_at_consecutive_blocks"].tolist() == [[0, 5, 1, 0], [1, 6, 2, 1]]
+    assert want["negative_first_block"].tolist() == [[1, -3, 2, 0], [1, 2, 1, 2]]
+    assert all(want[k] is None for k in ("unordered_blocks", "unordered_channels", "duplicate", "negative_record"))
+    d = want["drawn"]
+    assert d[:, 2].sum() == len(_run_cases()[9][1]) and np.array_equal(d[:, 3], np.concatenate([[0], np.cumsum(d[:, 2])[:-1]]))
+
+
+def test_pack_runs_library(rdsp):
+    """rdsp_pack_runs through the library: pack_runs() against the model, the refusals, and max_runs too small (the count of
+    all runs is returned, the first max_runs are written, nothing behind them)"""
+    from radiodsp_sdr_rx_amd.engine import pack_runs
+    lib = rdsp.load()
+    run_t = np.dtype([("channel", np.int32), ("n_blocks", np.int32), ("record", np.int32), ("block", np.int64)], align=True)
+    assert run_t.itemsize == 24
+    for name, rec, fb, max_runs in _run_cases():
+        want = _want(rec, fb)
+        rec = np.ascontiguousarray(rec, np.int32).reshape(-1, 2)
+        if want is None:
+            with pytest.raises(rdsp.RdspError) as ex:
+                pack_runs(rec, fb)
+            assert ex.value.code == -1 and b"rdsp_pack_runs" in lib.rdsp_last_error(), name
+            continue
+        assert np.array_equal(pack_runs(rec, fb), want), name
+        if max_runs is not None:
+            runs = np.zeros(max_runs + 2, run_t)
+            runs["channel"] = -7
+            n = lib.rdsp_pack_runs(rec.ctypes.data, len(rec), fb, runs.ctypes.data, max_runs)
+            assert n == len(want) > max_runs, name
+            got = np.stack([runs[k] for k in ("channel", "block", "n_blocks", "record")], 1)[:max_runs]
+            assert np.array_equal(got, want[:max_runs]) and np.all(runs["channel"][max_runs:] == -7), name
+    assert lib.rdsp_pack_runs(None, 1, 0, None, 0) == -1 and lib.rdsp_pack_runs(None, -1, 0, None, 0) == -1
+    assert lib.rdsp_pack_runs(None, 0, 0, None, -1) == -1 and lib.rdsp_pack_runs(None, 0, 0, None, 0) == 0
+    one = np.array([[0, 0]], np.int32)
+    assert lib.rdsp_pack_runs(one.ctypes.data, 1, 0, None, 1) == -1 and lib.rdsp_pack_runs(one.ctypes.data, 1, 0, None, 0) == 1
+    assert lib.rdsp_pack_runs(one.ctypes.data, 1, 2 ** 63 - 5, None, 0) == -1               # first_block + block would leave int64
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_pack_runs_host_program(tmp_path, sanitize):
+    """tests/host/host_pack_check.c with csrc/rdsp_pack_host.c, plain and under ASan + UBSan, a program of its own run on the
+    CPU: its printed runs equal the model's for every case, the refused ones are refused"""
+    exe = str(tmp_path / ("host_pack_check_san" if sanitize else "host_pack_check"))
+    extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror"] + extra + ["-I", os.path.join(ROOT, "include"),
+                           os.path.join(HERE, "host", "host_pack_check.c"), os.path.join(ROOT, "radiodsp_sdr_rx_amd", "csrc", "rdsp_pack_host.c"),
+                           "-o", exe])
+    cases = _run_cases()
+    text = []
+    for _, rec, fb, max_runs in cases:
+        rec = np.asarray(rec, np.int64).reshape(-1, 2)
+        text.append(f"{fb} {len(rec) if max_runs is None else max_runs} {len(rec)}")
+        text += [f"{c} {b}" for c, b in rec]
+    fin = tmp_path / "cases.txt"
+    fin.write_text("\n".join(text) + "\n")
+    out = subprocess.run([exe, str(fin)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.endswith("host_pack_check OK\n"), out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "Sanitizer" not in out.stderr, out.stderr
+    lines = out.stdout.splitlines()[:-1]
+    at = 0
+    for name, rec, fb, max_runs in cases:
+        want = _want(rec, fb)
+        if want is None:
+            assert lines[at] == "refused -1", name
+            at += 1
+            continue
+        assert lines[at] == f"runs {len(want)}", name
+        shown = len(want) if max_runs is None else min(len(want), max_runs)
+        got = np.array([[int(v) for v in ln.split()] for ln in lines[at + 1:at + 1 + shown]], np.int64).reshape(-1, 4)
+        assert np.array_equal(got[:, [0, 1, 2, 3]], want[:shown]), name
+        at += 1 + shown
+    assert at == len(lines)
+
+
+def test_pack_model_on_drawn_gates():
+    """the model itself: the order is the definition's (the records ascend in (channel, block) and are exactly the open
+    cells), needed is gate.sum(), every block is its cell's 128 words, and a capacity keeps a prefix"""
+    r = np.random.default_rng(8)
+    n, nb = 23, 17
+    audio = r.integers(-32768, 32768, (n, nb * 128)).astype(np.int16)
+    gate = (r.random((n, nb)) < 0.4).astype(np.uint8)
+    gate[5] = 0
+    gate[6] = 1
+    blocks, rec, needed = P.pack(audio, gate)
+    assert needed == gate.sum() == len(rec) == len(blocks)
+    assert np.array_equal(rec, np.argwhere(gate))                                        # numpy's row-major order is the definition's
+    key = rec[:, 0].astype(np.int64) * nb + rec[:, 1]
+    assert np.all(np.diff(key) > 0)
+    assert np.array_equal(blocks, audio.reshape(n, nb, 128)[rec[:, 0], rec[:, 1]])
+    for cap in (0, 1, needed - 1, needed, needed + 5):
+        b, q, need = P.pack(audio, gate, cap)
+        w = min(needed, cap)
+        assert need == needed and np.array_equal(b, blocks[:w]) and np.array_equal(q, rec[:w])
+    e = P.pack(audio, np.zeros_like(gate))
+    assert e[0].shape == (0, 128) and e[1].shape == (0, 2) and e[2] == 0
+    assert np.array_equal(P.pack(audio, np.ones_like(gate))[0].reshape(n, nb * 128), audio)   # all open: the rows themselves
+
+
+def test_pack_exports(rdsp):
+    from radiodsp_sdr_rx_amd import engine
+    lib = rdsp.load()
+    assert hasattr(lib, "rdsp_engine_pack_active") and hasattr(lib, "rdsp_pack_runs")
+    assert callable(engine.Engine.pack_active) and callable(engine.pack_runs)
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------
+NEVER = 1e30
+
+
+def _cuda(x):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+
+
+def _call(eng, x):
+    """one update of x int16 [n, t, 2] -> (the returned tensor, its left words on the host, the call's gates on the host)"""
+    y = eng.update(_cuda(x))
+    h = y.cpu().numpy()
+    assert np.array_equal(h[..., 0], h[..., 1])
+    return y, h[..., 0], eng.read_meter(x.shape[1] // 128)[2].cpu().numpy()
+
+
+def _is_model(eng, y, audio, gate, **kw):
+    """Engine.pack_active(y) against the model on (audio, gate), exactly -> (blocks, records) on the host"""
+    a, r, needed = eng.pack_active(y, **kw)
+    want = P.pack(audio, gate, kw.get("capacity"))
+    a, r = a.cpu().numpy(), r.cpu().numpy()
+    assert needed == want[2] and a.shape == want[0].shape and r.shape == want[1].shape
+    assert np.array_equal(r, want[1]) and np.array_equal(a, want[0])
+    return a, r
+
+
+def _pattern(n, t):
+    """int16 [n, t, 2], different in every word of a row and L != R: L = (ch * 131 + t) mod 65536 - 32768, R = ~L"""
+    left = ((np.arange(n)[:, None] * 131 + np.arange(t)[None, :]) % 65536 - 32768).astype(np.int16)
+    return np.stack([left, ~left], -1)
+
+
+@functools.lru_cache(maxsize=None)
+def _squelch_stream():
+    """test_gpu_squelch's stream and thresholds: 97 channels x 64 blocks of keyed tones (seed 22), thresholds from the model's
+    levels of the demodulated rows, hang 3 -> (x, the one-call audio with every gate open, Squelch)"""
+    x = _bursts(22, NCH, 64)
+    eng = _engine()
+    eng.set_meter(0.5, 0.5)
+    y, audio, gate = _call(eng, x)
+    assert gate.all()
+    _is_model(eng, y, audio, gate)                                                       # squelch off: the mono transpose of the whole output
+    demod = eng.read_demod(64).cpu().numpy()
+    open_ms, close_ms = _thresholds(Meter(NCH).run(demod, Squelch(attack=0.5, decay=0.5))[0])
+    return x, audio, Squelch(open_ms, close_ms, 3, attack=0.5, decay=0.5)
+
+
+def _between(level):
+    """a squelch for meter coefficients 1 and 1 (the level is the block's mean square) from the levels an engine measured on
+    keyed tones with the squelch off: thresholds a fifth and a fiftieth of the loudest level, far above the quiet blocks', and a
+    hang of one block -- loud blocks open, the second quiet block behind them closes"""
+    top = float(np.max(level))
+    return Squelch(F32(0.2 * top), F32(0.02 * top), 1, attack=1.0, decay=1.0)
+
+
+def _grouped(n, max_blocks, first, kinds, s):
+    """an engine of n receivers in groups starting at `first`, each "open" (squelch off), "closed" (never opens) or "bursts" (squelch s)"""
+    eng = _engine(n, max_blocks)
+    eng.set_meter(float(s.attack), float(s.decay))
+    eng.set_groups(first)
+    for g, kind in enumerate(kinds):
+        eng.select_group(g)
+        if kind == "closed":
+            eng.set_squelch(NEVER, NEVER, 0)
+        elif kind == "bursts":
+            eng.set_squelch(s.open_ms, s.close_ms, s.hang_blocks)
+    eng.select_group(-1)
+    return eng
+
+
+@pytest.mark.gpu
+def test_gpu_pack_is_the_model_for_every_call_split(rdsp):
+    """97 channels in three groups (0-29 all open, 30-59 never open, 60-96 keyed bursts), 64 blocks in calls of 64, 7 and 1: after
+    every call the pack equals the model applied to that call's returned audio and read_meter gates, and its runs are the
+    model's; with the records made absolute by the call's first block, every channel's sequence of (block, 128 words) is the
+    same for the three splits and is the open blocks of the one-call run's audio"""
+    from radiodsp_sdr_rx_amd.engine import pack_runs
+    x, free_audio, s = _squelch_stream()
+    seen = {}
+    for split in (64, 7, 1):
+        eng = _grouped(NCH, 64, [0, 30, 60], ["open", "closed", "bursts"], s)
+        got = np.zeros((NCH, 64, 128), np.int16)
+        have = np.zeros((NCH, 64), np.uint8)
+        audio, gates, joined = [], [], 0
+        for a in range(0, 64, split):
+            b = min(64, a + split)
+            y, au, g = _call(eng, x[:, a * 128:b * 128])
+            blocks, rec = _is_model(eng, y, au, g)
+            runs = pack_runs(rec, a)
+            assert np.array_equal(runs, P.runs(rec, a))
+            assert not have[rec[:, 0], a + rec[:, 1]].any()
+            got[rec[:, 0], a + rec[:, 1]], have[rec[:, 0], a + rec[:, 1]] = blocks, 1
+            if split == 7 and a > 0:                                                     # runs of the bursts group that go on from the call in front
+                starts = runs[(runs[:, 1] == a) & (runs[:, 0] >= 60)][:, 0]
+                joined += int(gates[-1][starts, -1].sum())
+            audio.append(au); gates.append(g)
+        audio, gate = np.concatenate(audio, 1), np.concatenate(gates, 1)
+        assert np.array_equal(have, gate) and gate[:30].all() and not gate[30:60].any()
+        assert 0.2 < gate[60:].mean() < 0.9
+        assert np.array_equal(got[have == 1], audio.reshape(NCH, 64, 128)[have == 1])
+        if split == 7:
+            assert joined >= 1
+        seen[split] = (got, have)
+        eng.close()
+    for split in (7, 1):
+        assert np.array_equal(seen[split][0], seen[64][0]) and np.array_equal(seen[split][1], seen[64][1]), split
+    got, have = seen[64]
+    assert np.array_equal(got[have == 1], free_audio.reshape(NCH, 64, 128)[have == 1])     # an open block is the ungated engine's
+
+
+SHAPES = {1: ([0], ["bursts"]),
+          5: ([0, 1, 2, 4], ["open", "closed", "bursts", "open"]),                      # a ragged workgroup of the four-wave kernels
+          300: ([0, 40, 170, 260], ["open", "closed", "bursts", "open"]),               # waves 1 of the scan's chunk (64 ... 127) all closed
+          1100: ([0, 70, 900, 1090], ["open", "bursts", "closed", "open"])}             # two scan chunks; 1024 ... 1087 closed
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", [1, 9, 70])
+@pytest.mark.parametrize("n", [1, 5, 300, 1100])
+def test_gpu_pack_shapes(rdsp, n, nb):
+    """1, 5, 300 and 1100 channels x 1, 9 and 70 blocks of an engine with max_blocks_per_call 80 (70: past one 64-block ballot
+    trip and past the eight blocks a gather step holds): the first and the last channel open, whole waves of channels closed
+    between them, a group of keyed bursts; then every channel closed (needed 0, nothing written) and every channel open (needed
+    n x nb, the mono transpose).  The mixed call is packed a second time from rows the test overwrote with a pattern that
+    differs in every word and has L != R: a wrong channel, block, sample or side shows whatever the audio was."""
+    import torch
+    first, kinds = SHAPES[n]
+    base = _bursts(40 + nb, min(n, 48), nb, quiet=(1, 2, 3))
+    x = np.tile(base, (-(-n // len(base)), 1, 1))[:n]
+    probe = _engine(n, 80)
+    probe.set_meter(1.0, 1.0)
+    probe.update(_cuda(x))
+    s = _between(probe.read_meter(nb)[0].cpu().numpy())
+    probe.close()
+    eng = _grouped(n, 80, first, kinds, s)
+    y, audio, gate = _call(eng, x)
+    _is_model(eng, y, audio, gate)
+    bursts = slice(first[kinds.index("bursts")], (first + [n])[kinds.index("bursts") + 1])
+    assert gate[0].all() or n == 1
+    assert gate[n - 1].all() or n == 1
+    if gate[bursts].size >= 9:
+        assert gate[bursts].any() and not gate[bursts].all()
+    if n == 1100:
+        assert not gate[1024:1088].any()
+    pat = _pattern(n, nb * 128)
+    y.copy_(_cuda(pat))
+    _is_model(eng, y, pat[..., 0], gate)
+    eng.set_squelch(NEVER, NEVER, 0)                                                     # every group
+    eng.reset()
+    y, audio, gate = _call(eng, x)
+    assert not gate.any()
+    a, r, needed = eng.pack_active(y, capacity=3)
+    assert needed == 0 and len(a) == 0 and len(r) == 0
+    sent_a, sent_r = torch.full((3, 128), 77, dtype=torch.int16, device="cuda"), torch.full((3, 2), 77, dtype=torch.int32, device="cuda")
+    cnt = torch.full((2,), 77, dtype=torch.int32, device="cuda")
+    assert eng.lib.rdsp_engine_pack_active(eng.h, y.data_ptr(), nb * 128, nb, sent_a.data_ptr(), sent_r.data_ptr(), 3, cnt.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert cnt.tolist() == [0, 0] and bool((sent_a == 77).all()) and bool((sent_r == 77).all())
+    eng.disable_squelch()
+    eng.reset()
+    y, audio, gate = _call(eng, x)
+    assert gate.all()
+    a, r = _is_model(eng, y, audio, gate)
+    assert len(a) == n * nb and np.array_equal(a.reshape(n, nb * 128), audio)
+    assert np.array_equal(r, np.stack([np.repeat(np.arange(n), nb), np.tile(np.arange(nb), n)], 1))
+
+
+@functools.lru_cache(maxsize=None)
+def _twelve():
+    """97 channels x 12 blocks of keyed tones and a squelch between their levels -> (x, Squelch)"""
+    x = _bursts(31, NCH, 12, quiet=(2, 3))
+    eng = _engine(NCH, 12)
+    eng.set_meter(1.0, 1.0)
+    eng.update(_cuda(x))
+    return x, _between(eng.read_meter(12)[0].cpu().numpy())
+
+
+def _twelve_engine():
+    x, s = _twelve()
+    return x, _grouped(NCH, 12, [0, 10, 20], ["open", "closed", "bursts"], s)
+
+
+@pytest.mark.gpu
+def test_gpu_pack_capacity(rdsp):
+    """capacities 0 (NULL buffers: the sizing call), 1, needed - 1, needed and needed + 5: the counts are {needed, min(needed,
+    capacity)}, the written prefix is the model's, and the sentinel words behind `written` stay in both buffers"""
+    import torch
+    x, eng = _twelve_engine()
+    y, audio, gate = _call(eng, x)
+    blocks, rec, needed = P.pack(audio, gate)
+    assert needed > 8 and needed == gate.sum()
+    room = needed + 8
+    for cap in (0, 1, needed - 1, needed, needed + 5):
+        a = torch.full((room, 128), -21846, dtype=torch.int16, device="cuda")
+        r = torch.full((room, 2), -7, dtype=torch.int32, device="cuda")
+        cnt = torch.full((2,), -7, dtype=torch.int32, device="cuda")
+        rc = eng.lib.rdsp_engine_pack_active(eng.h, y.data_ptr(), 12 * 128, 12, a.data_ptr() if cap else None, r.data_ptr() if cap else None,
+                                             cap, cnt.data_ptr(), None)
+        torch.cuda.synchronize()
+        w = min(needed, cap)
+        assert rc == 0 and cnt.tolist() == [needed, w], cap
+        a, r = a.cpu().numpy(), r.cpu().numpy()
+        assert np.array_equal(a[:w], blocks[:w]) and np.array_equal(r[:w], rec[:w]), cap
+        assert np.all(a[w:] == -21846) and np.all(r[w:] == -7), cap
+        _is_model(eng, y, audio, gate, capacity=cap)
+
+
+@pytest.mark.gpu
+def test_gpu_pack_unaligned_rows(rdsp):
+    """update writes into rows 12 x 128 + 2 pairs apart that start at an odd word (test_gpu_squelch's buffer): the pack of those
+    rows -- the 4-byte load path -- equals the pack of the aligned run, through the C entry point and through pack_active on
+    the strided view"""
+    import torch
+    x, eng = _twelve_engine()
+    y, audio, gate = _call(eng, x)
+    want_a, want_r = _is_model(eng, y, audio, gate)
+    eng.reset()
+    stride = 12 * 128 + 2
+    buf = torch.full((NCH * stride + 1, 2), 7, dtype=torch.int16, device="cuda")
+    assert eng.lib.rdsp_engine_update(eng.h, _cuda(x).data_ptr(), 12 * 128, 12, buf.data_ptr() + 4, stride, None) == 0
+    assert np.array_equal(eng.read_meter(12)[2].cpu().numpy(), gate)
+    n = len(want_a)
+    a = torch.zeros((n, 128), dtype=torch.int16, device="cuda")
+    r = torch.zeros((n, 2), dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(2, dtype=torch.int32, device="cuda")
+    assert (buf.data_ptr() + 4) % 16 != 0
+    assert eng.lib.rdsp_engine_pack_active(eng.h, buf.data_ptr() + 4, stride, 12, a.data_ptr(), r.data_ptr(), n, cnt.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert cnt.tolist() == [n, n] and np.array_equal(a.cpu().numpy(), want_a) and np.array_equal(r.cpu().numpy(), want_r)
+    view = buf.as_strided((NCH, 12 * 128, 2), (2 * stride, 2, 1), 2)
+    a, r, needed = eng.pack_active(view)
+    assert needed == n and np.array_equal(a.cpu().numpy(), want_a) and np.array_equal(r.cpu().numpy(), want_r)
+    # rows 16-byte aligned but a stride that is no multiple of four pairs: the 4-byte path too
+    eng.reset()
+    buf2 = torch.full((NCH * stride, 2), 7, dtype=torch.int16, device="cuda")
+    assert buf2.data_ptr() % 16 == 0
+    assert eng.lib.rdsp_engine_update(eng.h, _cuda(x).data_ptr(), 12 * 128, 12, buf2.data_ptr(), stride, None) == 0
+    a, r, needed = eng.pack_active(buf2.view(NCH, stride, 2)[:, :12 * 128])
+    assert needed == n and np.array_equal(a.cpu().numpy(), want_a) and np.array_equal(r.cpu().numpy(), want_r)
+
+
+@pytest.mark.gpu
+def test_gpu_pack_fewer_blocks_than_the_call(rdsp):
+    """n_blocks = 5 after a 12-block call: the model on the first 5 blocks; again: the same bytes; then all 12: the model"""
+    x, eng = _twelve_engine()
+    y, audio, gate = _call(eng, x)
+    one = _is_model(eng, y, audio[:, :5 * 128], gate[:, :5], n_blocks=5)
+    two = _is_model(eng, y, audio[:, :5 * 128], gate[:, :5], n_blocks=5)
+    assert one[0].tobytes() == two[0].tobytes() and one[1].tobytes() == two[1].tobytes() and 0 < len(one[0]) < gate.sum()
+    _is_model(eng, y, audio, gate)
+    a, r, needed = eng.pack_active(y, n_blocks=0)
+    assert needed == 0 and len(a) == 0 and len(r) == 0
+
+
+@pytest.mark.gpu
+def test_gpu_pack_on_the_sources_path(rdsp):
+    """two int16 sources at D = 4, twelve receivers on keyed stations, the squelch between their levels: the pack behind
+    update_sources equals the model on that call's audio and gates"""
+    nb, D = 12, 4
+    stations = -33000.0 + 6000.0 * np.arange(12)
+    source_of = [c % 2 for c in range(12)]
+    src = _on_sources(_bursts(27, 12, nb, quiet=(2, 3)), stations, source_of, D)
+    eng = _engine(12, nb)
+    eng.set_meter(1.0, 1.0)
+    eng.set_sources(2, source_of)
+    eng.set_source_decimation(D)
+    eng.tune(0, stations)
+    eng.update_sources(_cuda(src))
+    s = _between(eng.read_meter(nb)[0].cpu().numpy())
+    eng.reset()
+    eng.set_squelch(s.open_ms, s.close_ms, s.hang_blocks)
+    y = eng.update_sources(_cuda(src))
+    audio, gate = y.cpu().numpy()[..., 0], eng.read_meter(nb)[2].cpu().numpy()
+    assert 0 < gate.mean() < 1
+    a, _ = _is_model(eng, y, audio, gate)
+    assert a.any()
+
+
+@pytest.mark.gpu
+def test_gpu_pack_refusals(rdsp):
+    """RDSP_ERR_NOT_READY without the meter (the message names rdsp_engine_enable_meter); RDSP_ERR_INVALID for a NULL d_lr or
+    d_counts, n_blocks negative or above the last call's, a short out_stride, a capacity with a NULL buffer, a d_audio that is
+    not 16-byte aligned and a capacity above INT32_MAX: buffers and counts keep their sentinel.  No call yet: counts {0, 0}.
+    meter(), read_meter and active() return the same before and after a pack."""
+    import torch
+    x = _bursts(26, 5, 6)
+    e = _engine(5, 8, meter=False)
+    lib = e.lib
+    y = e.update(_cuda(x))
+    a = torch.full((40, 128), 77, dtype=torch.int16, device="cuda")
+    r = torch.full((40, 2), 77, dtype=torch.int32, device="cuda")
+    cnt = torch.full((2,), 77, dtype=torch.int32, device="cuda")
+    pa, pr, pc, py = a.data_ptr(), r.data_ptr(), cnt.data_ptr(), y.data_ptr()
+    assert pa % 16 == 0
+    assert lib.rdsp_engine_pack_active(e.h, py, 6 * 128, 6, pa, pr, 40, pc, None) == -4 and b"rdsp_engine_enable_meter" in lib.rdsp_last_error()
+    assert lib.rdsp_engine_pack_active(None, py, 6 * 128, 6, pa, pr, 40, pc, None) == -1
+    e.set_squelch(1e-4, 1e-5, 2)
+    e.enable_meter()
+    assert lib.rdsp_engine_pack_active(e.h, py, 6 * 128, 1, pa, pr, 40, pc, None) == -1   # the meter has seen no call yet
+    assert lib.rdsp_engine_pack_active(e.h, py, 6 * 128, 0, pa, pr, 40, pc, None) == 0
+    torch.cuda.synchronize()
+    assert cnt.tolist() == [0, 0]
+    cnt.fill_(77)
+    y = e.update(_cuda(x))
+    py = y.data_ptr()
+    before = (e.meter(), [v.cpu().numpy() for v in e.read_meter(6)], e.active()[0].cpu().numpy())
+    assert not before[1][2].all() and before[1][2].any()
+    for args in ((None, 6 * 128, 6, pa, pr, 40, pc), (py, 6 * 128, 6, pa, pr, 40, None), (py, 6 * 128, -1, pa, pr, 40, pc),
+                 (py, 6 * 128, 7, pa, pr, 40, pc), (py, 6 * 128 - 1, 6, pa, pr, 40, pc), (py, 6 * 128, 6, None, pr, 40, pc),
+                 (py, 6 * 128, 6, pa, None, 40, pc), (py, 6 * 128, 6, None, None, 1, pc), (py, 6 * 128, 6, pa + 8, pr, 39, pc),
+                 (py, 6 * 128, 6, pa + 2, pr, 39, pc), (py, 6 * 128, 6, pa, pr, 2 ** 31, pc), (py, 6 * 128, 6, pa + 8, None, 0, pc)):
+        assert lib.rdsp_engine_pack_active(e.h, *args, None) == -1, args
+        assert b"rdsp_engine_pack_active" in lib.rdsp_last_error()
+    torch.cuda.synchronize()
+    assert bool((a == 77).all()) and bool((r == 77).all()) and cnt.tolist() == [77, 77]   # no refused call wrote
+    audio, gate = y.cpu().numpy()[..., 0], before[1][2]
+    _is_model(e, y, audio, gate)
+    _is_model(e, y, audio, gate, capacity=2)
+    after = (e.meter(), [v.cpu().numpy() for v in e.read_meter(6)], e.active()[0].cpu().numpy())
+    assert np.array_equal(before[0].view(np.uint32), after[0].view(np.uint32)) and np.array_equal(before[2], after[2])
+    assert all(np.array_equal(v.view(np.uint8), w.view(np.uint8)) for v, w in zip(before[1], after[1]))
+    assert np.array_equal(y.cpu().numpy()[..., 0], audio)                                 # nor the caller's rows
