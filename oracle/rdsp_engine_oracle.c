@@ -263,6 +263,14 @@ orc_engine_t *orc_engine_create(const float *biquad_sets15x20, const float *hilb
   return e;
 }
 void orc_engine_destroy(orc_engine_t *e) { free(e); }
+/* a second receiver in the state of the first, settings included (the object holds no pointer into itself); no tap buffer */
+orc_engine_t *orc_engine_clone(const orc_engine_t *e) {
+  orc_engine_t *c = (orc_engine_t *)malloc(sizeof *c);
+  if (!c) return 0;
+  memcpy(c, e, sizeof *c);
+  c->tap = 0;
+  return c;
+}
 
 /* ---- table oscillator: cos and sin of a phase in [0, 2 pi) by linear interpolation in the 256-step table ------------ */
 static float table_sin(const orc_engine_t *e, float ph) {

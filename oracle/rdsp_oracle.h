@@ -243,6 +243,7 @@ typedef struct orc_engine orc_engine_t;
 float orc_newlib_expf(float x);
 orc_engine_t *orc_engine_create(const float *biquad_sets15x20, const float *hilbert64);
 void orc_engine_destroy(orc_engine_t *e);
+orc_engine_t *orc_engine_clone(const orc_engine_t *e);      /* a second receiver in the same state and settings */
 void orc_engine_update(orc_engine_t *e, const int16_t *i128, const int16_t *q128, int16_t *out128); /* image 0xe730 */
 float orc_engine_setDemodMode(orc_engine_t *e, int mode);   /* INO:139, CTL:337-407 */
 void orc_engine_setAudioFilter(orc_engine_t *e, int id);    /* INO:138, CTL:153-177 */

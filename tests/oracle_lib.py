@@ -73,7 +73,7 @@ def build(native=False, out_dir=None):
     portable build unless out_dir says otherwise)."""
     if not native:
         so = os.path.join(ORACLE_DIR, "liboracle.so")
-        srcs = [os.path.join(ORACLE_DIR, f) for f in ("rdsp_oracle.c", "rdsp_oracle.h", "Makefile")]
+        srcs = [os.path.join(ORACLE_DIR, f) for f in ("rdsp_oracle.c", "rdsp_engine_oracle.c", "rdsp_oracle.h", "Makefile")]
         # up to date: no child process (a GPU test session may already have initialised the device; tests/conftest.py
         # builds at session start for the same reason)
         if os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(f) for f in srcs):
@@ -315,6 +315,8 @@ def _bind_engine(lib):
     lib.orc_engine_create.restype = C.c_void_p
     lib.orc_engine_create.argtypes = [_F32P, _F32P]
     lib.orc_engine_destroy.argtypes = [C.c_void_p]
+    lib.orc_engine_clone.restype = C.c_void_p
+    lib.orc_engine_clone.argtypes = [C.c_void_p]
     lib.orc_engine_update.argtypes = [C.c_void_p, _I16P, _I16P, _I16P]
     lib.orc_engine_set_tap.argtypes = [C.c_void_p, _F32P]
     lib.orc_engine_setDemodMode.restype = C.c_float
@@ -346,10 +348,14 @@ def engine_tables():
 class OracleEngine:
     """orc_engine_t: one receiver; `sketch_setup` = INO:120-139"""
 
-    def __init__(self, sketch_setup=True, taps=False):
+    def __init__(self, sketch_setup=True, taps=False, like=None):
+        """like: another OracleEngine, whose state and settings the new one starts from (a copy; sketch_setup is not run)"""
         self.lib = _bind_engine(load())
-        bq, h = engine_tables()
-        self.e = self.lib.orc_engine_create(bq.ctypes.data_as(_F32P), h.ctypes.data_as(_F32P))
+        if like is None:
+            bq, h = engine_tables()
+            self.e = self.lib.orc_engine_create(bq.ctypes.data_as(_F32P), h.ctypes.data_as(_F32P))
+        else:
+            self.e, sketch_setup = self.lib.orc_engine_clone(like.e), False
         self.tapbuf = np.zeros((9, 2, 128), np.float32) if taps else None
         self.taps = {k: [] for k in ENGINE_TAPS}
         if taps:

@@ -654,3 +654,38 @@ def test_gpu_state_without_meter_words_zeroes_them(rdsp):
     assert not after[:4].any() and np.array_equal(after[4:], before[4:])
     assert np.array_equal(_tail(got, 4)[:4], _tail(bu, 4)) and not np.array_equal(_tail(got, 4)[:4], _tail(own, 4)[:4])
     assert not _tail(got, 4)[4:].any() and _tail(own, 4)[4:].any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", [7, 8, 9, 17])
+def test_gpu_meter_at_the_eight_block_steps(rdsp, nb):
+    """5 channels (a ragged workgroup of the meter's four) x 7, 8, 9 and 17 blocks in one call -- below, on and above the eight
+    blocks the meter kernel takes a step, and two steps and one block: levels, peaks and gates equal the restatement applied to
+    read_demod's rows, bit for bit, the gates open and close inside the call, and on output rows nb x 128 + 2 pairs apart that
+    start at an odd word a closed block is 128 zero words on both sides, an open one the meterless engine's"""
+    import torch
+    x = _bursts(70 + nb, 5, nb, quiet=(1, 2, 3))
+    plain = _Run(_engine(5, 17, meter=False), meter=False).play(x, nb).cat()
+    open_ms, close_ms = _thresholds(Meter(5).run(plain[1], Squelch(attack=0.5, decay=0.5))[0])
+    s = Squelch(open_ms, close_ms, 1, attack=0.5, decay=0.5)
+    m = Meter(5)
+    want_level, want_peak, want_gate = m.run(plain[1], s)
+    assert want_gate.any() and not want_gate.all()
+    eng = _engine(5, 17)
+    eng.set_meter(0.5, 0.5)
+    eng.set_squelch(open_ms, close_ms, 1)
+    stride = nb * 128 + 2
+    buf = torch.full((5 * stride + 1, 2), 7, dtype=torch.int16, device="cuda")
+    assert (buf.data_ptr() + 4) % 16 != 0
+    assert eng.lib.rdsp_engine_update(eng.h, torch.from_numpy(x).cuda().data_ptr(), nb * 128, nb, buf.data_ptr() + 4, stride, None) == 0
+    level, peak, gate = (v.cpu().numpy() for v in eng.read_meter(nb))
+    assert same_bits(eng.read_demod(nb).cpu().numpy(), plain[1])
+    assert same_bits(level, want_level) and same_bits(peak, want_peak) and np.array_equal(gate, want_gate)
+    assert same_bits(eng.meter(), m.scalars())
+    got = buf[1:].reshape(5, stride, 2).cpu().numpy()
+    assert np.all(got[:, nb * 128:] == 7) and np.all(buf[0].cpu().numpy() == 7)
+    assert np.array_equal(got[:, :nb * 128, 0], got[:, :nb * 128, 1]) and np.array_equal(got[:, :nb * 128, 0], M.gated(plain[0], want_gate))
+    a3 = got[:, :nb * 128, 0].reshape(5, nb, 128)
+    assert not a3[gate == 0].any() and a3[gate == 1].any() and plain[0].reshape(5, nb, 128)[gate == 0].any()
+    lst, cnt = eng.active()
+    assert cnt == len(lst) and np.array_equal(lst.cpu().numpy(), np.flatnonzero(want_gate.any(1)))

@@ -483,3 +483,145 @@ def test_gpu_pack_refusals(rdsp):
     assert np.array_equal(before[0].view(np.uint32), after[0].view(np.uint32)) and np.array_equal(before[2], after[2])
     assert all(np.array_equal(v.view(np.uint8), w.view(np.uint8)) for v, w in zip(before[1], after[1]))
     assert np.array_equal(y.cpu().numpy()[..., 0], audio)                                 # nor the caller's rows
+
+
+# ---- the boundaries of the ordered scans (chunks of 1024 channels) and of the 64-block ballot trips -------------------------
+def _kinds_engine(n, max_blocks, first, kinds, s):
+    """_grouped, and per channel the kind of its group"""
+    ends = first[1:] + [n]
+    return _grouped(n, max_blocks, first, kinds, s), np.concatenate([[k] * (e - f) for k, f, e in zip(kinds, first, ends)])
+
+
+# per channel count: the groups (first channels, kinds) that put the patterns of the docstring below onto the chunk boundary
+CHUNK_PATTERNS = {1023: [([0], ["bursts"]), ([0], ["open"]), ([0], ["closed"]), ([0, 1022], ["closed", "open"]), ([0, 1], ["open", "closed"])],
+                  1024: [([0], ["open"]), ([0], ["closed"]), ([0, 1023], ["bursts", "open"]), ([0, 1023], ["open", "closed"]), ([0, 1], ["closed", "bursts"])],
+                  1025: [([0, 1023, 1024], ["bursts", "open", "closed"]), ([0, 1023, 1024], ["bursts", "closed", "open"]),
+                         ([0, 1024], ["closed", "open"]), ([0, 1024], ["open", "closed"]), ([0, 1024], ["open", "bursts"])],
+                  2049: [([0, 1024, 2048], ["closed", "open", "open"]), ([0, 1024, 2048], ["open", "closed", "open"]),
+                         ([0, 1023, 1025, 2047], ["bursts", "open", "bursts", "closed"]), ([0, 2048], ["closed", "open"])]}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2049])
+def test_gpu_pack_and_active_list_at_the_scan_chunks(rdsp, n):
+    """1023, 1024, 1025 and 2049 channels x 2 blocks: the ordered scans of rdsp_engine_active_kernel and
+    rdsp_engine_pack_scan_kernel walk the channels in chunks of 1024.  Groups cut at 1023 / 1024 / 1025 are open, closed
+    (set_squelch(NEVER, NEVER, 0)) or keyed bursts, so that -- asserted on the gates read back -- the last channel of chunk 0 is
+    open with the first of chunk 1 closed and the reverse, a chunk has no open channel, a chunk has all channels open, and at
+    2049 channels a lone open last channel stands behind two full chunks of closed ones.  The active list is numpy's, the pack
+    the model's, exactly; then the pack again from rows overwritten with the L != R pattern"""
+    base = _bursts(60, 48, 2, quiet=(1, 2, 3))
+    x = np.tile(base, (-(-n // len(base)), 1, 1))[:n]
+    probe = _engine(n, 2)
+    probe.set_meter(1.0, 1.0)
+    probe.update(_cuda(x))
+    s = _between(probe.read_meter(2)[0].cpu().numpy())
+    probe.close()
+    seen = set()
+    for first, kinds in CHUNK_PATTERNS[n]:
+        eng, kind = _kinds_engine(n, 2, first, kinds, s)
+        y, audio, gate = _call(eng, x)
+        is_open = gate.any(1)
+        assert is_open[kind == "open"].all() and gate[kind == "open"].all() and not is_open[kind == "closed"].any(), (first, kinds)
+        if (kind == "bursts").sum() >= 48:
+            assert is_open[kind == "bursts"].any() and not gate[kind == "bursts"].all(), (first, kinds)
+        lst, cnt = eng.active()
+        assert cnt == int(is_open.sum()) and np.array_equal(lst.cpu().numpy(), np.flatnonzero(is_open)), (first, kinds)
+        _is_model(eng, y, audio, gate)
+        _is_model(eng, y, audio, gate, capacity=int(gate[:min(n, 1024)].sum()) + 1)     # ends with the first block of chunk 1's channels, if any
+        pat = _pattern(n, 2 * 128)
+        y.copy_(_cuda(pat))
+        _is_model(eng, y, pat[..., 0], gate)
+        chunks = [is_open[a:a + 1024] for a in range(0, n, 1024)]
+        if n > 1024:
+            seen |= {"last_open_first_closed"} if is_open[1023] and not is_open[1024] else set()
+            seen |= {"last_closed_first_open"} if not is_open[1023] and is_open[1024] else set()
+        seen |= {"chunk_without"} if any(not c.any() for c in chunks) else set()
+        seen |= {"chunk_all"} if any(c.all() for c in chunks) else set()
+        if n == 2049 and is_open[2048] and not is_open[:2048].any():
+            seen.add("lone_last")
+        eng.close()
+    want = {"chunk_without", "chunk_all"} | ({"last_open_first_closed", "last_closed_first_open"} if n > 1024 else set()) | ({"lone_last"} if n == 2049 else set())
+    assert seen >= want, want - seen
+
+
+def _keyed(seed, loud):
+    """_bursts with the keying given: int16 [n, nb * 128, 2], channel c loud in the blocks where loud[c] is set"""
+    r = np.random.default_rng(seed)
+    n, nb = loud.shape
+    t = np.arange(nb * 128)
+    x = np.zeros((n, nb * 128, 2), np.int16)
+    for c in range(n):
+        amp = np.where(loud[c], r.uniform(0.1, 0.4, nb), 0.0005)
+        z = np.repeat(amp, 128) * np.exp(2j * np.pi * r.uniform(6200, 7800) / 44100.0 * t + 1j * r.uniform(0, 6))
+        z += 0.0003 * (r.standard_normal(len(t)) + 1j * r.standard_normal(len(t)))
+        x[c, :, 0], x[c, :, 1] = np.round(z.real * 32767), np.round(z.imag * 32767)
+    return x
+
+
+def _trip_keying(nb=129):
+    """five channels: 0 loud across blocks 59 ... 65 (the end of the first 64-block trip and the start of the second) and silent
+    elsewhere; 1 loud for 40 blocks and again for 20 in the second trip; 2 loud for 6 blocks (8 open ones under _between's squelch:
+    exactly a gather step) and for 3 in the second trip; 3 and 4 keyed in drawn bursts"""
+    r = np.random.default_rng(5)
+    loud = np.zeros((5, nb), bool)
+    loud[0, 59:66] = True
+    loud[1, 0:40] = True
+    loud[1, 70:90] = True
+    loud[2, 10:16] = True
+    loud[2, 100:103] = True
+    for c in (3, 4):
+        b = int(r.integers(0, 4))
+        while b < nb:
+            k = int(r.integers(2, 6))
+            loud[c, b:b + k] = True
+            b += k + int(r.choice([1, 2, 3]))
+    return loud
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", [63, 64, 65, 129])
+def test_gpu_pack_at_the_ballot_trips(rdsp, nb):
+    """5 channels x 63, 64, 65 and 129 blocks of an engine with max_blocks_per_call 130, meter coefficients 1 and 1, _between's
+    squelch on keyed tones (_trip_keying): the count and the gather kernel read a channel's gates 64 blocks a trip, the gather
+    stores eight blocks a step.  Asserted on the gates read back: from 65 blocks on a channel has blocks 63 and 64 open; some
+    trip holds exactly 8 open blocks, some more, some fewer.  The pack is the model's for every capacity that ends at a channel's
+    first block, on a multiple of 8 inside a channel, one behind that, and inside a channel's second trip -- the sentinels
+    behind `written` stay -- and again from rows overwritten with the L != R pattern"""
+    import torch
+    x = _keyed(44, _trip_keying())[:, :nb * 128]
+    probe = _engine(5, 130)
+    probe.set_meter(1.0, 1.0)
+    probe.update(_cuda(x))
+    s = _between(probe.read_meter(nb)[0].cpu().numpy())
+    probe.close()
+    eng = _grouped(5, 130, [0], ["bursts"], s)
+    y, audio, gate = _call(eng, x)
+    trips = np.array([[int(gate[c, a:a + 64].sum()) for a in range(0, nb, 64)] for c in range(5)])
+    assert (trips == 8).any() and (trips > 8).any() and ((trips > 0) & (trips < 8)).any(), trips
+    if nb > 64:
+        assert (gate[:, 63] & gate[:, 64]).any()
+    blocks, rec, needed = P.pack(audio, gate)
+    offset = np.concatenate([[0], np.cumsum(gate.sum(1))])              # the index of every channel's first packed block
+    caps = {int(offset[c]) + 1 for c in range(1, 5) if gate[c].any()}                   # ends at a channel's first block
+    deep = [c for c in range(5) if gate[c].sum() > 9]
+    caps |= {int(offset[c]) + 8 for c in deep} | {int(offset[c]) + 9 for c in deep}     # a whole gather step inside a channel, and one block more
+    second = [c for c in range(5) if nb > 64 and gate[c, 64:128].any()]
+    caps |= {int(offset[c]) + int(gate[c, :64].sum()) + 1 + (int(gate[c, 64:128].sum()) > 2) for c in second}   # inside the second trip
+    assert len(caps) >= 4 and (nb <= 64 or second) and max(caps) <= needed and min(caps) < needed
+    pat = _pattern(5, nb * 128)
+    for rows, left in ((None, audio), (pat, pat[..., 0])):
+        if rows is not None:
+            y.copy_(_cuda(rows))
+        want_blocks = P.pack(left, gate)[0]
+        _is_model(eng, y, left, gate)
+        for cap in sorted(caps):
+            a = torch.full((needed + 8, 128), -21846, dtype=torch.int16, device="cuda")
+            r = torch.full((needed + 8, 2), -7, dtype=torch.int32, device="cuda")
+            cnt = torch.full((2,), -7, dtype=torch.int32, device="cuda")
+            assert eng.lib.rdsp_engine_pack_active(eng.h, y.data_ptr(), nb * 128, nb, a.data_ptr(), r.data_ptr(), cap, cnt.data_ptr(), None) == 0
+            torch.cuda.synchronize()
+            assert cnt.tolist() == [needed, cap], cap
+            a, r = a.cpu().numpy(), r.cpu().numpy()
+            assert np.array_equal(a[:cap], want_blocks[:cap]) and np.array_equal(r[:cap], rec[:cap]), cap
+            assert np.all(a[cap:] == -21846) and np.all(r[cap:] == -7), cap
