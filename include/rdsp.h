@@ -836,7 +836,8 @@ const float *rdsp_engine_tune_table(void);
  *   128 x D pairs (src_stride at least that); d_lr, out_stride and max_blocks count 44 100 Hz samples as before.
  * - Refused with nothing changed (RDSP_ERR_INVALID): D outside 1 ... 64, gain not above 0 or not finite, a channel already
  *   tuned to |f| >= D x 22 050.
- * - Out of scope: decimation in several stages. */
+ * - Decimation in several stages is not this pass's business: rdsp_channelizer_t (below) is a first stage shared by all
+ *   receivers of a source, and its sub-band rows are sources of this pass at a small D. */
 int rdsp_engine_set_source_decimation(rdsp_engine_t *e, int D, float gain);
 int rdsp_engine_source_decimation(const rdsp_engine_t *e);
 int rdsp_engine_ddc_taps(int D, float gain, float *out /* [16 D] */);
@@ -912,6 +913,80 @@ int rdsp_engine_set_source_format(rdsp_engine_t *e, int format);
 int rdsp_engine_source_format(const rdsp_engine_t *e);
 int rdsp_engine_update_source_samples(rdsp_engine_t *e, const void *d_src, size_t src_stride /* pairs */, int n_blocks,
                                       int16_t *d_lr, size_t out_stride, void *stream);
+/* ---- channelizer: a wide source split once into sub-bands that all its receivers share --------------------------------------
+ * The passes above do all of a receiver's down-conversion per receiver: 64 Dc FMAs per output sample, Dc = ceil(P / Q), and
+ * the same coarse filtering again for every receiver of a source.  rdsp_channelizer_t does the coarse part once per SOURCE: a
+ * polyphase channelizer splits the band into M overlapping sub-bands at D2 x 44 100 Hz, float rows on the device, and every
+ * receiver listens to the sub-band nearest its station through the engine's decimating pass at D = D2.  An object of its
+ * own, as rdsp_survey_t is (several engines may share one band); the engine does not know it.  A receiver is set up with the
+ * calls above: rdsp_channelizer_place(P, Q, M, station) -> subband, residual; rdsp_engine_set_sources(n_sources M, src M +
+ * subband); rdsp_engine_set_source_decimation(D2, gain); rdsp_engine_set_source_format(RDSP_SRC_F32);
+ * rdsp_engine_tune(residual); rdsp_engine_update_source_samples(d_sub, sub_stride, n_blocks, ...).
+ *
+ * Rates.  fs = 44100 P / Q; sub-band spacing fs / M, M one of 8, 16, 32, 64; sub-band rate fo = 44100 D2, D2 an integer 2 ... 64;
+ * P1 / Q1 = P / (Q D2) in lowest terms (rdsp_channelizer_rate).  Accepted when P / Q passes the rule of
+ * rdsp_engine_set_source_rate, P1 >= Q1, Q1 <= 441 and
+ *     fs / (2 M) + 12000 <= 12000 D2.
+ * The last condition is no tuning knob: a station anywhere in the band lies within half a spacing of a sub-band centre, so the
+ * +-12 kHz around it lie within fs / (2 M) + 12000 of that centre -- inside the prototype's flat band |f| <= 12000 D2 -- and all
+ * that aliases onto them at the rate fo lies at 44100 D2 - 12000 D2 = 32100 D2 or above, in its stop band.  Everything else is
+ * refused (RDSP_ERR_INVALID, nothing changed): 8000 / 147 with M = 32, D2 = 4; 2500 / 441 with M = 8, D2 = 2; 10240 / 441 with D2 =
+ * 3 (Q1 = 1323).
+ *
+ * Prototype (rdsp_channelizer_taps, host only): the taps of rdsp_engine_rate_taps(P1, Q1, 1.0) times 2^-15 (exact), so that
+ * sub-band rows are full scale +-1.0, what RDSP_SRC_F32 expects: the same Kaiser-windowed sinc as both passes above, its
+ * cutoff at the sub-band rate's Nyquist frequency.  Dc1 = ceil(P1 / Q1), Tb = 16 Dc1, branch r is hb[r][j] = out[j Q1 + r].  Over
+ * the configurations of tests/test_channelizer.py (and times 2^15): ripple <= 0.001 dB on |f| <= 12000 D2, >= 89 dB down from
+ * 32100 D2 to the prototype's Nyquist frequency, sum_j |hb[r][j]| <= 2.5.
+ *
+ * Schedule: the polyphase pass's with P1, Q1.  frac starts at 0; a call of n_out = n_blocks x 128 x D2 outputs per sub-band
+ * consumes (frac + n_out P1) div Q1 pairs of every source row (rdsp_channelizer_source_pairs for the NEXT call), then frac <-
+ * (frac + n_out P1) mod Q1.  Output i has its newest pair at local index n(i) = (frac + (i + 1) P1) div Q1 - 1 and uses branch
+ * r(i) = (frac + (i + 1) P1) mod Q1 (64-bit products).  The object also keeps T mod M, T the pairs consumed since the reset.
+ *
+ * Arithmetic of output i, sub-band k; x the source VALUES (the table of the engine's source formats, counts) with the pairs
+ * of earlier calls in front and zeros before the stream; N = T + n(i) the absolute index of the newest pair:
+ *     fold:  v[q] = 0 for q = 0 ... M - 1;  for j = 0 ... Tb - 1 ascending, q = (N - j) mod M:
+ *                vI[q] = fmaf(hb[r][j], xI[n - j], vI[q]);  vQ[q] = fmaf(hb[r][j], xQ[n - j], vQ[q])
+ *     DFT:   re = im = 0;  for q = 0 ... M - 1 ascending, (c, s) = twiddles[(k q) mod M]:
+ *                re = fmaf(c, vI[q], re);  re = fmaf(s, vQ[q], re);  im = fmaf(c, vQ[q], im);  im = fmaf(-s, vI[q], im)
+ * twiddles[m] = (cos, sin)(2 pi m / M), evaluated in double and rounded to float, exactly 0 and +-1 at quarter turns and
+ * symmetric between octants (rdsp_channelizer_twiddles; the kernel uses exactly these values).  This is mixing by
+ * e^{-j 2 pi k m / M} at the source's sample times, then low-passing and resampling; positive frequency is I + jQ.  Row
+ * src M + k of d_sub is sub-band k of source src; its centre lies ((k + M / 2) mod M - M / 2) fs / M Hz from the band centre.
+ * The order has no tile, lane or call size in it: a stream gives the SAME BITS however it is cut into calls, and
+ * tests/channelizer_model.py restates it in numpy bit for bit.  (A direct DFT, M^2 complex MACs an instant, for that reason.)
+ *
+ * State: per source the last Tb pairs as float2 values in every format, frac and T mod M; zero at create and after
+ * rdsp_channelizer_reset.  Nothing of it is in any engine blob.
+ *
+ * Rules: source rows aligned to one pair of their format, src_stride >= source_pairs(n_blocks); d_sub 16-byte aligned, float2
+ * [n_sources M][sub_stride], sub_stride (pairs) even and at least n_blocks x 128 x D2 -- the rows then satisfy the engine's
+ * rule for RDSP_SRC_F32 rows at an integer rate; n_blocks <= max_blocks_per_call (at most 4096); 1 ... 4096 sources.  Everything
+ * is launched on the caller's stream; update does not synchronise.  Every refusal leaves the object unchanged and sets
+ * rdsp_last_error.
+ *
+ * rdsp_channelizer_place (host, double): spacing = fs / M; kk = station / spacing rounded half away from zero; subband =
+ * kk mod M, non-negative; residual = station - kk spacing, so |residual| <= spacing / 2.  Refused for |station| >= fs / 2 or NaN. */
+typedef struct rdsp_channelizer rdsp_channelizer_t;
+int rdsp_channelizer_create(int n_sources, int device, int P, int Q, int M, int D2, int format /* RDSP_SRC_* */,
+                            int max_blocks_per_call, rdsp_channelizer_t **out);
+void rdsp_channelizer_destroy(rdsp_channelizer_t *c);
+int rdsp_channelizer_reset(rdsp_channelizer_t *c, void *stream);   /* histories, frac and T mod M zero */
+size_t rdsp_channelizer_source_pairs(const rdsp_channelizer_t *c, int n_blocks); /* pairs the NEXT update consumes */
+int rdsp_channelizer_update(rdsp_channelizer_t *c, const void *d_src, size_t src_stride /* pairs */, int n_blocks,
+                            float *d_sub /* float2 [n_sources * M][sub_stride] */, size_t sub_stride /* pairs */, void *stream);
+int rdsp_channelizer_sources(const rdsp_channelizer_t *c);
+int rdsp_channelizer_subbands(const rdsp_channelizer_t *c);        /* M */
+int rdsp_channelizer_decimation(const rdsp_channelizer_t *c);      /* D2 */
+int rdsp_channelizer_source_rate(const rdsp_channelizer_t *c, int *P, int *Q); /* in lowest terms */
+int rdsp_channelizer_format(const rdsp_channelizer_t *c);
+int rdsp_channelizer_device(const rdsp_channelizer_t *c);
+/* host only, no device */
+int rdsp_channelizer_rate(int P, int Q, int D2, int *P1, int *Q1);   /* P / (Q D2) in lowest terms, or refused */
+int rdsp_channelizer_taps(int P, int Q, int D2, float *out /* [16 ceil(P1 / Q1) Q1] */);
+int rdsp_channelizer_twiddles(int M, float *out /* [M][2] */);
+int rdsp_channelizer_place(int P, int Q, int M, double station_hz, int *subband, double *residual_hz);
 /* Signal meter, squelch and active-receiver list.  The engine writes audio for every receiver on every call; the meter says
  * which receivers hear something.  Off until rdsp_engine_enable_meter: an engine that never calls it allocates, launches,
  * returns and saves exactly what it did before the meter existed.  Everything runs on the device inside rdsp_engine_update,

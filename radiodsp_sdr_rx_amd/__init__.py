@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == "Survey":
         from . import survey
         return survey.Survey
+    if name == "Channelizer":
+        from . import channelizer
+        return channelizer.Channelizer
     raise AttributeError(name)

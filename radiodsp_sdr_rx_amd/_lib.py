@@ -353,6 +353,21 @@ SYMBOLS = [
     ("rdsp_survey_rows_between", _i, [_i, _i, C.c_uint64, _sz]),
     ("rdsp_survey_bin_hz", _d, [_i, _i, _i, _i]),
     ("rdsp_survey_find_stations", _i, [_f32p, _i, _i, _i, _d, _d, _i, _f64p, _f32p]),
+    ("rdsp_channelizer_create", _i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    ("rdsp_channelizer_destroy", None, [_vp]),
+    ("rdsp_channelizer_reset", _i, [_vp, _vp]),
+    ("rdsp_channelizer_source_pairs", _sz, [_vp, _i]),
+    ("rdsp_channelizer_update", _i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    ("rdsp_channelizer_sources", _i, [_vp]),
+    ("rdsp_channelizer_subbands", _i, [_vp]),
+    ("rdsp_channelizer_decimation", _i, [_vp]),
+    ("rdsp_channelizer_source_rate", _i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("rdsp_channelizer_format", _i, [_vp]),
+    ("rdsp_channelizer_device", _i, [_vp]),
+    ("rdsp_channelizer_rate", _i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("rdsp_channelizer_taps", _i, [_i, _i, _i, _f32p]),
+    ("rdsp_channelizer_twiddles", _i, [_i, _f32p]),
+    ("rdsp_channelizer_place", _i, [_i, _i, _i, _d, C.POINTER(C.c_int), _f64p]),
     ("rdsp_synth_iq", None, [_i16p, _i, _i, C.c_uint64, _i, C.POINTER(SynthConfig), _i]),
 ]
 
