@@ -1,7 +1,8 @@
 """rdsp_channelizer_t (include/rdsp.h "channelizer") restated in numpy, for tests/test_channelizer.py and
 tests/test_channelizer_gpu.py: the rate, the prototype, the twiddles, the placement, and the arithmetic of a call operation for
 operation (fold, then direct DFT, every fused operation an exact float32 fma) beside a float64 evaluation of the same
-definition.  The float32 fma, the table of values and the prototype's design are tests/engine_sources_model.py's."""
+definition.  The float32 fma, the table of values and the prototype's design are tests/engine_sources_model.py's.  CONFIGS are
+the six configurations of the tests, EDGE the accepted ones at the edges they do not reach."""
 import math
 
 import numpy as np
@@ -10,6 +11,16 @@ from engine_sources_model import F32, fma32, taps_of, values
 
 CONFIGS = [(16, 1, 16, 4), (16, 1, 16, 3), (640, 147, 8, 2), (8000, 147, 32, 5), (8000, 147, 64, 3), (20480, 441, 32, 4)]
 REFUSED = [(8000, 147, 32, 4), (2500, 441, 8, 2), (10240, 441, 32, 3)]
+# the edges CONFIGS does not reach, each accepted; EDGE_FACTS has per entry Tb, T mod M after 1, 2 and 3 blocks, and why it is here
+EDGE = [(320, 147, 16, 2), (640, 147, 16, 3), (2, 1, 8, 2), (4, 1, 64, 4), (4, 1, 32, 2), (64, 1, 64, 3), (1536, 49, 64, 2), (64, 1, 8, 16)]
+EDGE_FACTS = [(32, (6, 13, 3), "M = 16 with T mod M != 0"),
+              (32, (13, 10, 7), "M = 16 with T mod M != 0, Q1 = 441"),
+              (16, (0, 0, 0), "P1 = Q1: no rate change, Tb = 2 M"),
+              (16, (0, 0, 0), "Tb < M: the waves 1 to 3 fold nothing"),
+              (32, (0, 0, 0), "Tb = M: one tap a chain"),
+              (352, (0, 0, 0), "the top rate and the largest LDS plan"),
+              (256, (44, 24, 5), "M = 64 at D2 = 2, T mod M != 0"),
+              (64, (0, 0, 0), "D2 = 16")]
 
 
 def rate(P, Q, D2):
@@ -89,20 +100,26 @@ class Model:
     def source_pairs(self, n_blocks):
         return (self.frac + n_blocks * 128 * self.D2 * self.P1) // self.Q1
 
-    def _schedule(self, n_out):
-        t = self.frac + (np.arange(n_out, dtype=np.int64) + 1) * self.P1
+    def _schedule(self, i):
+        """(n, r) of the output instants i of the next call, in 64 bits"""
+        t = self.frac + (np.asarray(i, np.int64) + 1) * self.P1
         return t // self.Q1 - 1, t % self.Q1
 
-    def call(self, vals, n_blocks, exact=False, ks=None):
+    def call(self, vals, n_blocks, exact=False, ks=None, at=None):
         """vals: float32 VALUES [S, >= source_pairs(n_blocks), 2] -> float32 [S M, n_out, 2]; with exact, instead (float64
         evaluation of the definition [S M, n_out, 2], the bound's A [S, n_out]) and the state does not advance; with ks, only
-        those sub-bands of every source: [S len(ks), n_out, 2]"""
-        n_out, M, Tb = n_blocks * 128 * self.D2, self.M, self.Tb
+        those sub-bands of every source: [S len(ks), n_out, 2]; with at (an index array of output instants of this call), only
+        those instants are evaluated, [S M, len(at), 2], and the state advances as for the whole call"""
+        n_call, M, Tb = n_blocks * 128 * self.D2, self.M, self.Tb
         pairs = self.source_pairs(n_blocks)
         assert vals.dtype == F32 and vals.shape[0] == self.S and vals.shape[1] >= pairs
         xh = np.concatenate([self.hist, vals[:, :pairs]], 1)
-        n, r = self._schedule(n_out)
-        assert n[0] >= 0 and n[-1] == pairs - 1
+        ends = self._schedule([0, n_call - 1])[0]
+        assert ends[0] >= 0 and ends[1] == pairs - 1
+        inst = np.arange(n_call, dtype=np.int64) if at is None else np.asarray(at, np.int64)
+        assert inst.ndim == 1 and (inst.size == 0 or (inst.min() >= 0 and inst.max() < n_call))
+        n, r = self._schedule(inst)
+        n_out = inst.size                                          # the instants evaluated
         N = self.T + n
         ar = np.arange(n_out)
         if exact:
@@ -136,7 +153,7 @@ class Model:
             im = fma32(c, b, im)
             im = fma32(-s, a, im)
         self.hist = xh[:, pairs:pairs + Tb].copy()
-        self.frac = (self.frac + n_out * self.P1) % self.Q1
+        self.frac = (self.frac + n_call * self.P1) % self.Q1
         self.T += pairs
         return np.stack([re, im], -1).reshape(self.S * len(k), n_out, 2)
 

@@ -75,12 +75,15 @@ def fmaf(a, b, c):
 def fma32(a, b, c):
     """fmaf, with a short cut: a b is exact in double, so rounding the double sum a b + c to float32 differs from rounding
     the exact sum only if the double sum sits on a midpoint between two float32 (the low 29 bits of its mantissa are
-    1 << 28) -- no such element, no double rounding, and the 6-operation path is fmaf's answer.  (The values here are sums
-    of products of float32 taps above 1e-12 with integers, far above float32's subnormals, where the midpoints sit
-    elsewhere.)"""
+    1 << 28) -- no such element, no double rounding, and the 6-operation path is fmaf's answer.  That places the midpoints
+    of normal float32 only: below 2^-126 float32's spacing stays 2^-149 and its midpoints sit at other bits of the double.
+    So whenever a double sum is non-zero and below 2^-125 in magnitude the call is fmaf's as well, which is exact there too
+    (tests/test_channelizer.py holds both to rational arithmetic).  A double sum of exactly 0 is exact -- a b + c of float32
+    cannot underflow in double -- and takes the short cut: fresh histories are all zeros."""
     a, b, c = (np.asarray(v, F32) for v in (a, b, c))
     s = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)
-    if np.any((s.view(np.uint64) & np.uint64(0x1FFFFFFF)) == np.uint64(0x10000000)):
+    mag = np.abs(s)
+    if np.any((s.view(np.uint64) & np.uint64(0x1FFFFFFF)) == np.uint64(0x10000000)) or np.any((mag < 2.0 ** -125) & (mag > 0.0)):
         return fmaf(a, b, c)
     return s.astype(F32)
 

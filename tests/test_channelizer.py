@@ -7,7 +7,9 @@ tests/host/host_channelizer_check.cpp, a program of its own, plain and under the
 The bound of test_model_against_float64: every fold chain has at most ceil(Tb / M) fmaf, the DFT chain of a component 2 M, and
 each twiddle carries one rounding: (ceil(Tb / M) + 2 M + 1) 2^-24 A to first order, A = sum_j |hb[r][j]| (|xI| + |xQ|) (every
 twiddle is at most 1 in magnitude, so A bounds the sum of the magnitudes of either chain's terms); the issue's constant has
-+ 2, which leaves room for the second-order terms.  Worst observed fraction of it: 0.07 (printed)."""
++ 2, which leaves room for the second-order terms.  Worst observed fraction of it: 0.07 on the six configurations, 0.13 on the
+edges of CM.EDGE (printed).  The model's own parts have tests here too: the EDGE list's facts, Model.call's at=, and fma32 and
+fmaf against rational arithmetic where results are subnormal."""
 import math
 import os
 import subprocess
@@ -129,10 +131,11 @@ def _rails(rng, S, pairs):
     return x
 
 
-@pytest.mark.parametrize("cfg", CM.CONFIGS)
+@pytest.mark.parametrize("cfg", CM.CONFIGS + CM.EDGE)
 def test_model_against_float64(cfg):
     """every output of the float32 restatement lies within (ceil(Tb / M) + 2 M + 2) 2^-24 A of the float64 evaluation (the
-    module's docstring has the derivation), on full-scale noise with rows on the rails, over two calls"""
+    module's docstring has the derivation), on full-scale noise with rows on the rails, over two calls; the six configurations
+    and the edges of CM.EDGE"""
     P, Q, M, D2 = cfg
     m = CM.Model(2, P, Q, M, D2)
     rng = np.random.default_rng(5)
@@ -147,6 +150,101 @@ def test_model_against_float64(cfg):
         worst = max(worst, float(frac.max()))
         assert np.all(np.abs(got - want) <= bound), (cfg, float(frac.max()))
     print(f"{cfg}: worst fraction of the bound {worst:.4f}")
+
+
+def test_edge_list_keeps_its_purpose():
+    """CM.EDGE beside CM.EDGE_FACTS: every entry is accepted and new, has the Tb and the T mod M after 1, 2 and 3 blocks that the
+    list states, and the list still holds what it was made for: M = 16 with T mod M != 0 (one entry at Q1 = 441), P1 = Q1,
+    Tb < M, Tb = M, the top rate with the largest tile the GPU tests stage, M = 64 at D2 = 2, and D2 = 16"""
+    assert len(CM.EDGE) == len(CM.EDGE_FACTS) == len(set(CM.EDGE)) and not set(CM.EDGE) & set(CM.CONFIGS)
+    seen = {}
+    for cfg, (Tb, tmods, why) in zip(CM.EDGE, CM.EDGE_FACTS):
+        P, Q, M, D2 = cfg
+        assert CM.accepted(*cfg), cfg
+        m = CM.Model(1, *cfg)
+        got = tuple(m.source_pairs(nb) % M for nb in (1, 2, 3))
+        print(f"{cfg}: P1 / Q1 = {m.P1} / {m.Q1}, Tb = {m.Tb}, T mod M after 1, 2, 3 blocks {got}: {why}")
+        assert m.Tb == Tb and got == tmods, (cfg, m.Tb, got)
+        seen[cfg] = (m, got)
+    m16 = [c for c in CM.EDGE if c[2] == 16 and all(seen[c][1])]
+    assert len(m16) >= 2 and any(seen[c][0].Q1 == 441 for c in m16)
+    assert any(m.P1 == m.Q1 for m, _ in seen.values())
+    assert any(m.Tb < m.M and m.M == 64 for m, _ in seen.values()) and any(m.Tb == m.M for m, _ in seen.values())
+    assert any(c[0] == 64 * c[1] and c[2] == 64 for c in CM.EDGE)
+    assert any(c[2] == 64 and c[3] == 2 and all(seen[c][1]) for c in CM.EDGE) and max(c[3] for c in CM.EDGE) == 16
+
+    def tile(c):                                            # the kernel's LDS plan in bytes: (M 64 + 79 Dc1) float2
+        P1, Q1 = CM.rate(c[0], c[1], c[3])
+        return (c[2] * 64 + 79 * -(-P1 // Q1)) * 8
+
+    assert max(map(tile, CM.EDGE)) == tile((64, 1, 64, 3)) == 46672 > max(map(tile, CM.CONFIGS))
+
+
+def test_call_at():
+    """Model.call(..., at=idx) gives the columns idx of the whole call, bit for bit, and leaves the state the whole call leaves:
+    the next call's rows are the same either way.  (640, 147, 8, 2): frac and T mod M are non-zero after the first call"""
+    cfg = (640, 147, 8, 2)
+    a, b = CM.Model(2, *cfg), CM.Model(2, *cfg)
+    rng = np.random.default_rng(11)
+    vals = values(S16, _rails(rng, 2, a.source_pairs(3)))
+    idx = np.concatenate([[0, 1, 63, 64, 255, 256, 2 * 256 - 1], rng.integers(0, 2 * 256, 40)])
+    p2 = a.source_pairs(2)
+    whole = a.call(vals[:, :p2], 2)
+    some = b.call(vals[:, :p2], 2, at=idx)
+    assert some.shape == (2 * 8, len(idx), 2) and np.array_equal(_bits(some), _bits(whole[:, idx]))
+    assert (a.frac, a.T) == (b.frac, b.T) and a.frac != 0 and a.T % 8 != 0 and np.array_equal(_bits(a.hist), _bits(b.hist))
+    assert b.call(vals[:, :p2], 0, at=[]).shape == (16, 0, 2) and (a.frac, a.T) == (b.frac, b.T)
+    p1 = a.source_pairs(1)
+    assert np.array_equal(_bits(a.call(vals[:, p2:p2 + p1], 1)), _bits(b.call(vals[:, p2:p2 + p1], 1)))
+
+
+def _round_f32(x):
+    """a Fraction rounded to the nearest float32, ties to even, subnormals included (no overflow here)"""
+    from fractions import Fraction
+    if x == 0:
+        return F32(0.0)
+    e = -126
+    while abs(x) >= Fraction(2) ** (e + 1):
+        e += 1
+    quantum = Fraction(2) ** (e - 23)                       # float32's spacing at |x|; 2^-149 below 2^-125
+    q = x / quantum
+    n = q.numerator // q.denominator
+    rem = q - n
+    if rem > Fraction(1, 2) or (rem == Fraction(1, 2) and n % 2 == 1):
+        n += 1
+    return F32(float(n * quantum))                          # n quantum has at most 25 bits: exact in double, exact or 2^e+1 in float32
+
+
+def test_fma32_where_results_are_subnormal():
+    """fma32 and fmaf against a b + c in rational arithmetic, rounded once: 480 triples whose results are subnormal (drawn),
+    lie on a midpoint of the subnormal grid or 2^-196 beside one (where the double sum lands ON the midpoint and only the
+    TwoSum error says which side), or lie just above 2^-126 up to 2^-124; taken as one array and one by one (above 2^-125 a
+    lone triple takes fma32's short cut)"""
+    from fractions import Fraction
+    from engine_sources_model import fma32, fmaf
+    r = np.random.default_rng(17)
+    u = lambda e: F32(2.0 ** e)
+    trip = []
+    for lo, hi in ((0, 1 << 10), (1 << 18, 1 << 23), (1 << 23, 1 << 24), (1 << 24, 1 << 25)):      # c = +-k 2^-149 (k even above 2^24)
+        for _ in range(24):
+            k = int(r.integers(lo, hi))
+            k -= k % 2 if k >= 1 << 24 else 0
+            c = F32(float(k) * 2.0 ** -149) * F32(r.choice([-1.0, 1.0]))
+            for a, b in ((u(-100), F32(r.choice([1.0, 3.0, -1.0, -3.0])) * u(-50)),                  # a b = +-j 2^-150: half a step
+                         (u(-75) * F32(1 + 2.0 ** -23), u(-75) * F32(1 - 2.0 ** -23) * F32(r.choice([-1.0, 1.0]))),   # +-(2^-150 - 2^-196)
+                         (u(-75) * F32(1 + 2.0 ** -23), u(-75) * F32(1 + 2.0 ** -23) * F32(r.choice([-1.0, 1.0]))),   # +-(2^-150 + 2^-172 + 2^-196)
+                         (F32(r.uniform(-2, 2)) * u(-60), F32(r.uniform(-2, 2)) * u(-80)),
+                         (F32(r.uniform(-2, 2)) * u(-70), F32(r.uniform(-2, 2)) * u(-75))):
+                trip.append((a, b, c))
+    a, b, c = (np.array(v, F32) for v in zip(*trip))
+    want = np.array([_round_f32(Fraction(float(x)) * Fraction(float(y)) + Fraction(float(z))) for x, y, z in trip], F32)
+    tiny = np.abs(want) < F32(2.0 ** -126)
+    assert len(trip) == 480 and tiny.sum() >= 200 and (~tiny).sum() >= 150 and (np.abs(want) >= F32(2.0 ** -125)).sum() >= 60
+    s = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)
+    assert (np.abs(s).astype(F32) != np.abs(want)).sum() >= 10, "no triple on which rounding the double sum goes wrong"
+    assert np.array_equal(_bits(fmaf(a, b, c)), _bits(want)) and np.array_equal(_bits(fma32(a, b, c)), _bits(want))
+    one = np.array([fma32(x, y, z) for x, y, z in trip], F32)
+    assert np.array_equal(_bits(one), _bits(want)), int(np.argmax(_bits(one) != _bits(want)))
 
 
 # ---- signal path, model only ------------------------------------------------------------------------------------------------
