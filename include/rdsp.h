@@ -1080,6 +1080,51 @@ int rdsp_engine_pack_active(rdsp_engine_t *e, const int16_t *d_lr, size_t out_st
                             int16_t *d_audio /* [capacity_blocks][128] */, rdsp_pack_record_t *d_records /* [capacity_blocks] */,
                             size_t capacity_blocks, int32_t *d_counts /* [2]: needed, written */, void *stream);
 int rdsp_pack_runs(const rdsp_pack_record_t *records, int n_records, int64_t first_block, rdsp_pack_run_t *runs, int max_runs);
+/* Voice-rate audio.  The engine writes int16 audio at 44 100 Hz; what its audio filters pass is voice, about 3 kHz wide.  With
+ * rdsp_engine_enable_voice(e, R), R = 2 or 4 (one per engine), every call also low-passes and decimates the LEFT words of every
+ * receiver's output row by R on the device, behind the meter's gate, into rows the engine owns: 22 050 or 11 025 Hz, a half or
+ * a quarter of the bytes.  Opt-in: an engine that never calls it allocates, launches, returns and saves what it did before.
+ *   Taps: T = 16 R, q_k = (int32) rint((double) h_k x 2^18), h = rdsp_engine_ddc_taps(R, 1.0f): the Kaiser-windowed sinc (beta 9)
+ *     of the source passes, here at the input rate 44 100 Hz with its cutoff at the output's Nyquist frequency 44100 / (2 R).
+ *     rdsp_engine_voice_taps writes them; host only, no GPU.  sum q = 2^18 (R = 2), 2^18 + 2 (R = 4); sum |q| / 2^18 = 1.649,
+ *     1.603; ripple <= 0.0005 dB on |f| <= 0.544 fs / (2 R) (6 000 / 3 000 Hz); at least 91.0 dB down from 1.456 fs / (2 R)
+ *     (16 050 / 8 025 Hz) to 22 050 Hz.  Between those two edges lies the transition band: at R = 4 whatever the audio filter
+ *     leaves between 5.5 and 8 kHz folds onto 3 ... 5.5 kHz; R = 2 is the setting for AM.
+ *   Stream: x[n] is the stream of left words of a channel's output row exactly as the call leaves it -- behind the gate, so a
+ *     closed block is 128 zeros; n counts from the last reset and x[n] = 0 for n < 0.
+ *   Output:  acc[m] = sum_{k < T} q_k x[R m + R - 1 - k]                 exact integer, |acc| < 2^34
+ *            y[m]   = clamp((acc[m] + 2^17) >> 18, -32768, 32767)         arithmetic shift: floor, ties upwards
+ *     The window of output m ends at the newest of its R samples (the decimating pass's convention); a block of 128 samples
+ *     gives 128 / R outputs, so blocks stay aligned and there is no phase state.  The sum is exact, so the order of the adds
+ *     is free: no tile, lane or call size is in the bits, and the rows do not depend on how the stream is cut into calls.
+ *   State: per channel the last 60 left words of x, oldest first, as int32 (60 = 15 R at R = 4; R = 2 uses the newest 30):
+ *     the same words whatever R, so a receiver moves between engines with different R.  Signal state: it stays with the channel
+ *     through rdsp_engine_set_groups, is zeroed by rdsp_engine_reset, and travels in rdsp_engine_save_state / load_state as a
+ *     third optional part: header flag 4, 60 words per channel, behind the meter's words; rdsp_engine_state_bytes says so.  The
+ *     blob of an engine without the stage is unchanged; a blob with the part is refused by an engine without the stage
+ *     (RDSP_ERR_NOT_READY, nothing changed); a blob without it zeroes the history of the channels it lands on.
+ * - rdsp_engine_enable_voice works as rdsp_engine_enable_meter does: it takes no stream, waits for everything queued on the
+ *   engine's device, then allocates the history (240 bytes a channel) and the rows, int16 [ch][max_blocks x 128 / R]; if that
+ *   fails the object is as it was (RDSP_ERR_NOMEM).  The same R again: RDSP_OK, nothing changed.  Another R once the stage is on,
+ *   or an R other than 2 or 4: RDSP_ERR_INVALID, nothing changed.  It does not need the meter.  rdsp_engine_voice_rate: 0 while
+ *   the stage is off, otherwise R.
+ * - From then on every rdsp_engine_update runs the stage once, behind the last group's meter kernel, on the caller's stream
+ *   -- so also inside rdsp_engine_update_sources and _update_source_samples.  It reads d_lr and writes the engine's rows and
+ *   the history; n_blocks == 0 launches nothing.
+ * - rdsp_engine_read_voice copies the last call's rows, n_blocks x 128 / R words a row, into d_out [ch][out_stride] (a DEVICE
+ *   buffer), stream-ordered, as rdsp_engine_read_demod does.  RDSP_ERR_NOT_READY before rdsp_engine_enable_voice;
+ *   RDSP_ERR_INVALID for a NULL d_out, n_blocks negative or above the last call's, out_stride below the row.
+ * - rdsp_engine_pack_voice is rdsp_engine_pack_active for these rows: the packed sequence, the records, needed / written, the
+ *   sizing call, "nothing at or behind written is written", the counts {0, 0} of n_blocks == 0, repeatability and the refusals
+ *   are the same; the blocks are 128 / R words (d_audio[k x 128 / R + t]), there is no d_lr, and d_audio must be 16-byte
+ *   aligned.  It needs the meter and the stage, otherwise RDSP_ERR_NOT_READY.  rdsp_pack_runs serves unchanged. */
+int rdsp_engine_voice_taps(int R, int32_t *out /* [16 R] */);
+int rdsp_engine_enable_voice(rdsp_engine_t *e, int R);
+int rdsp_engine_voice_rate(const rdsp_engine_t *e);
+int rdsp_engine_read_voice(rdsp_engine_t *e, int n_blocks, int16_t *d_out, size_t out_stride, void *stream);
+int rdsp_engine_pack_voice(rdsp_engine_t *e, int n_blocks, int16_t *d_audio /* [capacity_blocks][128 / R] */,
+                           rdsp_pack_record_t *d_records /* [capacity_blocks] */, size_t capacity_blocks,
+                           int32_t *d_counts /* [2]: needed, written */, void *stream);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

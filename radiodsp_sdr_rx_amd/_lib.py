@@ -311,6 +311,11 @@ SYMBOLS = [
     ("rdsp_engine_read_demod", _i, [_vp, _i, _vp, _sz, _vp]),
     ("rdsp_engine_pack_active", _i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp, _vp]),
     ("rdsp_pack_runs", _i, [_vp, _i, C.c_int64, _vp, _i]),
+    ("rdsp_engine_voice_taps", _i, [_i, C.POINTER(C.c_int32)]),
+    ("rdsp_engine_enable_voice", _i, [_vp, _i]),
+    ("rdsp_engine_voice_rate", _i, [_vp]),
+    ("rdsp_engine_read_voice", _i, [_vp, _i, _vp, _sz, _vp]),
+    ("rdsp_engine_pack_voice", _i, [_vp, _i, _vp, _vp, _sz, _vp, _vp]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

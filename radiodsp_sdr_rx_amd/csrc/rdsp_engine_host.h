@@ -3,9 +3,10 @@
  * meter as an owner, the walk over groups.  rdsp_engine_host.hip holds the sketch's settings and setters and creates, resets
  * and runs the object; rdsp_engine_groups.hip the receiver groups; rdsp_engine_meter_host.hip the signal meter's owner and
  * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
- * rdsp_engine_state.hip the state blob.  Host logic only: the kernels are rdsp_engine.hip's stage files' (rdsp_engine_front /
- * _hilbert / _tail.hip), rdsp_engine_meter.hip's and rdsp_engine_pack.hip's, the front end is
- * rdsp_engine_sources.h's.  All five are compiled with the kernels' flags (-ffp-contract=off).
+ * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_state.hip the state blob.  Host logic
+ * only: the kernels are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's,
+ * rdsp_engine_pack.hip's and rdsp_engine_voice.hip's, the front end is rdsp_engine_sources.h's.  All six are compiled with the
+ * kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
 #define RDSP_ENGINE_HOST_H
@@ -22,6 +23,7 @@
 #include "rdsp_engine_meter.h"
 #include "rdsp_engine_pack.h"
 #include "rdsp_engine_sources.h"
+#include "rdsp_engine_voice.h"
 
 using namespace rdsp_eng;
 
@@ -51,6 +53,17 @@ struct EngMeter {
   /* the open blocks of the last call's first n_blocks, out of the caller's rows: p carries the caller's arguments, the rest is filled in here */
   hipError_t launch_pack(PackParams p, hipStream_t s) const;
 };
+/* the voice-rate audio (rdsp_engine_voice_host.hip): every channel's history of left words, the last call's decimated rows */
+struct EngVoice {
+  int R = 0;
+  DevBuf<int32_t> hist, taps; /* [ch][VOICE_HIST]; the 16 R tap words of voice_tap_pairs */
+  DevBuf<int16_t> rows;       /* [ch][row_words], row_words = max_blocks 128 / R */
+  size_t n_channels = 0, row_words = 0;
+  int blocks = 0; /* of the last call */
+  hipError_t init(size_t n_channels, size_t max_blocks, int R); /* every buffer; history and rows zeroed */
+  hipError_t reset(hipStream_t s);                              /* the history zero */
+  hipError_t launch(const int16_t *d_lr, size_t out_stride, int n_blocks, hipStream_t s); /* once per call, behind the last group's meter */
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -67,6 +80,7 @@ struct rdsp_engine {
   /* shared IQ streams (rdsp_engine_set_sources / tune / update_sources): the front end, from the first set_sources on */
   std::unique_ptr<EngFrontEnd> src;
   std::unique_ptr<EngMeter> meter; /* the signal meter, from rdsp_engine_enable_meter on */
+  std::unique_ptr<EngVoice> voice; /* the voice-rate audio, from rdsp_engine_enable_voice on */
   int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
   std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
 };

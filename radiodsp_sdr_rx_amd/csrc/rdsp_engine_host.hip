@@ -132,6 +132,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
                           : hipMemcpyAsync(e->plane[k], fill[k].data(), fill[k].size() * 4, hipMemcpyHostToDevice, s);
   if (err == hipSuccess && e->src) err = e->src->reset(s);
   if (err == hipSuccess && e->meter) err = e->meter->reset(s);
+  if (err == hipSuccess && e->voice) err = e->voice->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -233,6 +234,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
   }
   e->last_blocks = n_blocks;
   if (e->meter && (err = e->meter->launch_list(n_blocks, s)) != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
+  if (e->voice && (err = e->voice->launch(d_lr, out_stride, n_blocks, s)) != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
   return RDSP_OK;
 }
 

@@ -25,6 +25,7 @@ class Engine(Handle):
     def __init__(self, n_channels, max_blocks_per_call=64, device=0, tables=None):
         self._create("rdsp_engine_create", n_channels, device, max_blocks_per_call)
         self.n_channels, self.max_blocks = n_channels, max_blocks_per_call
+        self._last_blocks = 0   # of the last update made through this object: read_voice's and pack_voice's default
         if tables is not None:
             self.load_tables(*tables)
 
@@ -52,6 +53,7 @@ class Engine(Handle):
         if out is None:
             out = torch.empty_like(d_iq)
         check(self.lib.rdsp_engine_update(self.h, d_iq.data_ptr(), n, n // 128, out.data_ptr(), n, stream_ptr(stream)))
+        self._last_blocks = n // 128
         return out
 
     def set_sources(self, n_sources, source_of_channel):
@@ -127,6 +129,7 @@ class Engine(Handle):
         if out is None:
             out = torch.empty((self.n_channels, n, 2), dtype=torch.int16, device=d_src.device)
         check(self.lib.rdsp_engine_update_source_samples(self.h, d_src.data_ptr(), stride, n_blocks, out.data_ptr(), n, stream_ptr(stream)))
+        self._last_blocks = n_blocks
         return out
 
     def enable_meter(self):
@@ -215,6 +218,57 @@ class Engine(Handle):
         needed, written = counts()
         return audio[:written], records[:written], needed
 
+    def enable_voice(self, R):
+        """voice-rate audio from the next update on (include/rdsp.h, "voice-rate audio"): the left words of every receiver's
+        output row, behind the gate, low-passed and decimated by R = 2 or 4 on the device.  One R per engine; the same R again:
+        a no-op.  Takes no stream and waits for the device; does not need the meter."""
+        check(self.lib.rdsp_engine_enable_voice(self.h, int(R)))
+
+    @property
+    def voice_rate(self):
+        """R, or 0 while the stage is off"""
+        return int(self.lib.rdsp_engine_voice_rate(self.h))
+
+    def read_voice(self, n_blocks=None, stream=None):
+        """the last call's voice rows -> int16 [n_channels, n_blocks x 128 / R] on the device (default: the blocks of the last
+        update() or update_sources() of this object)"""
+        import torch
+        R = self.voice_rate
+        if n_blocks is None:
+            n_blocks = self._last_blocks
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks) * 128 // max(R, 1)
+        out = torch.empty((self.n_channels, n), dtype=torch.int16, device=dev)
+        check(self.lib.rdsp_engine_read_voice(self.h, int(n_blocks), out.data_ptr(), n, stream_ptr(stream)))
+        return out
+
+    def pack_voice(self, n_blocks=None, capacity=None, stream=None):
+        """the open blocks of the last call's voice rows, dense (include/rdsp.h, "voice-rate audio"): pack_active for blocks
+        of 128 / R words -> (audio int16 [written, 128 // R], records int32 [written, 2] = channel, block inside the call, both
+        on the device; needed).  Needs the meter and the stage.  n_blocks: the call's first so many blocks (default: all);
+        capacity: room for so many blocks (default: a sizing call first, then exactly `needed`)."""
+        import torch
+        R = self.voice_rate
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = self._last_blocks if n_blocks is None else int(n_blocks)
+        cnt = torch.empty(2, dtype=torch.int32, device=dev)
+        s = stream_ptr(stream)
+
+        def counts():   # read on the host: wait for the caller's stream, whichever form it came in, as active() does
+            if stream is not None:
+                (stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(stream)).synchronize()
+            return [int(v) for v in cnt.tolist()]
+        if capacity is None:
+            check(self.lib.rdsp_engine_pack_voice(self.h, n, None, None, 0, cnt.data_ptr(), s))
+            capacity = counts()[0]
+        capacity = int(capacity)
+        audio = torch.empty((capacity, 128 // max(R, 1)), dtype=torch.int16, device=dev)
+        records = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_pack_voice(self.h, n, audio.data_ptr() if capacity else None, records.data_ptr() if capacity else None,
+                                              capacity, cnt.data_ptr(), s))
+        needed, written = counts()
+        return audio[:written], records[:written], needed
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -257,6 +311,13 @@ def ddc_taps(D, gain=1.0):
     """the prototype low-pass of set_source_decimation(D, gain): 16 D float32 taps (host only, no GPU)"""
     o = np.zeros(16 * int(D), np.float32)
     check(load().rdsp_engine_ddc_taps(int(D), float(gain), o.ctypes.data_as(_F32P)))
+    return o
+
+
+def voice_taps(R):
+    """the taps of enable_voice(R): 16 R int32, the prototype of ddc_taps(R) times 2^18, rounded (host only, no GPU)"""
+    o = np.zeros(16 * int(R) if int(R) in (2, 4) else 1, np.int32)
+    check(load().rdsp_engine_voice_taps(int(R), o.ctypes.data_as(C.POINTER(C.c_int32))))
     return o
 
 
