@@ -357,7 +357,14 @@ int rdsp_chain_set_priorities(rdsp_chain_t *c, int front_fir_prio, int tail_prio
  * form.  All of them are the same exact linear convolution with the same taps (RDSP_ERR_UNSUPPORTED for 2 / 4 / 5
  * on decim-1 chains, which have no decimator).  RDSP_ERR_UNSUPPORTED, measured and not adopted (docs/history.md):
  * 1 matrix-core GEMM slices, 3 the same unless the tail stage shares the SIMDs, 6 the row form with 192 outputs
- * per window. */
+ * per window.
+ * One more thing decides how the wave-wide frequency-domain forms (2, 4 and the default beside a tail stage) round: the
+ * number of receiver groups.  A chain of at most 64 groups keeps, per group, the decimator's branch spectra multiplied by
+ * the mixer's rotations of the branches (rebuilt on the host at every retune) and mixes every branch with one phasor per
+ * quad column; above 64 groups each branch's phasors are rotated per frame on the device.  The same arithmetic to 1e-7
+ * of the output's peak, not to the bit: rdsp_chain_set_groups across that threshold changes the last bits of what
+ * follows, like a change of variant.  Within either range calls, splits, pipelining and sub-batches give the bits they
+ * gave before. */
 int rdsp_chain_set_fir_variant(rdsp_chain_t *c, int variant);
 /* tail-kernel variant: (16, 2) is the kernel there is -- a channel per 16-lane DPP row, two steps per
  * DPP reduction, delay line fed from LDS.  RDSP_ERR_UNSUPPORTED, measured and not adopted (docs/history.md): (16, 4)

@@ -88,6 +88,7 @@ static int chain_build(rdsp_chain_t *c, const rdsp_chain_config_t *cfg, int n_ch
       return chain_fail(RDSP_ERR_INVALID, "decimator spectra failed");
     HIP_TRY(c->d_fd_mask.alloc(img.size() / 2));
     HIP_TRY(hipMemcpy(c->d_fd_mask, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->fd_img = std::move(img); /* the groups' rotated spectra are made from it (chain_groups_commit) */
     std::vector<float> rimg(2 * 4 * 256);
     rdsp_rd_decimator_image(c->fir_nat.data(), rimg.data());
     HIP_TRY(c->d_rd_mask.alloc(rimg.size() / 2));
@@ -382,6 +383,7 @@ static void front_params(rdsp_chain_t *c, Call &k) {
    * call, not of how the stream is cut: both give the same bits for any split. */
   if (c->fir_mode == -1 && fp.fir_fd == 2 && !fp.to_mid) fp.fir_fd = 3;
   fp.fd_mask = c->d_fd_mask;
+  fp.rot_pool = c->d_rot_pool; /* null above RDSP_FD_ROT_GROUPS groups: the instance that rotates per frame (rdsp_front_pick_rotg) */
   fp.rd_mask = c->d_rd_mask;
   RdspFrontPick pick; /* the kernel this call runs, for the timing records (a refusal leaves the name: the launch reports it) */
   if (rdsp_front_pick(c->N, c->decim, &fp, &pick) == 0) c->front_name = rdsp_front_kernel_name(pick.family);

@@ -25,6 +25,7 @@ static uint32_t demod_tuning_offset(int demod) {
 }
 
 /* ---- receiver groups: double-buffered masks, records rewritten in stream order ---- */
+static const size_t kRotImg = 4 * (size_t)RDSP_FD_N; /* float2 of one group's rotated branch spectra (one buffer) */
 static void group_design(rdsp_chain_t *c, GroupState &g) { /* CONV:209-224 without the upload */
   const double fs_out = c->cfg.fs_in / (double)c->decim;
   rdsp_calc_cplx_FIR_coeffs(g.coef_I.data(), g.coef_Q.data(), c->hop + 1, g.lo, g.hi, fs_out, c->cfg.window);
@@ -65,12 +66,22 @@ int chain_groups_resize(rdsp_chain_t *c, int n) {
   }
   c->d_groups.release();
   c->d_mask_pool.release();
+  c->d_rot_pool.release();
   HIP_TRY(alloc_zero(c->d_groups, (size_t)n));
   HIP_TRY(alloc_zero(c->d_mask_pool, 2 * (size_t)c->N * (size_t)n));
+  /* the rotated branch spectra of the frequency-domain decimator, per group while the groups are few (rdsp_kernels.h) */
+  const bool rot = c->decim == 4 && n <= RDSP_FD_ROT_GROUPS;
+  if (rot) HIP_TRY(alloc_zero(c->d_rot_pool, 2 * kRotImg * (size_t)n));
   for (auto &g : c->groups) { /* pool contents are gone: every group restages */
     g.applied = 0;
     g.staged = -1;
     g.dirty = true;
+    g.rot_applied = 0;
+    g.rot_valid = false;
+    for (int k = 0; k < 2 && rot; k++) {
+      if (!g.ev_rot[k]) HIP_TRY(g.ev_rot[k].create(hipEventDisableTiming));
+      if (!g.rot_staging[k]) HIP_TRY(g.rot_staging[k].alloc(2 * kRotImg));
+    }
   }
   c->fence_valid = false;
   return RDSP_OK;
@@ -119,12 +130,36 @@ static void group_record(const rdsp_chain_t *c, const GroupState &g, int gi, int
   rdsp_nco_rot(r->dphi, 512, t); r->rotq2 = make_float2(t[0], t[1]);
   rdsp_nco_rot(r->dphi, 768, t); r->rotq3 = make_float2(t[0], t[1]);
   r->mask_off = (uint32_t)(((size_t)gi * 2 + (size_t)buf) * (size_t)c->N);
+  r->rot_off = c->d_rot_pool ? (uint32_t)(((size_t)gi * 2 + (size_t)g.rot_applied) * kRotImg) : 0u;
   /* the FIR history was mixed with the increment of the launch that brought it in */
   r->dphi_hist = g.has_dev_dphi ? g.dev_dphi : r->dphi;
   rdsp_nco_rot(r->dphi_hist, 1, t); r->roth1 = make_float2(t[0], t[1]);
   rdsp_nco_rot(r->dphi_hist, 2, t); r->roth2 = make_float2(t[0], t[1]);
   rdsp_nco_rot(r->dphi_hist, 3, t); r->roth3 = make_float2(t[0], t[1]);
   rdsp_nco_rot(r->dphi_hist, 12 * nt, t); r->rothp3 = make_float2(t[0], t[1]);
+}
+
+/* Group gi's rotated branch spectra for its current tuning offset, into the buffer of its slot that the device record does
+ * not point to; the record written right behind it (chain_groups_commit) switches over.  The copy is queued on the
+ * processing stream itself, behind every front kernel launched so far (the fence covers launches on another stream), so
+ * nothing that still reads that buffer -- it was live two retunes ago -- runs beside it.  The host waits only where the
+ * pinned image it is about to fill was read by an upload two retunes back that has not run yet. */
+static int group_stage_rot(rdsp_chain_t *c, int gi, uint32_t dphi, hipStream_t stream) {
+  GroupState &g = c->groups[(size_t)gi];
+  const int si = g.rot_next;
+  if (g.rot_issued[si]) HIP_TRY(hipEventSynchronize(g.ev_rot[si]));
+  rdsp_fd_rot_image(c->fd_img.data(), RDSP_FD_N, dphi, g.rot_staging[si]);
+  const int target = g.rot_valid ? 1 - g.rot_applied : g.rot_applied;
+  if (c->fence_valid) HIP_TRY(hipStreamWaitEvent(stream, c->ev_fence, 0));
+  float2 *dst = c->d_rot_pool + ((size_t)gi * 2 + (size_t)target) * kRotImg;
+  HIP_TRY(hipMemcpyAsync(dst, g.rot_staging[si], sizeof(float2) * kRotImg, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(g.ev_rot[si], stream));
+  g.rot_issued[si] = true;
+  g.rot_next = si ^ 1;
+  g.rot_applied = target;
+  g.rot_dphi = dphi;
+  g.rot_valid = true;
+  return RDSP_OK;
 }
 
 /* before a launch on `stream`: switch every changed group over, in stream order */
@@ -136,6 +171,10 @@ int chain_groups_commit(rdsp_chain_t *c, hipStream_t stream) {
     if (g.staged >= 0) {
       HIP_TRY(hipStreamWaitEvent(stream, g.ev_copy[g.stage_last], 0));
       buf = g.staged;
+    }
+    if (c->d_rot_pool) { /* a retune, a regrouping, the chain's first call: the slot follows the tuning offset */
+      const uint32_t dphi = rdsp_nco_dphi(g.nco_hz, c->cfg.fs_in);
+      if (!g.rot_valid || g.rot_dphi != dphi) RC_TRY(group_stage_rot(c, (int)i, dphi, stream));
     }
     RdspGroup r;
     group_record(c, g, (int)i, buf, &r);

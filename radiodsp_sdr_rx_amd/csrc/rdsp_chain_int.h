@@ -61,7 +61,18 @@ struct GroupState {
   PinnedBuf<float> staging[2];
   bool issued[2] = {false, false};
   int stage_next = 0, stage_last = 0;
-  float iir[20];            /* the group's audio band-pass as four biquads (RDSP_AUDIO_KIND_IIR) */
+  /* the group's slot of the rotated pool (d_rot_pool), double-buffered like the masks: which buffer the record points to,
+   * the increment its contents were made for, and two pinned images with the event of the upload that last read each.
+   * Derived data: made from the decimator's spectra and the tuning offset at the commit that follows a retune, a
+   * regrouping or a loaded state, never part of the state blob */
+  int rot_applied = 0;
+  bool rot_valid = false;
+  uint32_t rot_dphi = 0;
+  Event ev_rot[2];
+  PinnedBuf<float> rot_staging[2];
+  bool rot_issued[2] = {false, false};
+  int rot_next = 0;
+  float iir[20];           /* the group's audio band-pass as four biquads (RDSP_AUDIO_KIND_IIR) */
   bool iir_dirty = true;
 };
 /* Every device buffer, stream and event below has one owner (rdsp_dev.h), so `delete` releases the object once, whatever
@@ -89,6 +100,9 @@ struct rdsp_chain {
   DevBuf<float> d_fir_hc;
   DevBuf<float2> d_fd_mask; /* [4][512] branch spectra of the frequency-domain decimator (decim 4 only) */
   DevBuf<float2> d_rd_mask; /* [4][256] the same for the 256-point windows of the row forms */
+  std::vector<float> fd_img;     /* d_fd_mask's contents on the host: what the groups' rotated spectra are made from */
+  DevBuf<float2> d_rot_pool;     /* [n_groups][2][4][512] rot_r x d_fd_mask per group (RdspFrontParams::rot_pool); chains of
+                                    at most RDSP_FD_ROT_GROUPS groups with decimation 4, else none */
   DevBuf<float> d_sin_table; /* [513] sinTable_f32 (spectral stage as written, rdsp_set_spectral_resynthesis); made on first use */
   int spectral_literal = 0;
   /* rdsp_sdr_set_engine_literal: the reference's own pre-processor and engine in front of the CONV stage (INO:53-54,71-86) */

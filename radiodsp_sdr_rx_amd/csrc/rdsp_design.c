@@ -224,6 +224,23 @@ int rdsp_fd_decimator_image(const float *h_nat, int fft_l, float *image) {
   return 0;
 }
 
+/* One group's slot of the rotated pool (RdspFrontParams::rot_pool): the image above with the mixer's rotation of each
+ * branch folded in, out[r][k] = rot_r image[r][k], rot_r = exp(-j 2 pi r dphi / 2^32) -- rdsp_nco_rot's angle, kept in
+ * double until the product is rounded; branch 0 is copied.  A factor per branch, so the image's bin order does not matter. */
+void rdsp_fd_rot_image(const float *image, int fft_l, uint32_t dphi, float *out) {
+  for (int r = 0; r < 4; r++) {
+    const uint32_t ph = dphi * (uint32_t)r;
+    const double a = 2.0 * kPi * (double)ph / 4294967296.0;
+    const double c = cos(a), s = -sin(a);
+    for (int k = 0; k < fft_l; k++) {
+      const size_t o = 2 * ((size_t)r * (size_t)fft_l + (size_t)k);
+      const double re = (double)image[o], im = (double)image[o + 1];
+      out[o] = r ? (float)(re * c - im * s) : image[o];
+      out[o + 1] = r ? (float)(re * s + im * c) : image[o + 1];
+    }
+  }
+}
+
 /* The same branch spectra for the decimator on 16-lane rows (rdsp_front_rd_kernel): 256-point windows, 16 points per
  * lane, bin i + 16 e of lane i at [r][16 e + i]; /256 (the inverse transform is unnormalised). */
 int rdsp_rd_decimator_image(const float *h_nat, float *image) {

@@ -66,8 +66,16 @@ struct FrontFdLds {
  *     Every call boundary is a frame boundary and a frame's input is a function of the absolute sample position:
  *     the same bits for any call split, at 5 transforms per 256 outputs instead of per 448.
  * Pipelining, sub-batches and the channel partition never change a bit in either.  The pre-processor's IQ swap and
- * the noise blanker are compiled in with PRE. */
-template <int N, int P, bool LEAN, bool PRE, bool Q4 = false, int VC = RDSP_FD_P - 1>
+ * the noise blanker are compiled in with PRE.
+ *
+ * ROTG (chains of at most RDSP_FD_ROT_GROUPS groups, rdsp_front_pick_rotg): sample 4 q + r of a quad follows sample 4 q by
+ * the rotation rot_r, one constant per branch and group, and a constant factor on a transform's whole input commutes with
+ * the transform:  sum_r G_r . FFT(x_r P rot_r) = sum_r (rot_r G_r) . FFT(x_r P).  The group's own rot_r G_r come from its
+ * slot of p.rot_pool (filled on the host at every retune, the layout of fd_mask) and every branch is mixed with the column
+ * phasors pj[j] alone: 24 complex products per frame and lane less, and rot1..3 out of the scalar registers.  Only column 0
+ * of the first frame behind a retune was mixed with other rotations (roth_r): its phasor takes roth_r conj(rot_r) there.
+ * The two forms round differently (1e-7); which one a chain runs depends on its number of groups alone (include/rdsp.h). */
+template <int N, int P, bool LEAN, bool PRE, bool Q4 = false, int VC = RDSP_FD_P - 1, bool ROTG = false>
 __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams p) {
   using PL = FftPlan<N, P>;              /* the overlap-save filter's transform (FFT_L)     */
   constexpr int ND = RDSP_FD_N, PD = RDSP_FD_P; /* the decimator's: 512 points whatever FFT_L is  */
@@ -122,7 +130,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams
     const uint32_t *gw = reinterpret_cast<const uint32_t *>(p.groups + gi);
     uint32_t r[32];
 #pragma unroll
-    for (int i = 0; i < 32; i++) r[i] = (i < 30) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)gw[i]) : 0u;
+    for (int i = 0; i < 32; i++) r[i] = (i < 31) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)gw[i]) : 0u;
     G = __builtin_bit_cast(RdspGroup, r);
   }
   const int total = p.n_chunks * 256; /* outputs = input quads of this call */
@@ -327,7 +335,7 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams
     for (int r = 0; r < 4; r++) {
       float2 gm[PD]; /* G_r slice of this lane: L2-resident, lands behind the transform */
       {
-        const float2 *mp = p.fd_mask + (size_t)r * ND;
+        const float2 *mp = ROTG ? p.rot_pool + G.rot_off + (size_t)r * ND : p.fd_mask + (size_t)r * ND;
         asm volatile("" : "+s"(mp));
         const auto gp = as_global(mp);
 #pragma unroll
@@ -343,7 +351,13 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams
         float2 x = make_float2((float)(int16_t)(w & 0xFFFFu), (float)(int16_t)(w >> 16));
         if constexpr (PRE) x = make_float2(x.x * (j == 0 ? sxi0 : sxi), x.y * (j == 0 ? sxq0 : sxq));
         float2 ph = pj[j];
-        if (r > 0) {
+        if constexpr (ROTG) {
+          /* rot_r rides on the branch's spectrum; the history column behind a retune came in under roth_r */
+          if (r > 0 && j == 0 && hist && dphi_hist != G.dphi) {
+            ph = cmul_pinned_u(ph, (r == 1) ? RDSP_GROUP_LATE_F2(gi, roth1) : (r == 2) ? RDSP_GROUP_LATE_F2(gi, roth2) : RDSP_GROUP_LATE_F2(gi, roth3));
+            ph = cmulc_uniform(ph, (r == 1) ? RDSP_GROUP_LATE_F2(gi, rot1) : (r == 2) ? RDSP_GROUP_LATE_F2(gi, rot2) : RDSP_GROUP_LATE_F2(gi, rot3));
+          }
+        } else if (r > 0) {
           const float2 rr = (r == 1) ? G.rot1 : (r == 2) ? G.rot2 : G.rot3;
           if (j == 0) { /* the history column of the call's first frame: the rotation it was mixed with */
             float2 r0 = rr;
@@ -479,17 +493,17 @@ inline size_t granule_form_lds_pad(int to_mid) {
   return 0;
 }
 
-template <int N, int P, bool LEAN, bool PRE, bool Q4, int VC>
+template <int N, int P, bool LEAN, bool PRE, bool Q4, int VC, bool ROTG>
 int launch_fd(const RdspFrontParams *p, int n_channels, hipStream_t stream) {
   constexpr size_t lds = FrontFdLds<N, P, Q4>::BYTES;
   static_assert(!Q4 || lds <= 48 * 1024, "no raised dynamic-LDS limit needed");
   if constexpr (lds > 48 * 1024) {
-    int e = ensure_lds_limit<&rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC>>(lds);
+    int e = ensure_lds_limit<&rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC, ROTG>>(lds);
     if (e != 0) return e;
   }
   size_t ask = lds;
   if constexpr (!Q4 && lds <= 16 * 1024) ask = lds + granule_form_lds_pad(p->to_mid);
-  hipLaunchKernelGGL((rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC>), dim3(n_channels), dim3(N / P), ask, stream, *p);
+  hipLaunchKernelGGL((rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC, ROTG>), dim3(n_channels), dim3(N / P), ask, stream, *p);
   return (int)hipGetLastError();
 }
 
@@ -508,8 +522,11 @@ int rdsp::front_fd_launch(int fft_l, const RdspFrontPick &k, const RdspFrontPara
           constexpr int N = decltype(plan)::N, P = decltype(plan)::P;
           constexpr bool LEAN = decltype(lean)::value, PRE = decltype(pre)::value, Q4 = decltype(q4)::value;
           if constexpr (fd_instance<N, P, LEAN, Q4>)
-            return k.frame == 4 ? launch_fd<N, P, LEAN, PRE, Q4, 4>(p, n_channels, stream)
-                                : launch_fd<N, P, LEAN, PRE, Q4, RDSP_FD_P - 1>(p, n_channels, stream);
+            return with_flag(rdsp_front_pick_rotg(p) != 0, [&](auto rotg) {
+              constexpr bool ROTG = decltype(rotg)::value;
+              return k.frame == 4 ? launch_fd<N, P, LEAN, PRE, Q4, 4, ROTG>(p, n_channels, stream)
+                                  : launch_fd<N, P, LEAN, PRE, Q4, RDSP_FD_P - 1, ROTG>(p, n_channels, stream);
+            });
           else return (int)hipErrorInvalidValue;
         });
       });

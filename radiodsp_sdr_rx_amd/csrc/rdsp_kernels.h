@@ -33,7 +33,8 @@ struct RdspGroup {
   float2 rothp3;       /* rotp3 for dphi_hist                                      */
   float2 rotq1, rotq2, rotq3; /* the same for 256 k samples: one quad column of the
                                  frequency-domain decimator's frame (rdsp_front_fd_kernel)   */
-  uint32_t pad[2];
+  uint32_t rot_off;    /* float2 offset of the group's active rotated branch spectra in rot_pool (0 without one) */
+  uint32_t pad;
 };
 
 /* front kernel: A1 unpack, A2 mixer, A3 decimator, A5 overlap-save filter,
@@ -89,7 +90,14 @@ struct RdspFrontParams {
   float *mid_q;            /* [ch][mid_stride] Im y for SAM channels, else unused */
   size_t mid_stride;
   int ch_base;             /* first channel of this launch (workgroup b works on ch_base + b) */
+  const float2 *rot_pool;  /* [n_groups][2][4][RDSP_FD_N] per group rot_r x the spectra of fd_mask, r = 0..3 (double-buffered
+                              like mask_pool; RdspGroup::rot_off); null: chains of more than RDSP_FD_ROT_GROUPS groups, and
+                              chains without the frequency-domain decimator */
 };
+/* Up to this many groups a chain keeps pre-rotated branch spectra per group (rot_pool) and its frequency-domain front
+ * kernel is the instance that reads them (ROTG).  16 KiB per group at 512 points: the tables of the groups one XCD serves
+ * stay within a quarter of its 4 MiB L2. */
+#define RDSP_FD_ROT_GROUPS 64
 
 /* Which front-kernel instance a call runs: the one statement of that choice (rdsp_front_pick, rdsp_kernels.hip).
  * rdsp_launch_front launches what it names, and the chain takes the kernel's name for its timing records from it. */
@@ -222,6 +230,9 @@ int rdsp_launch_front(int fft_l, int decim, const RdspFrontParams *p, int n_chan
  * FFT_L / decimation, or a row form without its masks; hipErrorNotSupported: a variant this build does not carry), and
  * leaves *pick alone then.  Looks at no pointer of *p but rd_mask (null or not). */
 int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, RdspFrontPick *pick);
+/* the one more choice inside the RDSP_FRONT_FD family: 1 when the call runs the instances that read the groups' pre-rotated
+ * branch spectra (ROTG) -- the chain has a rot_pool, which it keeps up to RDSP_FD_ROT_GROUPS groups -- else 0, today's */
+int rdsp_front_pick_rotg(const RdspFrontParams *p);
 const char *rdsp_front_kernel_name(int family); /* "rdsp_front_kernel", "rdsp_front_fd_kernel", "rdsp_front_rd_kernel" */
 int rdsp_launch_tail(const RdspTailParams *p, int lanes_per_channel, hipStream_t stream);
 int rdsp_launch_sam(const RdspSamParams *p, hipStream_t stream);

@@ -112,6 +112,10 @@ extern "C" int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, R
   return 0;
 }
 
+/* ROTG, inside the wave-wide frequency-domain family: the chain hands over a pool of per-group rotated branch spectra
+ * while it has at most RDSP_FD_ROT_GROUPS groups (chain_groups_resize), and with one the instances that read it run */
+extern "C" int rdsp_front_pick_rotg(const RdspFrontParams *p) { return p->rot_pool != nullptr; }
+
 extern "C" const char *rdsp_front_kernel_name(int family) {
   return family == RDSP_FRONT_RD ? "rdsp_front_rd_kernel" : (family == RDSP_FRONT_FD ? "rdsp_front_fd_kernel" : "rdsp_front_kernel");
 }
