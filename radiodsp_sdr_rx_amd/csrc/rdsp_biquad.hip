@@ -6,7 +6,7 @@
  *     (RDSP_controls.h:153-177) is a table of 8th-order band-passes in
  *     arm_biquad_cascade_df1_f32 layout in the shipped firmware; the chain
  *     runs it on the demodulated mono audio between the front kernel and the tail stage when
- *     rdsp_sdr_setAudioFilterKind selects it (rdsp_chain_groups.hip).  SectionF32: arm_biquad_cascade_df1_f32 as
+ *     rdsp_sdr_setAudioFilterKind selects it (rdsp_chain_select.hip).  SectionF32: arm_biquad_cascade_df1_f32 as
  *     CMSIS-DSP publishes it, direct form 1 in float, per stage
  *         acc = (b0 * Xn) + (b1 * Xn1) + (b2 * Xn2) + (a1 * Yn1) + (a2 * Yn2)
  *     summed left to right, EVERY PRODUCT ROUNDED BEFORE IT IS ADDED (feedback terms added, coefficient order

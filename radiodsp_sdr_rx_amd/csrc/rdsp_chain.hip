@@ -1,8 +1,8 @@
 /*
  * rdsp_chain.hip -- C-ABI launch layer: the chain object (per-channel state in
  * HBM, shared tables) and the calls declared in include/rdsp.h that create, destroy,
- * reset and run it.  Its groups, setters and state live in rdsp_chain_groups.hip,
- * rdsp_chain_ctl.hip and rdsp_chain_state.hip (rdsp_chain_int.h).  Host logic
+ * reset and run it.  Its groups, their selection logic, setters and state live in rdsp_chain_groups.hip,
+ * rdsp_chain_select.hip, rdsp_chain_ctl.hip and rdsp_chain_state.hip (rdsp_chain_int.h).  Host logic
  * only; the arithmetic lives in the kernel files (rdsp_front_*.hip, rdsp_tail*.hip, ...).  No CPU fallback exists: if
  * HIP reports no device every compute entry point returns RDSP_ERR_NO_DEVICE.
  */

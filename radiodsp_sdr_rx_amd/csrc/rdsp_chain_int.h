@@ -1,8 +1,9 @@
 /*
  * rdsp_chain_int.h -- what the host files of rdsp_chain_t share: the object, the error returns, the table of per-channel
- * state planes.  rdsp_chain.hip creates, destroys, resets and runs it; rdsp_chain_groups.hip holds the receiver groups and
- * what selects their filters and demodulators; rdsp_chain_ctl.hip the setters; rdsp_chain_state.hip the state planes, the
- * blob and the read-backs.  Host logic only; the arithmetic lives in the kernel files (rdsp_front_*.hip, rdsp_tail*.hip, ...).
+ * state planes.  rdsp_chain.hip creates, destroys, resets and runs it; rdsp_chain_groups.hip holds the receiver groups'
+ * device side (their double-buffered slots, GroupSlot below, and their records); rdsp_chain_select.hip what selects a
+ * group's filter and demodulator; rdsp_chain_ctl.hip the setters; rdsp_chain_state.hip the state planes, the blob and the
+ * read-backs.  Host logic only; the arithmetic lives in the kernel files (rdsp_front_*.hip, rdsp_tail*.hip, ...).
  */
 #ifndef RDSP_CHAIN_INT_H
 #define RDSP_CHAIN_INT_H
@@ -18,6 +19,7 @@
 #include "rdsp_dev.h"
 #include "rdsp_host.h"
 #include "rdsp_kernels.h"
+#include "rdsp_slot.h"
 
 using namespace rdsp_dev; /* DevBuf, PinnedBuf, Stream, Event */
 
@@ -39,39 +41,66 @@ static inline hipError_t push_event(std::deque<Event> &pool, unsigned flags) {
   return e;
 }
 
-/* host side of one receiver group: filter, tuning offset, demodulator.
- * The device sees it as one RdspGroup record plus two mask buffers; a retune fills
- * the buffer the record does not point to (copy stream) and the record is rewritten
- * in stream order at the next processing call. */
+/* One double-buffered per-group table that the front kernels read while the host replaces it (rdsp_slot.h has the protocol):
+ * group g's two halves are pool[(g * 2 + half) * words ...], and there are two pinned images with the event of the upload
+ * that last read each.  A fill writes the image whose upload is two fills old, so the host never overwrites an image that an
+ * earlier, still queued upload has yet to read (streams only wait for uploads on the device; the host does not know when
+ * one has run).  Used by rdsp_chain_groups.hip alone. */
+struct GroupSlot {
+  rdsp_slot::Slot plan;
+  size_t words = 0; /* float2 per half and per image */
+  PinnedBuf<float> image[2];
+  Event ev[2];
+  bool issued[2] = {false, false};
+  int create(size_t n_words) { /* idempotent */
+    words = n_words;
+    for (int k = 0; k < 2; k++) {
+      if (!ev[k]) HIP_TRY(ev[k].create(hipEventDisableTiming));
+      if (!image[k]) HIP_TRY(image[k].alloc(2 * words));
+    }
+    return RDSP_OK;
+  }
+  /* the image to write.  The upload that last read it is two fills old: almost always long done; if not (a burst of
+   * retunes of one group while the device is calls behind) the host waits for it */
+  int begin_fill(float **img) {
+    const int si = plan.next_image;
+    if (issued[si]) HIP_TRY(hipEventSynchronize(ev[si]));
+    *img = image[si];
+    return RDSP_OK;
+  }
+  /* queue that image's upload on `stream`, behind `fence` if there is one: kernels launched so far may still read the
+   * target half (it was live before the last switch) */
+  int upload(float2 *pool, int group, hipEvent_t fence, hipStream_t stream) {
+    const rdsp_slot::Fill f = plan.fill();
+    if (fence) HIP_TRY(hipStreamWaitEvent(stream, fence, 0));
+    float2 *dst = pool + ((size_t)group * 2 + (size_t)f.target) * words;
+    HIP_TRY(hipMemcpyAsync(dst, image[f.image], sizeof(float2) * words, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(ev[f.image], stream));
+    issued[f.image] = true;
+    return RDSP_OK;
+  }
+  hipEvent_t last_upload() const { return ev[plan.last_image]; }
+  uint32_t live_off(int group) const { return (uint32_t)(((size_t)group * 2 + (size_t)plan.live) * words); }
+};
+
+/* host side of one receiver group: filter, tuning offset, demodulator.  The device sees it as one RdspGroup
+ * record plus its slots of the mask pool and of the rotated pool; a retune fills the half the record does not point to and
+ * the record is rewritten in stream order at the next processing call. */
 struct GroupState {
   double lo = 0.0, hi = 0.0, nco_hz = 0.0;
   int demod = RDSP_DEMOD_USB, audio_filter = RDSP_AUDIO_2700;
   std::vector<double> coef_I, coef_Q; /* FIR_Coef_I/Q, CONV:69-70 */
   std::vector<float> mask_nat;        /* FIR_filter_mask, CONV:77 */
-  int applied = 0;   /* mask buffer the device record points to (as queued) */
-  int staged = -1;   /* buffer holding a newer mask that is not yet switched in */
   bool dirty = true; /* the device record must be rewritten before the next launch */
   bool has_dev_dphi = false; /* dev_dphi: increment the last launch mixed with */
   uint32_t dev_dphi = 0;
-  /* two pinned images of the mask (N float2 each) with the event of the upload that last read each:
-   * a retune fills the one whose upload is two retunes old, so the host never overwrites an image
-   * an earlier, still queued upload has yet to read (the processing stream only waits for uploads
-   * on the device; the host does not know when one has run) */
-  Event ev_copy[2];
-  PinnedBuf<float> staging[2];
-  bool issued[2] = {false, false};
-  int stage_next = 0, stage_last = 0;
-  /* the group's slot of the rotated pool (d_rot_pool), double-buffered like the masks: which buffer the record points to,
-   * the increment its contents were made for, and two pinned images with the event of the upload that last read each.
-   * Derived data: made from the decimator's spectra and the tuning offset at the commit that follows a retune, a
-   * regrouping or a loaded state, never part of the state blob */
-  int rot_applied = 0;
+  GroupSlot mask; /* d_mask_pool: N float2, uploaded on the copy stream by a filter change */
+  /* d_rot_pool: 4 x RDSP_FD_N float2, valid for the increment rot_dphi.  Derived data: made from the decimator's spectra
+   * and the tuning offset on the processing stream, at the commit that follows a retune, a regrouping or a loaded state,
+   * never part of the state blob */
+  GroupSlot rot;
   bool rot_valid = false;
   uint32_t rot_dphi = 0;
-  Event ev_rot[2];
-  PinnedBuf<float> rot_staging[2];
-  bool rot_issued[2] = {false, false};
-  int rot_next = 0;
   float iir[20];           /* the group's audio band-pass as four biquads (RDSP_AUDIO_KIND_IIR) */
   bool iir_dirty = true;
 };

@@ -45,6 +45,22 @@ def test_pbt_step_rejects_bad_arguments(rdsp):
     assert (a.value, b.value) == (300.0, 2700.0)
 
 
+def test_slot_protocol_on_the_host(tmp_path):
+    """tests/host/host_slot_check.cpp: csrc/rdsp_slot.h, the double-buffering of the groups' masks and rotated spectra, as a
+    program of its own under ASan + UBSan -- every sequence of fills and switches up to length 12 against the mask
+    staging as it was written out before the slot existed"""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "host_slot_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(root, "radiodsp_sdr_rx_amd", "csrc"),
+                           os.path.join(root, "tests", "host", "host_slot_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.startswith("host_slot_check OK"), out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "Sanitizer" not in out.stderr, out.stderr
+
+
 # ---- GPU parity --------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def torch_cuda():

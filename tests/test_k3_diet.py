@@ -280,6 +280,76 @@ def test_rotation_fold_pipelined_is_the_unpipelined_result_to_the_bit(fold_iq):
     assert np.array_equal(a, b)
 
 
+# ---- a burst of retunes: both pinned images, the host's wait for an upload two retunes old, both halves of the slot -----------
+ROT_NCO = (12000.0, 14600.0, 9300.0)
+ROT_OFFSETS = (13150.0, 9300.0, 9300.0, 14600.0, 11250.0, 12000.0, 0.0, 2500.0)   # the third repeats the second: nothing is staged
+
+
+def rot_burst_run(parts, first, offsets, sync_before_retune=False, want_f32=False):
+    """eight calls on three groups (channel % 3); from call `first` on group 1 is retuned before every call.  Outputs per call"""
+    from radiodsp_sdr_rx_amd.chain import Chain
+    nch = parts[0].shape[0]
+    ch = Chain(nch, max_blocks_per_call=parts[0].shape[1] // 128, fir_variant=2, fft_l=512, demod="USB")
+    ch.set_groups((np.arange(nch) % 3).astype(np.uint16))
+    for g, hz in enumerate(ROT_NCO):
+        ch.group_setTuningOffsetHz(g, hz)
+    outs = []
+    for k, part in enumerate(parts):
+        if k >= first and offsets:
+            if sync_before_retune:
+                torch.cuda.synchronize()
+            ch.group_setTuningOffsetHz(1, offsets[k - first])
+        o = ch.process(part, want_f32=want_f32)
+        outs.append(o[1] if want_f32 else o)
+    ch.flush()
+    torch.cuda.synchronize()
+    return np.stack([o.cpu().numpy() for o in outs])
+
+
+@gpu
+def test_back_to_back_retunes_of_the_rotated_spectra_while_the_device_is_calls_behind():
+    """the counterpart of tests/test_groups.py's burst test of the masks, for the other slot: a retune of group 1 before each of five calls, issued
+    while the device is still working on earlier calls.  An upload of the rotated spectra is queued behind those calls when
+    the next retune but one fills the same pinned image, and must still carry its own spectra.  The reference run
+    synchronises before every retune; both must give the same bits."""
+    from radiodsp_sdr_rx_amd.chain import synth_iq
+    nch, per, calls = 1024, 32, 8
+    iq = torch.from_numpy(synth_iq(nch, per * 128)).cuda()       # every call gets the same block of input
+    parts, offsets = [iq] * calls, ROT_OFFSETS[:5]
+    ref = rot_burst_run(parts, 3, offsets, sync_before_retune=True)
+    got = rot_burst_run(parts, 3, offsets)
+    assert np.array_equal(got, ref)
+    for k in range(3, calls - 1):                                # the retunes do change group 1 from call to call
+        assert not np.array_equal(ref[k][1::3], ref[k + 1][1::3]), f"calls {k} and {k + 1}"
+    plain = rot_burst_run(parts, 3, ())
+    assert np.array_equal(got[:, 0::3], plain[:, 0::3]) and np.array_equal(got[:, 2::3], plain[:, 2::3])
+    assert not np.array_equal(got[3:, 1::3], plain[3:, 1::3])
+
+
+@gpu
+def test_a_retune_before_every_call_against_the_oracle(oracle):
+    """the same burst on five channels and calls of 8 blocks, a retune before every one of them, by value: one oracle chain
+    per channel, the criterion of the fold tests above"""
+    from radiodsp_sdr_rx_amd.chain import synth_iq
+    nch, per, calls = 5, 8, 8
+    iq = synth_iq(nch, calls * per * 128)
+    parts = [np.ascontiguousarray(iq[:, k * per * 128:(k + 1) * per * 128]) for k in range(calls)]
+    got = rot_burst_run([torch.from_numpy(p).cuda() for p in parts], 0, ROT_OFFSETS, want_f32=True)
+    got = np.concatenate(list(got), 1)
+    ref = []
+    for c in range(nch):
+        oc, outs = oracle.OracleChain(fft_l=512, demod="USB", nco_hz=ROT_NCO[c % 3]), []
+        for k in range(calls):
+            if c % 3 == 1:
+                oc.set_nco_hz(ROT_OFFSETS[k])
+            outs.append(oc.process(parts[k][c])[1])
+        ref.append(np.concatenate(outs))
+    ref = np.stack(ref)
+    err = [float(np.abs(got[c] - ref[c]).max() / max(np.abs(ref[c]).max(), 1e-30)) for c in range(nch)]
+    print("normwise per channel:", ["%.2e" % e for e in err])
+    assert normwise(got, ref) <= TOL
+
+
 # ---- host: a group's slot of the pool against rot_r x G_r in double (no GPU) -------------------------------------------------
 def test_rotated_pool_image_on_the_host(rdsp, tmp_path):
     import os
