@@ -1132,6 +1132,66 @@ int rdsp_engine_read_voice(rdsp_engine_t *e, int n_blocks, int16_t *d_out, size_
 int rdsp_engine_pack_voice(rdsp_engine_t *e, int n_blocks, int16_t *d_audio /* [capacity_blocks][128 / R] */,
                            rdsp_pack_record_t *d_records /* [capacity_blocks] */, size_t capacity_blocks,
                            int32_t *d_counts /* [2]: needed, written */, void *stream);
+/* Narrow-band FM.  Between 30 MHz and 1 GHz nearly every voice channel is narrow-band FM; the sketch's engine has no FM mode,
+ * this is a design of this build.  After rdsp_engine_enable_fm(e), rdsp_engine_setDemodMode(e, RDSP_ENGINE_MODE_NFM) puts the
+ * selected group(s) into NFM: one kernel stands where the IF filter, the mixer and the detector stood, the audio filter, AGC,
+ * ALS, output gain and mute run unchanged on what it writes, and the group's meter measures the POWER IN THE CHANNEL, not the
+ * audio -- a carrier squelch: a discriminator with no signal delivers full-scale noise, which would hold an audio squelch open.
+ * Opt-in: an engine that never calls rdsp_engine_enable_fm allocates, launches, returns and saves what it did before.
+ *   Input: the receiver's int16 IQ row at 44 100 Hz exactly as rdsp_engine_update receives it (with sources: the tuned row).
+ *     x[n] = ((float) I, (float) Q) in counts; n counts from the last FM reset and x[n] = 0 for n < 0.  NFM ignores
+ *     rdsp_engine_setInputGain, rdsp_engine_setIQgainBalance and the blanker: a discriminator does not care about amplitude.
+ *   1. Channel filter.  h = rdsp_engine_ddc_taps(W, 1.0f), T = 16 W taps: the Kaiser-windowed sinc of the source passes at the
+ *      input rate.  zI[n] is ONE chain over k ascending from 0, zI = fmaf(h[k], xI[n - k], zI); zQ likewise.  On the float taps:
+ *        W = 2 (wide):   within 0.001 dB to 7 kHz, -0.07 dB at 8 kHz, -6 dB at 11.0 kHz, -17 dB at 12.5 kHz, >= 90 dB from 16.05 kHz
+ *        W = 3 (narrow): within 0.001 dB to 4 kHz, -0.13 dB at 5.5 kHz, -6 dB at 7.35 kHz, >= 82 dB from 10 kHz
+ *      for 5 kHz deviation on 25 kHz channels (Carson +-8 kHz) and 2.5 kHz on 12.5 kHz channels (+-5.5 kHz).  sum |h| <= 1.65.
+ *   2. Level row.  lvl[n] = sqrtf(fmaf(zI, zI, zQ zQ)) 2^-15, the square root correctly rounded.  A full-scale complex carrier
+ *      reads 1.0; its mean square, 1.0, is +3 dB on the scale of the meter's thresholds, which is referred to a real sine.
+ *   3. Discriminator.  (pI, pQ) = z[n - 1]; re = fmaf(zI, pI, zQ pQ); im = fmaf(zQ, pI, -(zI pQ)); d[n] = fm_atan2(im, re).
+ *      fm_atan2(y, x) is this build's own function (csrc/rdsp_fm.h has every operation): +0 when both arguments are 0; t =
+ *      min(|x|, |y|) / max(|x|, |y|), one correctly rounded quotient; a seven-term odd polynomial in t by Horner with fmaf;
+ *      pi/2 - p when |y| > |x|, pi - p when x < 0, the sign bit of y.  Its worst error against the double atan2, measured over
+ *      every t = j / 2^20 and a million drawn pairs, is 5.2e-7 rad (the bound: 2^-19).  rdsp_engine_fm_atan2 exports it.
+ *   4. Scale and clip.  k = (float)(44100.0 / (6.283185307179586 (double) deviation_hz)); u[n] = fminf(fmaxf(d[n] k, -1), 1).
+ *      The peak deviation reads +-1.0; the noise of an empty channel is clipped to the rails.
+ *   5. De-emphasis.  a = (float)(1.0 / (1.0 + 44100.0 (double) tau_us 1e-6)); y[n] = fmaf(a, u[n] - y[n - 1], y[n - 1]).
+ *      tau_us == 0 bypasses the stage (y = u).  rdsp_engine_fm_constants writes {k, a}; host only, no GPU.
+ *   6. Output.  y[n] is the "demod" tap (rdsp_engine_read_demod); the tail runs on it with the group's settings.  The useful
+ *      combination is one of the audio band-passes (they remove sub-audible tones) with the AGC off.
+ *   7. Meter.  For a group in NFM the meter is handed the level rows in place of the demodulated ones: level, peak, gate, hang,
+ *      the zeroing of closed blocks, the active list, rdsp_engine_pack_active, the voice stage and rdsp_engine_pack_voice work
+ *      unchanged.  Thresholds stay mean squares.
+ *   Everything is a function of the sample index: a stream gives the same bits however it is cut into calls.
+ *   State: per channel 50 words -- the newest 47 input pair words (I | Q << 16), oldest first (W = 2 uses the newest 31); z[n - 1],
+ *     two floats; y[n - 1].  Signal state: it stays with the channel through rdsp_engine_set_groups, is zeroed by
+ *     rdsp_engine_reset and by a pending FM reset at the next update, is maintained only while the group is in NFM, and travels
+ *     in rdsp_engine_save_state / load_state as a fourth optional part: header flag 8, 50 words per channel, behind the voice
+ *     history; rdsp_engine_state_bytes says so.  The blob of an engine without FM is unchanged; a blob with the part is refused
+ *     by an engine without FM (RDSP_ERR_NOT_READY, nothing changed); a blob without it zeroes the detector words of the channels
+ *     it lands on.  NFM groups do not move the side-band lines (as AM).
+ * - rdsp_engine_enable_fm works as rdsp_engine_enable_meter does: it takes no stream, waits for everything queued on the
+ *   engine's device, then allocates the state (200 bytes a channel) and the level rows, float [ch][max_blocks x 128]; if that
+ *   fails the object is as it was (RDSP_ERR_NOMEM).  Again: RDSP_OK, nothing changed.
+ * - rdsp_engine_setDemodMode(e, RDSP_ENGINE_MODE_NFM) after it: returns TuningOffset 0.0 (the station sits at DC, so
+ *   rdsp_engine_tune, the source passes and rdsp_channelizer_place work unchanged) and leaves a reset of the group's detector
+ *   words pending, with the rules of the other pending resets (rdsp_engine_set_groups below).  Before rdsp_engine_enable_fm
+ *   the value is one the engine does not know, as ever: the group's mode word becomes 7 and nothing else changes.  A later
+ *   rdsp_engine_enable_fm leaves such a group alone -- it runs no detector until rdsp_engine_setDemodMode(e, 7) is called again,
+ *   after rdsp_engine_enable_fm.  Leaving the mode and coming back resets the detector.
+ * - rdsp_engine_set_fm(e, W, deviation_hz, tau_us): settings of the selected group(s), copied by a new group, kept by reset,
+ *   in no blob; they may precede rdsp_engine_enable_fm.  W is 2 or 3, deviation_hz in [1000, 7500], tau_us 0 or in [25, 1000];
+ *   the defaults are 2, 5000, 750.  Anything else: RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_read_fm_level copies the last call's level rows, n_blocks x 128 floats a row, into d_out [ch][stride] (a DEVICE
+ *   buffer), stream-ordered, as rdsp_engine_read_demod does; rows of receivers not in NFM read as zeros.  RDSP_ERR_NOT_READY
+ *   before rdsp_engine_enable_fm; RDSP_ERR_INVALID for a NULL d_out, n_blocks negative or above the last call's, a short stride. */
+#define RDSP_ENGINE_MODE_NFM 7
+int rdsp_engine_enable_fm(rdsp_engine_t *e);
+int rdsp_engine_fm_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_fm(rdsp_engine_t *e, int W, float deviation_hz, float tau_us);
+int rdsp_engine_read_fm_level(rdsp_engine_t *e, int n_blocks, float *d_out, size_t stride, void *stream);
+float rdsp_engine_fm_atan2(float y, float x);
+int rdsp_engine_fm_constants(float deviation_hz, float tau_us, float *out /* [2]: k, a */);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

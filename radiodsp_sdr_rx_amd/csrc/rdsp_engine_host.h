@@ -3,10 +3,11 @@
  * meter as an owner, the walk over groups.  rdsp_engine_host.hip holds the sketch's settings and setters and creates, resets
  * and runs the object; rdsp_engine_groups.hip the receiver groups; rdsp_engine_meter_host.hip the signal meter's owner and
  * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
- * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_state.hip the state blob.  Host logic
- * only: the kernels are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's,
- * rdsp_engine_pack.hip's and rdsp_engine_voice.hip's, the front end is rdsp_engine_sources.h's.  All six are compiled with the
- * kernels' flags (-ffp-contract=off).
+ * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_fm_host.hip the narrow-band FM
+ * detector's; rdsp_engine_state.hip the state blob.  Host logic only: the kernels are rdsp_engine.hip's stage files'
+ * (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's, rdsp_engine_pack.hip's, rdsp_engine_voice.hip's and
+ * rdsp_engine_fm.hip's, the front end is rdsp_engine_sources.h's.  All seven are compiled with the kernels' flags
+ * (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
 #define RDSP_ENGINE_HOST_H
@@ -18,6 +19,7 @@
 #include <memory>
 #include <vector>
 
+#include "rdsp_engine_fm.h"
 #include "rdsp_engine_int.h"
 #include "rdsp_engine_laws.h"
 #include "rdsp_engine_meter.h"
@@ -31,6 +33,8 @@ using namespace rdsp_eng;
 struct EngSettings {
   float input_gain, gain_i, gain_q, iq_balance, output_gain, tuning_offset;
   int mode, mute, audio_on, audio_id, audio_set, pre_set, agc_on, als_on, als_notch, als_adaptive, nb_on, resets;
+  int nfm; /* the group demodulates narrow-band FM: setDemodMode(RDSP_ENGINE_MODE_NFM) behind rdsp_engine_enable_fm */
+  rdsp_fm::FmSet fm; /* rdsp_engine_set_fm: in force while the group is in NFM */
   EngineAgcSet agc;
   rdsp_meter::MeterSet meter; /* rdsp_engine_set_meter / set_squelch: in force once rdsp_engine_enable_meter was called */
   uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
@@ -64,6 +68,20 @@ struct EngVoice {
   hipError_t reset(hipStream_t s);                              /* the history zero */
   hipError_t launch(const int16_t *d_lr, size_t out_stride, int n_blocks, hipStream_t s); /* once per call, behind the last group's meter */
 };
+/* the narrow-band FM detector (rdsp_engine_fm_host.hip): every channel's state words, the last call's level rows, the taps */
+struct EngFm {
+  DevBuf<uint32_t> state; /* [ch][FM_STATE_WORDS] */
+  DevBuf<float> level;    /* [ch][row_words], row_words = max_blocks 128: what an NFM group's meter measures */
+  DevBuf<float> taps;     /* the 32 taps of W = 2, then the 48 of W = 3 */
+  size_t n_channels = 0, row_words = 0;
+  std::vector<std::pair<size_t, size_t>> nfm_rows; /* of the last call: first channel and count of every group that ran the detector */
+  hipError_t init(size_t n_channels, size_t max_blocks); /* every buffer; state and rows zeroed */
+  hipError_t reset(hipStream_t s);                       /* the state zero */
+  /* in place of the front and Hilbert kernels of the group p describes (channels c0 on): y into p.audio, the level rows beside it */
+  hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_fm::FmSet &set, const int16_t *d_iq, hipStream_t s);
+  /* p with the group's level rows where its demodulated rows were: what the meter of an NFM group is handed */
+  EngParams metered(EngParams p, size_t c0) const { p.audio = level + c0 * row_words; p.audio_stride = row_words; return p; }
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -81,6 +99,7 @@ struct rdsp_engine {
   std::unique_ptr<EngFrontEnd> src;
   std::unique_ptr<EngMeter> meter; /* the signal meter, from rdsp_engine_enable_meter on */
   std::unique_ptr<EngVoice> voice; /* the voice-rate audio, from rdsp_engine_enable_voice on */
+  std::unique_ptr<EngFm> fm;       /* the narrow-band FM detector, from rdsp_engine_enable_fm on */
   int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
   std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
 };

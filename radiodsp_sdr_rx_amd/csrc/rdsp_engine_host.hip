@@ -24,7 +24,13 @@ void settings_agc_mode(EngSettings &s, int mode) { /* 0xdfe0 */
 }
 void settings_demod(const rdsp_engine_t *e, EngSettings &s, int mode) { /* 0xd798 */
   s.mode = mode & 0xffff;
+  s.nfm = 0;
   switch (s.mode) {
+    case RDSP_ENGINE_MODE_NFM: /* this build's own; without rdsp_engine_enable_fm a value the engine does not know */
+      if (!e->fm) return;
+      s.nfm = 1; s.tuning_offset = 0.0f; /* the station sits at DC */
+      s.resets |= RESET_FM;
+      return;
     case 0: s.tuning_offset = (float)((double)e->if_centre + (double)e->ssb_band * 0.5); s.pre_set = 12; break;
     case 1: s.tuning_offset = (float)((double)e->if_centre - (double)e->ssb_band * 0.5); s.pre_set = 12; break;
     case 6: s.tuning_offset = (float)((double)e->if_centre - (double)e->ssb_band * 0.5); s.pre_set = 11; break;
@@ -43,6 +49,7 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.agc = engine_agc_set(0); /* 0xdf14: the medium attack with the slow decay and the fast hang time */
   s.agc_on = 1;
   s.meter.attack = rdsp_meter::ATTACK_DEFAULT; s.meter.decay = rdsp_meter::DECAY_DEFAULT; /* squelch off, thresholds and hang 0 */
+  s.fm = {rdsp_fm::FM_DEFAULT_W, rdsp_fm::FM_DEFAULT_DEVIATION, rdsp_fm::FM_DEFAULT_TAU};
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -133,6 +140,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess && e->src) err = e->src->reset(s);
   if (err == hipSuccess && e->meter) err = e->meter->reset(s);
   if (err == hipSuccess && e->voice) err = e->voice->reset(s);
+  if (err == hipSuccess && e->fm) err = e->fm->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -223,13 +231,21 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
   if (err != hipSuccess) return engine_fail("rdsp_engine_update", err);
   EngParams call = e->base;
   call.iq = (const int32_t *)d_iq; call.in_stride = in_stride; call.out = (int32_t *)d_lr; call.out_stride = out_stride; call.n_blocks = n_blocks;
+  if (e->fm) e->fm->nfm_rows.clear();
   for (size_t g = 0; g < e->grp.size(); g++) {
     EngSettings &q = e->grp[g];
     const EngParams p = group_params(e, g, call);
-    err = rdsp_engine_launch(p, q.nb_on != 0, q.als_on != 0, s);
-    if (err == hipSuccess && e->meter) err = e->meter->launch_group(p, (size_t)e->first[g], q.meter, d_lr, s);
+    const size_t c0 = (size_t)e->first[g];
+    const bool nfm = e->fm && q.nfm; /* the detector in place of the front and Hilbert kernels, the tail on what it wrote */
+    if (nfm) {
+      err = e->fm->launch_group(p, c0, q.fm, d_iq, s);
+      if (err == hipSuccess) { engine_launch_tail(p, q.als_on != 0, s); err = hipGetLastError(); }
+    } else {
+      err = rdsp_engine_launch(p, q.nb_on != 0, q.als_on != 0, s);
+    }
+    if (err == hipSuccess && e->meter) err = e->meter->launch_group(nfm ? e->fm->metered(p, c0) : p, c0, q.meter, d_lr, s); /* NFM: a carrier squelch */
     if (err != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
-    if (q.mode <= 3 || q.mode == 6) q.pos = (q.pos + (uint32_t)n_blocks * BS) & (e->ring_size - 1); /* the lines only move when the SSB / CW path runs */
+    if (!nfm && (q.mode <= 3 || q.mode == 6)) q.pos = (q.pos + (uint32_t)n_blocks * BS) & (e->ring_size - 1); /* the lines only move when the SSB / CW path runs */
     q.resets = 0;
   }
   e->last_blocks = n_blocks;

@@ -17,7 +17,7 @@ constexpr int BS = RDSP_BLOCK_SAMPLES;
 /* per-channel state, floats (ints bit-cast): [channel][NF] */
 enum { ST_PRE = 0, ST_AM = 32, ST_AUDIO = 64, ST_NCO = 80, ST_AMPH, ST_SAM_COS, ST_SAM_SIN, ST_SAM_U, ST_SAM_ERR, ST_SAM_HZ,
        ST_SAM_PH, ST_SAM_LOCK, ST_AGC_ENV, ST_AGC_GAIN, ST_AGC_HANG, ST_AGC_ACTIVE, ST_NB_AVG, ST_NB_HIT, ST_NB_LAST, NF = 96 };
-enum { RESET_PRE = 1, RESET_AUDIO = 2, RESET_ALS = 4 };
+enum { RESET_PRE = 1, RESET_AUDIO = 2, RESET_ALS = 4, RESET_FM = 8 }; /* RESET_FM: the host's and the FM kernel's (rdsp_engine_fm.h) */
 constexpr int ALS_WORDS = 256 + 64;                       /* per channel in HBM: the 256-sample line, then the taps (64 words) */
 constexpr int NB_WORDS = 3 * 384;                          /* per channel: I line, Q line, mask */
 

@@ -8,6 +8,7 @@ import numpy as np
 from ._lib import Handle, check, load, stream_ptr
 
 LSBmode, USBmode, CW_LSBmode, CW_USBmode, AMmode, SAMmode = range(6)      # as the compiled tuningMode() passes them
+NFMmode = 7                                                              # RDSP_ENGINE_MODE_NFM: this build's own, behind enable_fm()
 audioAM, audioCW, audio2100, audio2700, audio3100, audioNone = 0, 1, 3, 6, 8, 10
 AGCoff, AGCfast, AGCmedium, AGCslow = range(4)
 SRC_S16, SRC_U8, SRC_S8, SRC_F32 = range(4)                              # RDSP_SRC_*: what the source rows hold
@@ -269,6 +270,30 @@ class Engine(Handle):
         needed, written = counts()
         return audio[:written], records[:written], needed
 
+    def enable_fm(self):
+        """narrow-band FM from now on (include/rdsp.h, "narrow-band FM"): setDemodMode(NFMmode) puts the selected group(s) into
+        it, and their meter becomes a carrier squelch.  Again: a no-op.  Takes no stream and waits for the device."""
+        check(self.lib.rdsp_engine_enable_fm(self.h))
+
+    @property
+    def fm_enabled(self):
+        return bool(self.lib.rdsp_engine_fm_enabled(self.h))
+
+    def set_fm(self, W=2, deviation_hz=5000.0, tau_us=750.0):
+        """the selected group's detector: channel filter W = 2 (wide) or 3 (narrow), the deviation that reads +-1.0
+        (1000 ... 7500 Hz), the de-emphasis time constant (0: none, or 25 ... 1000 us)"""
+        check(self.lib.rdsp_engine_set_fm(self.h, int(W), float(deviation_hz), float(tau_us)))
+
+    def read_fm_level(self, n_blocks, stream=None):
+        """the last call's level rows (the magnitude behind the channel filter, 1.0 = a full-scale carrier: what an NFM group's
+        meter measures) -> float32 [n_channels, n_blocks x 128] on the device; zeros for receivers not in NFM"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks) * 128
+        out = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_fm_level(self.h, int(n_blocks), out.data_ptr(), n, stream_ptr(stream)))
+        return out
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -319,6 +344,19 @@ def voice_taps(R):
     o = np.zeros(16 * int(R) if int(R) in (2, 4) else 1, np.int32)
     check(load().rdsp_engine_voice_taps(int(R), o.ctypes.data_as(C.POINTER(C.c_int32))))
     return o
+
+
+def fm_atan2(y, x):
+    """the discriminator's arctangent, csrc/rdsp_fm.h's fm_atan2 (host only, no GPU)"""
+    return float(load().rdsp_engine_fm_atan2(float(y), float(x)))
+
+
+def fm_constants(deviation_hz=5000.0, tau_us=750.0):
+    """(k, a) of set_fm's deviation and time constant as float32: the discriminator's scale and the de-emphasis coefficient
+    (host only, no GPU)"""
+    o = np.zeros(2, np.float32)
+    check(load().rdsp_engine_fm_constants(float(deviation_hz), float(tau_us), o.ctypes.data_as(_F32P)))
+    return o[0], o[1]
 
 
 def rate_taps(P, Q, gain=1.0):
