@@ -1158,7 +1158,8 @@ int rdsp_engine_pack_voice(rdsp_engine_t *e, int n_blocks, int16_t *d_audio /* [
  *   5. De-emphasis.  a = (float)(1.0 / (1.0 + 44100.0 (double) tau_us 1e-6)); y[n] = fmaf(a, u[n] - y[n - 1], y[n - 1]).
  *      tau_us == 0 bypasses the stage (y = u).  rdsp_engine_fm_constants writes {k, a}; host only, no GPU.
  *   6. Output.  y[n] is the "demod" tap (rdsp_engine_read_demod); the tail runs on it with the group's settings.  The useful
- *      combination is one of the audio band-passes (they remove sub-audible tones) with the AGC off.
+ *      combination is one of the audio band-passes (they remove sub-audible tones from the audio; the tone squelch below
+ *      listens for them on this tap, in front of those filters) with the AGC off.
  *   7. Meter.  For a group in NFM the meter is handed the level rows in place of the demodulated ones: level, peak, gate, hang,
  *      the zeroing of closed blocks, the active list, rdsp_engine_pack_active, the voice stage and rdsp_engine_pack_voice work
  *      unchanged.  Thresholds stay mean squares.
@@ -1192,6 +1193,70 @@ int rdsp_engine_set_fm(rdsp_engine_t *e, int W, float deviation_hz, float tau_us
 int rdsp_engine_read_fm_level(rdsp_engine_t *e, int n_blocks, float *d_out, size_t stride, void *stream);
 float rdsp_engine_fm_atan2(float y, float x);
 int rdsp_engine_fm_constants(float deviation_hz, float tau_us, float *out /* [2]: k, a */);
+/* Tone squelch (CTCSS).  Repeater outputs and shared simplex channels carry several user groups on one frequency, separated by
+ * a sub-audible tone (67.0 ... 254.1 Hz at 10 ... 15 % of the peak deviation); a receiver set to one group stays shut for the
+ * others, and for interference that opens a carrier gate.  After rdsp_engine_enable_tone(e) every NFM group runs one more kernel
+ * behind its meter kernel (behind its tail kernel without a meter): a correlator per receiver at the receiver's own tone, on the
+ * "demod" tap, where +-1.0 is the peak deviation -- so a tone's amplitude there is a physical quantity and needs no AGC or
+ * reference level.  The tone is per CHANNEL (rdsp_engine_set_tones, as rdsp_engine_tune gives one station per channel), the
+ * window and the thresholds per GROUP (rdsp_engine_set_tone_squelch).  Opt-in: an engine that never calls
+ * rdsp_engine_enable_tone allocates, launches, returns and saves what it did before.  The arithmetic is csrc/rdsp_tone.h's.
+ *   a[n] is the receiver's "demod" tap, y[n] of step 6 above: what rdsp_engine_read_demod returns.  Per channel:
+ *   1. Step.  dphi = (uint32) llround((double) tone_hz 2^32 / 44100.0); tone_hz is 0 (no tone, the default) or in [60, 300].
+ *   2. Block correlation.  The phase ph is a uint32.  For t = 0 ... 127 of a block: (c, s) = the tuning pass's phasor at
+ *      ph + t dphi (the 1024-entry table of rdsp_engine_tune_table and its interpolation, unchanged; the detector keeps a copy of
+ *      its own); pr[t] = a[t] c, pi[t] = a[t] s, one rounded product each; Sr, Si = their sums by the meter's balanced binary
+ *      tree over adjacent pairs.  Then re = re + Sr, im = im + Si (one add each), ph += 128 dphi, cnt += 1.
+ *   3. Window.  K blocks, non-overlapping, counted from the detector's last reset.  When cnt == K:
+ *      a2 = fmaf(re, re, im im) scale, scale = (float)(4.0 / ((128.0 K) (128.0 K))): the squared amplitude of a sinusoid at the
+ *      tone's frequency; tone = a2 >= (tone ? off2 : on2), on2 = on_amp on_amp and off2 = off_amp off_amp as float products;
+ *      then re = im = 0 and cnt = 0.
+ *   4. Records.  After block b of a call: a2_rec[ch][b] = a2, the last completed window's value (0 before the first), and
+ *      tone_rec[ch][b] = tone.
+ *   5. Gate.  Only with the meter on, and only for a channel with dphi != 0: open[ch][b] <- open[ch][b] & tone_rec[ch][b] in the
+ *      meter's per-call record; a block closed this way is written as 128 zero words, exactly what the meter writes for its own
+ *      closed blocks; the channel's entry in the active list follows the combined records.  The meter's signal state (level,
+ *      open, hang) is NOT touched: the carrier gate evolves as it does without the detector.  So rdsp_engine_read_meter's
+ *      d_open, rdsp_engine_active, rdsp_engine_pack_active, the voice stage and rdsp_engine_pack_voice see the COMBINED gate,
+ *      while rdsp_engine_get_meter's fourth value stays the CARRIER gate.  With the meter's squelch off (always open) the tone
+ *      gate works alone.  Without the meter nothing is gated: the records are all there is.
+ *   6. Everything is a function of whole blocks counted from a reset: a stream gives the same bits however it is cut into calls.
+ *   Latency: the gate opens at the end of the first full window that carries the tone, so up to two windows of a transmission's
+ *     start are lost (K = 128 blocks: 0.37 s a window), and it closes a window after the tone stops.  This is the nature of tone
+ *     squelch.
+ *   State: per channel 8 words -- dphi, K, ph, re, im, cnt, tone, a2.  At the start of a call the stored dphi and K are compared
+ *     with the channel's current tone and its group's K; if either differs the detector starts from zeros (tone = 0, a2 = 0).
+ *     That one rule covers a changed tone, a changed K, a regrouping into a group with another K and a loaded blob that does not
+ *     match.  A channel with dphi == 0 has its words and its records written as zeros and is not gated.  Signal state: it stays
+ *     with the channel through rdsp_engine_set_groups, is zeroed by rdsp_engine_reset and by the group's pending FM reset at the
+ *     next update, is maintained only while the group is in NFM, and travels in rdsp_engine_save_state / load_state as a fifth
+ *     optional part: header flag 16, 8 words per channel, behind the FM words; rdsp_engine_state_bytes says so.  The blob of an
+ *     engine without the detector is unchanged; a blob with the part is refused by an engine without it (RDSP_ERR_NOT_READY,
+ *     nothing changed); a blob without it zeroes the words of the channels it lands on.
+ * - rdsp_engine_enable_tone works as rdsp_engine_enable_fm does: it takes no stream, waits for everything queued on the engine's
+ *   device, then allocates 32 bytes of state and 4 bytes of step per channel, 5 bytes per channel and block of max_blocks and the
+ *   16 KiB table; if that fails the object is as it was (RDSP_ERR_NOMEM).  Again: RDSP_OK, nothing changed.  It needs
+ *   rdsp_engine_enable_fm first (RDSP_ERR_NOT_READY) and does not need the meter.
+ * - rdsp_engine_set_tones(e, first_channel, n_channels, tone_hz): the tones of a channel range from a HOST array, kept in a host
+ *   mirror and uploaded stream-ordered at the next update, as rdsp_engine_tune's steps are.  Settings: kept by reset, in no
+ *   blob, and they may precede rdsp_engine_enable_tone.  A NaN or a value outside {0} and [60, 300] anywhere in the array, a NULL
+ *   array or a range outside the object: RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_set_tone_squelch(e, K, on_amp, off_amp): settings of the selected group(s), copied by a new group, kept by
+ *   reset, in no blob.  K in 4 ... 512; 0 < off_amp <= on_amp <= 1; the defaults are 128, 0.04, 0.025.  Anything else:
+ *   RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_read_tone copies the last call's records, [ch][n_blocks] with the given strides (elements), into the caller's
+ *   DEVICE buffers, stream-ordered; either pointer may be NULL; rows of receivers the detector did not run on read as zeros.
+ *   RDSP_ERR_NOT_READY before rdsp_engine_enable_tone; RDSP_ERR_INVALID for n_blocks negative or above the last call's, a stride
+ *   below n_blocks.
+ * - rdsp_engine_tone_gain(tone_hz, tau_us), host only: the magnitude of the de-emphasis of step 5 above at tone_hz, in double
+ *   (1.0 for tau_us == 0), with which a caller turns "tone deviation in Hz" into a threshold on the tap: a tone at d Hz of
+ *   deviation reads d / deviation_hz x gain.  0.0 for a tone_hz outside (0, 22050) or a tau_us rdsp_engine_set_fm refuses. */
+int rdsp_engine_enable_tone(rdsp_engine_t *e);
+int rdsp_engine_tone_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_tones(rdsp_engine_t *e, int first_channel, int n_channels, const float *tone_hz /* host */);
+int rdsp_engine_set_tone_squelch(rdsp_engine_t *e, int K, float on_amp, float off_amp);
+int rdsp_engine_read_tone(rdsp_engine_t *e, int n_blocks, float *d_a2, size_t a2_stride, uint8_t *d_tone, size_t tone_stride, void *stream);
+double rdsp_engine_tone_gain(float tone_hz, float tau_us);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

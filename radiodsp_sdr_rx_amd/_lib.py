@@ -322,6 +322,12 @@ SYMBOLS = [
     ("rdsp_engine_read_fm_level", _i, [_vp, _i, _vp, _sz, _vp]),
     ("rdsp_engine_fm_atan2", C.c_float, [C.c_float, C.c_float]),
     ("rdsp_engine_fm_constants", _i, [C.c_float, C.c_float, _f32p]),
+    ("rdsp_engine_enable_tone", _i, [_vp]),
+    ("rdsp_engine_tone_enabled", _i, [_vp]),
+    ("rdsp_engine_set_tones", _i, [_vp, _i, _i, _f32p]),
+    ("rdsp_engine_set_tone_squelch", _i, [_vp, _i, C.c_float, C.c_float]),
+    ("rdsp_engine_read_tone", _i, [_vp, _i, _vp, _sz, _vp, _sz, _vp]),
+    ("rdsp_engine_tone_gain", C.c_double, [C.c_float, C.c_float]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

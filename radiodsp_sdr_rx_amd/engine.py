@@ -294,6 +294,37 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_fm_level(self.h, int(n_blocks), out.data_ptr(), n, stream_ptr(stream)))
         return out
 
+    def enable_tone(self):
+        """the CTCSS tone squelch from the next update on (include/rdsp.h, "tone squelch"): every NFM group runs a correlator per
+        receiver at the receiver's tone and, with the meter on, closes the blocks that do not carry it.  After enable_fm();
+        again: a no-op.  Takes no stream and waits for the device; does not need the meter."""
+        check(self.lib.rdsp_engine_enable_tone(self.h))
+
+    @property
+    def tone_enabled(self):
+        return bool(self.lib.rdsp_engine_tone_enabled(self.h))
+
+    def set_tones(self, first_channel, tone_hz):
+        """receivers first_channel ... get the tones tone_hz (Hz: 0 for none, or 60 ... 300); may precede enable_tone()"""
+        t = np.ascontiguousarray(np.atleast_1d(tone_hz), np.float32)
+        check(self.lib.rdsp_engine_set_tones(self.h, int(first_channel), t.size, t.ctypes.data_as(_F32P)))
+
+    def set_tone_squelch(self, K=128, on_amp=0.04, off_amp=0.025):
+        """the selected group's detector: windows of K blocks (4 ... 512); the tone is there from an amplitude of on_amp on the
+        demodulated tap (1.0: the peak deviation) and until it falls below off_amp"""
+        check(self.lib.rdsp_engine_set_tone_squelch(self.h, int(K), float(on_amp), float(off_amp)))
+
+    def read_tone(self, n_blocks, stream=None):
+        """the last call's records -> (a2 float32: the squared tone amplitude of the last completed window, tone uint8), each
+        [n_channels, n_blocks] on the device; zeros for receivers the detector did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        a2 = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        tone = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        check(self.lib.rdsp_engine_read_tone(self.h, n, a2.data_ptr(), n, tone.data_ptr(), n, stream_ptr(stream)))
+        return a2, tone
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -357,6 +388,15 @@ def fm_constants(deviation_hz=5000.0, tau_us=750.0):
     o = np.zeros(2, np.float32)
     check(load().rdsp_engine_fm_constants(float(deviation_hz), float(tau_us), o.ctypes.data_as(_F32P)))
     return o[0], o[1]
+
+
+def tone_gain(tone_hz, tau_us=750.0):
+    """the magnitude of the NFM de-emphasis at tone_hz (1.0 for tau_us == 0): a tone at d Hz of deviation reads
+    d / deviation_hz x tone_gain on the demodulated tap (host only, no GPU)"""
+    g = float(load().rdsp_engine_tone_gain(float(tone_hz), float(tau_us)))
+    if g == 0.0:
+        check(-1)
+    return g
 
 
 def rate_taps(P, Q, gain=1.0):
