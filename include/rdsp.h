@@ -361,7 +361,10 @@ int rdsp_chain_set_priorities(rdsp_chain_t *c, int front_fir_prio, int tail_prio
  * One more thing decides how the wave-wide frequency-domain forms (2, 4 and the default beside a tail stage) round: the
  * number of receiver groups.  A chain of at most 64 groups keeps, per group, the decimator's branch spectra multiplied by
  * the mixer's rotations of the branches (rebuilt on the host at every retune) and mixes every branch with one phasor per
- * quad column; above 64 groups each branch's phasors are rotated per frame on the device.  The same arithmetic to 1e-7
+ * quad column; above 64 groups each branch's phasors are rotated per frame on the device.  Where the filter's transform
+ * is at most 1024 points long, a chain of at most 64 groups goes one step further: it keeps the branch spectra of the
+ * decimator's taps shifted by the group's tuning offset, transforms the unmixed samples and mixes behind the decimator, on
+ * a quarter of the samples (FFT_L 2048 and 4096 keep the rotated spectra).  The same arithmetic to 1e-6
  * of the output's peak, not to the bit: rdsp_chain_set_groups across that threshold changes the last bits of what
  * follows, like a change of variant.  Within either range calls, splits, pipelining and sub-batches give the bits they
  * gave before. */

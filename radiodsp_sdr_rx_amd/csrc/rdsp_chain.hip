@@ -384,6 +384,7 @@ static void front_params(rdsp_chain_t *c, Call &k) {
   if (c->fir_mode == -1 && fp.fir_fd == 2 && !fp.to_mid) fp.fir_fd = 3;
   fp.fd_mask = c->d_fd_mask;
   fp.rot_pool = c->d_rot_pool; /* null above RDSP_FD_ROT_GROUPS groups: the instance that rotates per frame (rdsp_front_pick_rotg) */
+  fp.fd_shift = c->d_rot_pool && rdsp_fd_shift_plan(c->N); /* what group_stage_rot fills the pool with */
   fp.rd_mask = c->d_rd_mask;
   RdspFrontPick pick; /* the kernel this call runs, for the timing records (a refusal leaves the name: the launch reports it) */
   if (rdsp_front_pick(c->N, c->decim, &fp, &pick) == 0) c->front_name = rdsp_front_kernel_name(pick.family);

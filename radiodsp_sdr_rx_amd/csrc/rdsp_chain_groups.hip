@@ -103,15 +103,19 @@ static void group_record(const rdsp_chain_t *c, const GroupState &g, int gi, Rds
   r->rothp3 = nco_rot(r->dphi_hist, 12 * nt);
 }
 
-/* Group gi's rotated branch spectra for its current tuning offset, into the half of its slot that the device record does
- * not point to; the record written right behind it (chain_groups_commit) switches over.  The copy is queued on the
+/* Group gi's rotated branch spectra for its current tuning offset -- where the NCO runs behind the decimator, the spectra of
+ * the shifted taps (rdsp_fd_shift_plan) -- into the half of its slot that the device record does not point to; the record written right behind it (chain_groups_commit) switches over.  The copy is queued on the
  * processing stream itself, behind every front kernel launched so far (the fence covers launches on another stream), so
  * nothing that still reads that half -- it was live two retunes ago -- runs beside it. */
 static int group_stage_rot(rdsp_chain_t *c, int gi, uint32_t dphi, hipStream_t stream) {
   GroupState &g = c->groups[(size_t)gi];
   float *img;
   RC_TRY(g.rot.begin_fill(&img));
-  rdsp_fd_rot_image(c->fd_img.data(), RDSP_FD_N, dphi, img);
+  if (rdsp_fd_shift_plan(c->N)) { /* the NCO behind the decimator: the spectra of the shifted taps */
+    if (rdsp_fd_shift_image(c->fir_nat.data(), RDSP_FD_N, dphi, img) != 0) return chain_fail(RDSP_ERR_NOMEM, "shifted branch spectra");
+  } else {
+    rdsp_fd_rot_image(c->fd_img.data(), RDSP_FD_N, dphi, img);
+  }
   RC_TRY(g.rot.upload(c->d_rot_pool, gi, group_fence(c), stream));
   g.rot_dphi = dphi;
   g.rot_valid = true;

@@ -131,7 +131,8 @@ struct rdsp_chain {
   DevBuf<float2> d_rd_mask; /* [4][256] the same for the 256-point windows of the row forms */
   std::vector<float> fd_img;     /* d_fd_mask's contents on the host: what the groups' rotated spectra are made from */
   DevBuf<float2> d_rot_pool;     /* [n_groups][2][4][512] rot_r x d_fd_mask per group (RdspFrontParams::rot_pool); chains of
-                                    at most RDSP_FD_ROT_GROUPS groups with decimation 4, else none */
+                                    at most RDSP_FD_ROT_GROUPS groups with decimation 4, else none.  On the one-wave plans
+                                    (rdsp_fd_shift_plan) the spectra of fir_nat shifted by the group's increment instead */
   DevBuf<float> d_sin_table; /* [513] sinTable_f32 (spectral stage as written, rdsp_set_spectral_resynthesis); made on first use */
   int spectral_literal = 0;
   /* rdsp_sdr_set_engine_literal: the reference's own pre-processor and engine in front of the CONV stage (INO:53-54,71-86) */

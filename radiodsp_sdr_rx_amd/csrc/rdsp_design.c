@@ -241,6 +241,69 @@ void rdsp_fd_rot_image(const float *image, int fft_l, uint32_t dphi, float *out)
   }
 }
 
+/* One group's slot of the pool for the instances that run the NCO behind the decimator (SHF, rdsp_front_fd.hip): the
+ * branch spectra of the frequency-shifted taps.  With the mixer's increment theta = 2 pi dphi / 2^32 per input sample
+ * (rdsp_nco_rot's angle),
+ *     sum_k h[k] x[4m - k] exp(-j theta (4m - k)) = exp(-j theta 4m) sum_k (h[k] exp(+j theta k)) x[4m - k],
+ * so branch r takes g_r[k] exp(+j theta (4k - r)), g_r[k] = h[4k - r] as in rdsp_fd_decimator_image: its N-point DFT
+ * divided by N, in the layout of fd_mask.  The 65 tap phases are exact 32-bit products, the transform is a radix-2 one in
+ * double with a table of N/2 roots: 4 x 65 + N/2 cos/sin pairs per call instead of one per tap and bin, and one rounding
+ * per value, at the end.  fft_l: a power of two that rdsp_plan_radix knows; returns 0, -1 (no such plan) or -6 (memory). */
+int rdsp_fd_shift_image(const float *h_nat, int fft_l, uint32_t dphi, float *out) {
+  const int P = rdsp_plan_radix(fft_l);
+  if (P == 0 || fft_l < 128 || (fft_l & (fft_l - 1))) return -1;
+  const int n = fft_l, nt = n / P, logn = ilog2i(n);
+  double *wr = (double *)malloc(sizeof(double) * 3 * (size_t)n + sizeof(int) * 2 * (size_t)n);
+  if (!wr) return -6;
+  double *wi = wr + n / 2, *ar = wr + n, *ai = ar + n;
+  int *bin_at = (int *)(ai + n), *rev_of = bin_at + n; /* the image's bin order; bit reversal */
+  for (int m = 0; m < n / 2; m++) {
+    const double a = -2.0 * kPi * (double)m / (double)n;
+    wr[m] = cos(a);
+    wi[m] = sin(a);
+  }
+  for (int i = 0; i < n; i++) {
+    bin_at[i] = rdsp_bin_of_pos(n, i);
+    int rev = 0;
+    for (int b = 0; b < logn; b++) rev |= ((i >> b) & 1) << (logn - 1 - b);
+    rev_of[i] = rev;
+  }
+  const double inv_n = 1.0 / (double)n;
+  for (int r = 0; r < 4; r++) {
+    for (int i = 0; i < n; i++) ar[i] = ai[i] = 0.0;
+    for (int k = 0; k <= 64; k++) { /* in bit-reversed order: the passes below run in place and leave natural order */
+      const int t = 4 * k - r;
+      if (t < 0 || t >= 256) continue;
+      const uint32_t ph = dphi * (uint32_t)t;
+      const double a = 2.0 * kPi * (double)ph / 4294967296.0;
+      ar[rev_of[k]] = (double)h_nat[t] * cos(a);
+      ai[rev_of[k]] = (double)h_nat[t] * sin(a);
+    }
+    for (int half = 1; half < n; half *= 2) {
+      const int step = n / (2 * half);
+      for (int base = 0; base < n; base += 2 * half)
+        for (int i = 0; i < half; i++) {
+          const double c = wr[i * step], s = wi[i * step];
+          const int u = base + i, v = u + half;
+          const double tr = ar[v] * c - ai[v] * s, ti = ar[v] * s + ai[v] * c;
+          ar[v] = ar[u] - tr;
+          ai[v] = ai[u] - ti;
+          ar[u] += tr;
+          ai[u] += ti;
+        }
+    }
+    for (int t = 0; t < nt; t++)
+      for (int e = 0; e < P; e++) {
+        const int bin = bin_at[t * P + e];
+        const size_t o = (size_t)r * (size_t)n + (size_t)e * (size_t)nt + (size_t)t;
+        out[2 * o] = (float)(ar[bin] * inv_n);
+        out[2 * o + 1] = (float)(ai[bin] * inv_n);
+      }
+  }
+  free(wr);
+  return 0;
+}
+
 /* The same branch spectra for the decimator on 16-lane rows (rdsp_front_rd_kernel): 256-point windows, 16 points per
  * lane, bin i + 16 e of lane i at [r][16 e + i]; /256 (the inverse transform is unnormalised). */
 int rdsp_rd_decimator_image(const float *h_nat, float *image) {

@@ -74,9 +74,23 @@ struct FrontFdLds {
  * slot of p.rot_pool (filled on the host at every retune, the layout of fd_mask) and every branch is mixed with the column
  * phasors pj[j] alone: 24 complex products per frame and lane less, and rot1..3 out of the scalar registers.  Only column 0
  * of the first frame behind a retune was mixed with other rotations (roth_r): its phasor takes roth_r conj(rot_r) there.
- * The two forms round differently (1e-7); which one a chain runs depends on its number of groups alone (include/rdsp.h). */
-template <int N, int P, bool LEAN, bool PRE, bool Q4 = false, int VC = RDSP_FD_P - 1, bool ROTG = false>
+ * The two forms round differently (1e-7); which one a chain runs depends on its number of groups alone (include/rdsp.h).
+ *
+ * SHF (with ROTG, the one-wave plans: rdsp_front_pick_shift): the NCO runs behind the decimator.  For a constant increment
+ *     sum_k h[k] x[4m - k] exp(-j theta (4m - k)) = exp(-j theta 4m) sum_k (h[k] exp(+j theta k)) x[4m - k]:
+ * the branch transforms take the converted raw samples, the group's slot of p.rot_pool holds the spectra of the shifted
+ * taps (rdsp_fd_shift_image) and the frame's 64 VC outputs are multiplied by gain x exp(-j phi) at their absolute input
+ * index before they go into the ring: VC complex products per frame and lane in place of 4 (VC + 1), the column phasors
+ * (one nco_phasor_alu from the absolute position, then rotq1..3) on the output side, and no phasor live across the
+ * transforms.  Column 0 of the first frame behind a retune came in under dphi_hist: there only, its raw samples take the
+ * per-sample phasor of the increment difference, so that the window is consistent with the new theta.
+ * Gains: one common gain in the frame's window (every column's I and Q gain, the history's included) rides on the output
+ * phasor; anything else is scaled per sample, every column with its own two gains, and the phasor carries none.  The rule
+ * looks at the frame's own columns only and is the same with and without PRE (without PRE the launch code guarantees one
+ * gain), so a sample rounds the same whichever of the two kernels runs its frame. */
+template <int N, int P, bool LEAN, bool PRE, bool Q4 = false, int VC = RDSP_FD_P - 1, bool ROTG = false, bool SHF = false>
 __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams p) {
+  static_assert(!SHF || (ROTG && N / P == 64), "the shifted spectra come from the pool; one-wave plans");
   using PL = FftPlan<N, P>;              /* the overlap-save filter's transform (FFT_L)     */
   constexpr int ND = RDSP_FD_N, PD = RDSP_FD_P; /* the decimator's: 512 points whatever FFT_L is  */
   using PLD = FftPlan<ND, PD>;
@@ -301,12 +315,16 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams
      * looks at the column's own gains only, in the kernels with and without PRE alike (without PRE the launch
      * code guarantees one gain, history included), so how a sample rounds does not depend on which of the two
      * kernels a call split happens to run it through */
-    const bool fold = !PRE || p.scale_i == p.scale_q, fold0 = !PRE || si0 == sq0;
+    /* SHF: the phasor is on the output side, behind the sum over the window's columns: it can carry one gain only, the
+     * one every column of this frame has (the kernel's comment) */
+    const bool one = p.scale_i == p.scale_q && si0 == p.scale_i && sq0 == p.scale_q;
+    const bool fold = !PRE || (SHF ? one : p.scale_i == p.scale_q), fold0 = !PRE || (SHF ? one : si0 == sq0);
     const float gph = fold ? p.scale_i : 1.0f, gph0 = fold0 ? si0 : 1.0f;      /* on the phasor ...           */
     const float sxi = fold ? 1.0f : p.scale_i, sxq = fold ? 1.0f : p.scale_q;  /* ... or on the samples (x 1.0 is exact) */
     const float sxi0 = fold0 ? 1.0f : si0, sxq0 = fold0 ? 1.0f : sq0;
+    const bool retuned = hist && dphi_hist != G.dphi; /* column 0 came in under another increment */
     float2 pj[NC];
-    {
+    if constexpr (!SHF) {
       float2 b1u = make_float2(1.f, 0.f);
       if (G.dphi != 0u) b1u = nco_phasor_alu((nq + 256u) * G.dphi);
       const float2 b1 = make_float2(b1u.x * gph, b1u.y * gph); /* the gain first, the rotations after it */
@@ -350,6 +368,12 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams
         if (j == 0 ? swap0 : SWAP_IQ) w = __builtin_amdgcn_alignbit(w, w, 16);
         float2 x = make_float2((float)(int16_t)(w & 0xFFFFu), (float)(int16_t)(w >> 16));
         if constexpr (PRE) x = make_float2(x.x * (j == 0 ? sxi0 : sxi), x.y * (j == 0 ? sxq0 : sxq));
+        if constexpr (SHF) {
+          /* raw samples; behind a retune the history column turns by the difference of the two increments, per sample */
+          if (j == 0 && retuned) x = cmul_pinned(x, nco_phasor_alu((nq + (uint32_t)r) * (dphi_hist - G.dphi)));
+          v[j] = x;
+          continue;
+        }
         float2 ph = pj[j];
         if constexpr (ROTG) {
           /* rot_r rides on the branch's spectrum; the history column behind a retune came in under roth_r */
@@ -401,6 +425,20 @@ __global__ void __launch_bounds__(N / P, 2) rdsp_front_fd_kernel(RdspFrontParams
       inv_pass0_load<ND, PD>(lbd, acc, wbd, twp);
     }
     /* acc[j] = y at window index lane + 64 j; index 64 (j = 1) is output fr*VAL of the call */
+    if constexpr (SHF) {
+      /* the NCO, on the decimated samples: output j stands at input column j of the window (nq + 256 j), its phasor a
+       * function of that absolute position -- and of the window's common gain, if it has one */
+      float2 b1u = make_float2(1.f, 0.f);
+      if (G.dphi != 0u) b1u = nco_phasor_alu((nq + 256u) * G.dphi);
+      float2 po[NC];
+      po[1] = make_float2(b1u.x * gph, b1u.y * gph); /* the gain first, the rotations after it */
+      if constexpr (NC > 2) po[2] = cmul_pinned_u(po[1], G.rotq1);
+      if constexpr (NC > 3) po[3] = cmul_pinned_u(po[1], G.rotq2);
+#pragma unroll
+      for (int j = 4; j < NC; j++) po[j] = cmul_pinned_u(po[j - 3], G.rotq3);
+#pragma unroll
+      for (int j = 1; j < NC; j++) acc[j] = cmul_pinned(acc[j], po[j]);
+    }
     {
       /* a frame's outputs start at a multiple of 64 in the ring, so a column of 64 never wraps: the wrap is
        * scalar arithmetic per column, one vector add per store (past the end of the call: slots nobody
@@ -493,17 +531,17 @@ inline size_t granule_form_lds_pad(int to_mid) {
   return 0;
 }
 
-template <int N, int P, bool LEAN, bool PRE, bool Q4, int VC, bool ROTG>
+template <int N, int P, bool LEAN, bool PRE, bool Q4, int VC, bool ROTG, bool SHF>
 int launch_fd(const RdspFrontParams *p, int n_channels, hipStream_t stream) {
   constexpr size_t lds = FrontFdLds<N, P, Q4>::BYTES;
   static_assert(!Q4 || lds <= 48 * 1024, "no raised dynamic-LDS limit needed");
   if constexpr (lds > 48 * 1024) {
-    int e = ensure_lds_limit<&rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC, ROTG>>(lds);
+    int e = ensure_lds_limit<&rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC, ROTG, SHF>>(lds);
     if (e != 0) return e;
   }
   size_t ask = lds;
   if constexpr (!Q4 && lds <= 16 * 1024) ask = lds + granule_form_lds_pad(p->to_mid);
-  hipLaunchKernelGGL((rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC, ROTG>), dim3(n_channels), dim3(N / P), ask, stream, *p);
+  hipLaunchKernelGGL((rdsp_front_fd_kernel<N, P, LEAN, PRE, Q4, VC, ROTG, SHF>), dim3(n_channels), dim3(N / P), ask, stream, *p);
   return (int)hipGetLastError();
 }
 
@@ -523,9 +561,13 @@ int rdsp::front_fd_launch(int fft_l, const RdspFrontPick &k, const RdspFrontPara
           constexpr bool LEAN = decltype(lean)::value, PRE = decltype(pre)::value, Q4 = decltype(q4)::value;
           if constexpr (fd_instance<N, P, LEAN, Q4>)
             return with_flag(rdsp_front_pick_rotg(p) != 0, [&](auto rotg) {
-              constexpr bool ROTG = decltype(rotg)::value;
-              return k.frame == 4 ? launch_fd<N, P, LEAN, PRE, Q4, 4, ROTG>(p, n_channels, stream)
-                                  : launch_fd<N, P, LEAN, PRE, Q4, RDSP_FD_P - 1, ROTG>(p, n_channels, stream);
+              return with_flag(rdsp_front_pick_shift(fft_l, p) != 0, [&](auto shf) {
+                constexpr bool ROTG = decltype(rotg)::value, SHF = decltype(shf)::value;
+                if constexpr (SHF && !(ROTG && N / P == 64)) return (int)hipErrorInvalidValue; /* no such instance */
+                else
+                  return k.frame == 4 ? launch_fd<N, P, LEAN, PRE, Q4, 4, ROTG, SHF>(p, n_channels, stream)
+                                      : launch_fd<N, P, LEAN, PRE, Q4, RDSP_FD_P - 1, ROTG, SHF>(p, n_channels, stream);
+              });
             });
           else return (int)hipErrorInvalidValue;
         });

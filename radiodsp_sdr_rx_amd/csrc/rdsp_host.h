@@ -17,6 +17,8 @@ void rdsp_mask_device_image(const float *mask_nat, int fft_l, float *image);
 int rdsp_design_decimator(int ntaps, double cut_hz, double fs, int window, float *h_nat, float *hc);
 int rdsp_fd_decimator_image(const float *h_nat, int fft_l, float *image);
 void rdsp_fd_rot_image(const float *image, int fft_l, uint32_t dphi, float *out); /* [4][fft_l] float2 each */
+/* [4][fft_l] float2: the branch spectra of the taps shifted by dphi (the NCO behind the decimator), fd_mask's layout */
+int rdsp_fd_shift_image(const float *h_nat, int fft_l, uint32_t dphi, float *out);
 int rdsp_rd_decimator_image(const float *h_nat, float *image);
 uint32_t rdsp_nco_dphi(double hz, double fs);
 void rdsp_nco_rot(uint32_t dphi, int k, float *out2);

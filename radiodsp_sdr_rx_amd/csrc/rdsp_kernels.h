@@ -93,6 +93,8 @@ struct RdspFrontParams {
   const float2 *rot_pool;  /* [n_groups][2][4][RDSP_FD_N] per group rot_r x the spectra of fd_mask, r = 0..3 (double-buffered
                               like mask_pool; RdspGroup::rot_off); null: chains of more than RDSP_FD_ROT_GROUPS groups, and
                               chains without the frequency-domain decimator */
+  int fd_shift;            /* 1: rot_pool holds the spectra of the frequency-shifted taps instead (rdsp_fd_shift_image) and the
+                              instances that run the NCO behind the decimator read it (SHF, rdsp_front_pick_shift) */
 };
 /* Up to this many groups a chain keeps pre-rotated branch spectra per group (rot_pool) and its frequency-domain front
  * kernel is the instance that reads them (ROTG).  16 KiB per group at 512 points: the tables of the groups one XCD serves
@@ -233,6 +235,10 @@ int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, RdspFrontPic
 /* the one more choice inside the RDSP_FRONT_FD family: 1 when the call runs the instances that read the groups' pre-rotated
  * branch spectra (ROTG) -- the chain has a rot_pool, which it keeps up to RDSP_FD_ROT_GROUPS groups -- else 0, today's */
 int rdsp_front_pick_rotg(const RdspFrontParams *p);
+/* and among those: 1 when the pool holds the spectra of the frequency-shifted taps and the call runs the instances with the
+ * NCO behind the decimator (SHF): the one-wave plans, FFT_L <= 1024 (rdsp_fd_shift_plan); the four-wave plans keep ROTG */
+int rdsp_front_pick_shift(int fft_l, const RdspFrontParams *p);
+int rdsp_fd_shift_plan(int fft_l); /* 1: a chain of this FFT_L fills its pool with shifted spectra */
 const char *rdsp_front_kernel_name(int family); /* "rdsp_front_kernel", "rdsp_front_fd_kernel", "rdsp_front_rd_kernel" */
 int rdsp_launch_tail(const RdspTailParams *p, int lanes_per_channel, hipStream_t stream);
 int rdsp_launch_sam(const RdspSamParams *p, hipStream_t stream);

@@ -116,6 +116,15 @@ extern "C" int rdsp_front_pick(int fft_l, int decim, const RdspFrontParams *p, R
  * while it has at most RDSP_FD_ROT_GROUPS groups (chain_groups_resize), and with one the instances that read it run */
 extern "C" int rdsp_front_pick_rotg(const RdspFrontParams *p) { return p->rot_pool != nullptr; }
 
+/* SHF, inside ROTG: the NCO behind the decimator, on a quarter of the samples, the pool holding the spectra of the
+ * frequency-shifted taps.  The one-wave plans take it; the four-wave plans (FFT_L >= 2048) keep the rotated spectra: a
+ * run-time form of this lost there once (docs/history.md) and this form has not been timed on K4.  The chain fills the pool
+ * by the same rule (rdsp_fd_shift_plan) and says so in fd_shift. */
+extern "C" int rdsp_fd_shift_plan(int fft_l) { return fft_l <= 1024; }
+extern "C" int rdsp_front_pick_shift(int fft_l, const RdspFrontParams *p) {
+  return rdsp_front_pick_rotg(p) && p->fd_shift && rdsp_fd_shift_plan(fft_l);
+}
+
 extern "C" const char *rdsp_front_kernel_name(int family) {
   return family == RDSP_FRONT_RD ? "rdsp_front_rd_kernel" : (family == RDSP_FRONT_FD ? "rdsp_front_fd_kernel" : "rdsp_front_kernel");
 }
