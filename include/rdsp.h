@@ -1260,6 +1260,84 @@ int rdsp_engine_set_tones(rdsp_engine_t *e, int first_channel, int n_channels, c
 int rdsp_engine_set_tone_squelch(rdsp_engine_t *e, int K, float on_amp, float off_amp);
 int rdsp_engine_read_tone(rdsp_engine_t *e, int n_blocks, float *d_a2, size_t a2_stride, uint8_t *d_tone, size_t tone_stride, void *stream);
 double rdsp_engine_tone_gain(float tone_hz, float tau_us);
+/* Tone search (CTCSS).  The tone squelch above holds a receiver shut until ITS tone is there; the tone search tells a caller WHICH
+ * tone a channel carries -- receivers parked on stations a band survey found know their frequencies and not their tones.  After
+ * rdsp_engine_enable_tone_search(e) every NFM group whose search window K is above 0 runs one more kernel behind its tone-squelch
+ * kernel: a bank of correlators per receiver, one per tone of the engine's bank, on the "demod" tap decimated by 32.  It only
+ * measures: it reads the demodulated rows and writes its own records and words; the audio, the meter's records and the active
+ * list are untouched, and acting on the result (rdsp_engine_set_tones) is the caller's.  Opt-in: an engine that never calls
+ * rdsp_engine_enable_tone_search allocates, launches, returns and saves what it did before.  It is independent of
+ * rdsp_engine_enable_tone: each works without the other.  The arithmetic is csrc/rdsp_tone_search.h's.
+ *   a[n] is the receiver's "demod" tap, the row the tone squelch reads; blocks of 128 samples are counted from the detector's
+ *   last reset.
+ *   1. Bank (one per engine, a setting).  n_tones frequencies, 1 <= n_tones <= 64, each in [60, 300] Hz, strictly ascending; the
+ *      default is the 50 standard CTCSS tones 67.0 ... 254.1 Hz of the EIA list (rdsp_engine_tone_standard).  Step per DECIMATED
+ *      sample: dphi_t = (uint32) llround((double) tone_hz_t 2^32 32 / 44100.0).  bank_key = 32-bit FNV-1a (offset basis
+ *      2166136261, prime 16777619) over the little-endian bytes of n_tones (a uint32) and then of every dphi_t; a result of 0 is
+ *      replaced by 1.
+ *   2. Decimation by 32.  Block b gives four values d[b][q], q = 0 ... 3: the sum of a[128 b + 32 q ... + 31] by the meter's
+ *      balanced binary tree over adjacent pairs in index order, cut off after five levels.  No products.  The rate is
+ *      1378.125 Hz; every tone lies below 689 Hz.
+ *   3. Bank correlation.  m = 4 cnt + q is the index of a decimated sample inside the current window, cnt the blocks completed in
+ *      it.  For every tone t: (c, s) = the tuning pass's phasor at the uint32 product m dphi_t (it wraps; the 1024-entry table of
+ *      rdsp_engine_tune_table and its interpolation, unchanged); re_t = fmaf(d, c, re_t), im_t = fmaf(d, s, im_t): one chain per
+ *      tone over m ascending.  No phase is carried: a window starts at phase 0.
+ *   4. Window.  K blocks, non-overlapping.  After a block cnt += 1; when cnt == K:
+ *      P_t = fmaf(re_t, re_t, im_t im_t) scale, scale = (float)(4.0 / ((128.0 K) (128.0 K))) as in the tone squelch: the squared
+ *      amplitude of a sinusoid at the tone as seen BEHIND the boxcar of step 2 (rdsp_engine_tone_search_gain);
+ *      i = the lowest index with the largest P_t; next = the largest P_t over |t - i| > 1, or 0 if there is none (the two
+ *      neighbours in the bank are left out: a short window cannot separate tones 2.3 Hz apart);
+ *      found = P_i >= min2 && P_i >= ratio next, min2 = min_amp min_amp and ratio next one rounded float product each;
+ *      best1 = found ? i + 1 : 0, a2 = P_i, and next is kept.  The P_t stay as the "last spectrum"; re, im and cnt go to 0.
+ *   5. Records.  After block b of a call: best_rec[ch][b] = (uint8)(best1 - 1), 255: none; a2_rec[ch][b] = a2; next_rec[ch][b] =
+ *      next -- the values of the last completed window, 255 / 0 / 0 before the first.
+ *   6. Everything is a function of whole blocks counted from a reset: a stream gives the same bits however it is cut into calls.
+ *   A short window declines to decide at the low end of the list (K = 32: 0.09 s a window, tones 2.3 Hz apart three bins away
+ *     still leak above 1 / ratio); K = 128 separates every standard tone.
+ *   State: per channel 200 words -- K, bank_key, cnt, best1, a2, next, 0, 0, then re[64], im[64], P[64]; lanes at or above n_tones
+ *     hold zeros.  At the start of a call the stored K and bank_key are compared with the group's K and the engine's bank; if
+ *     either differs, or the group's FM reset is pending, the detector starts from zeros.  That one rule covers a changed K, a
+ *     changed bank, a regrouping into a group with another K and a loaded blob that does not match.  The words are zeroed by
+ *     rdsp_engine_reset, are maintained only for NFM groups with K > 0 (a channel of a group with K == 0 has zero words from the
+ *     next update on and the records 255 / 0 / 0), stay with the channel through rdsp_engine_set_groups, and travel in
+ *     rdsp_engine_save_state / load_state as a sixth optional part: header flag 32, 200 words per channel, behind the tone words;
+ *     rdsp_engine_state_bytes says so.  The blob of an engine without the search is unchanged; a blob with the part is refused by
+ *     an engine without it (RDSP_ERR_NOT_READY, nothing changed); a blob without it zeroes the words of the channels it lands on.
+ * - rdsp_engine_enable_tone_search works as rdsp_engine_enable_tone does: it takes no stream, waits for everything queued on the
+ *   engine's device, then allocates 800 bytes of state per channel, 9 bytes per channel and block of max_blocks, the bank's 256
+ *   bytes and the 16 KiB table; if that fails the object is as it was (RDSP_ERR_NOMEM).  Again: RDSP_OK, nothing changed.  It
+ *   needs rdsp_engine_enable_fm first (RDSP_ERR_NOT_READY) and neither the meter nor the tone squelch.
+ * - rdsp_engine_set_tone_bank(e, tone_hz, n_tones): the bank from a HOST array, kept in a host mirror and uploaded stream-ordered
+ *   at the next update when it changed.  A setting: kept by reset, in no blob, and it may precede the enable.
+ *   rdsp_engine_tone_bank(e, out64) writes the bank in force (room for 64) and returns n_tones.  A NaN or a value outside
+ *   [60, 300] anywhere, a bank that is not strictly ascending, n_tones outside 1 ... 64 or a NULL array: RDSP_ERR_INVALID, nothing
+ *   changed.
+ * - rdsp_engine_set_tone_search(e, K, min_amp, ratio): settings of the selected group(s), copied by a new group, kept by reset,
+ *   in no blob.  K is 0 (off, the default) or 4 ... 512; 0 < min_amp <= 1 (default 0.04); 1 <= ratio <= 1e6 (default 4).  Anything
+ *   else: RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_read_tone_search copies the last call's records, [ch][n_blocks] with the given strides (elements), into the
+ *   caller's DEVICE buffers, stream-ordered; any pointer may be NULL; rows of receivers the kernel did not run on read 255 / 0 /
+ *   0.  RDSP_ERR_NOT_READY before rdsp_engine_enable_tone_search; RDSP_ERR_INVALID for n_blocks negative or above the last
+ *   call's, a stride below n_blocks.
+ * - rdsp_engine_read_tone_spectrum copies the last completed window's P_t of n_channels receivers from first_channel on,
+ *   [ch][n_tones] floats with `stride` elements a row (at least n_tones of the bank in force), from the state words into the
+ *   caller's DEVICE buffer, stream-ordered.  RDSP_ERR_NOT_READY before the enable; RDSP_ERR_INVALID for a NULL buffer, a range
+ *   outside the object or a short stride.
+ * - rdsp_engine_tone_standard(out50), host only: the 50 standard tones, ascending; returns 50.
+ * - rdsp_engine_tone_search_gain(tone_hz, tau_us), host only, in double:
+ *   |sin(32 pi f / 44100) / (32 sin(pi f / 44100))| x rdsp_engine_tone_gain(f, tau_us) -- the boxcar of step 2 and the
+ *   de-emphasis: sqrt(a2) of a tone at d Hz of deviation reads d / deviation_hz x this.  The argument limits are
+ *   rdsp_engine_tone_gain's (0.0 outside them). */
+int rdsp_engine_enable_tone_search(rdsp_engine_t *e);
+int rdsp_engine_tone_search_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_tone_bank(rdsp_engine_t *e, const float *tone_hz /* host */, int n_tones);
+int rdsp_engine_tone_bank(const rdsp_engine_t *e, float *out64 /* host */);
+int rdsp_engine_set_tone_search(rdsp_engine_t *e, int K, float min_amp, float ratio);
+int rdsp_engine_read_tone_search(rdsp_engine_t *e, int n_blocks, uint8_t *d_best, size_t best_stride, float *d_a2, size_t a2_stride, float *d_next,
+                                 size_t next_stride, void *stream);
+int rdsp_engine_read_tone_spectrum(rdsp_engine_t *e, int first_channel, int n_channels, float *d_power, size_t stride, void *stream);
+int rdsp_engine_tone_standard(float *out50 /* host */);
+double rdsp_engine_tone_search_gain(float tone_hz, float tau_us);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

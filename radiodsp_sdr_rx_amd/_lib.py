@@ -328,6 +328,15 @@ SYMBOLS = [
     ("rdsp_engine_set_tone_squelch", _i, [_vp, _i, C.c_float, C.c_float]),
     ("rdsp_engine_read_tone", _i, [_vp, _i, _vp, _sz, _vp, _sz, _vp]),
     ("rdsp_engine_tone_gain", C.c_double, [C.c_float, C.c_float]),
+    ("rdsp_engine_enable_tone_search", _i, [_vp]),
+    ("rdsp_engine_tone_search_enabled", _i, [_vp]),
+    ("rdsp_engine_set_tone_bank", _i, [_vp, _f32p, _i]),
+    ("rdsp_engine_tone_bank", _i, [_vp, _f32p]),
+    ("rdsp_engine_set_tone_search", _i, [_vp, _i, C.c_float, C.c_float]),
+    ("rdsp_engine_read_tone_search", _i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    ("rdsp_engine_read_tone_spectrum", _i, [_vp, _i, _i, _vp, _sz, _vp]),
+    ("rdsp_engine_tone_standard", _i, [_f32p]),
+    ("rdsp_engine_tone_search_gain", C.c_double, [C.c_float, C.c_float]),
     ("rdsp_engine_set_groups", _i, [_vp, _i, C.POINTER(C.c_int)]),
     ("rdsp_engine_groups", _i, [_vp]),
     ("rdsp_engine_select_group", _i, [_vp, _i]),

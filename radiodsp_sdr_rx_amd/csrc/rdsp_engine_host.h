@@ -4,10 +4,11 @@
  * and runs the object; rdsp_engine_groups.hip the receiver groups; rdsp_engine_meter_host.hip the signal meter's owner and
  * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
  * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_fm_host.hip the narrow-band FM
- * detector's; rdsp_engine_tone_host.hip the tone squelch's; rdsp_engine_state.hip the state blob.  Host logic only: the kernels
+ * detector's; rdsp_engine_tone_host.hip the tone squelch's; rdsp_engine_tone_search_host.hip the tone search's;
+ * rdsp_engine_state.hip the state blob.  Host logic only: the kernels
  * are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's, rdsp_engine_pack.hip's,
- * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's and rdsp_engine_tone.hip's, the front end is rdsp_engine_sources.h's.  All eight
- * are compiled with the kernels' flags (-ffp-contract=off).
+ * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's and rdsp_engine_tone_search.hip's, the front end is
+ * rdsp_engine_sources.h's.  All nine are compiled with the kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
 #define RDSP_ENGINE_HOST_H
@@ -26,6 +27,7 @@
 #include "rdsp_engine_pack.h"
 #include "rdsp_engine_sources.h"
 #include "rdsp_engine_tone.h"
+#include "rdsp_engine_tone_search.h"
 #include "rdsp_engine_voice.h"
 
 using namespace rdsp_eng;
@@ -37,6 +39,7 @@ struct EngSettings {
   int nfm; /* the group demodulates narrow-band FM: setDemodMode(RDSP_ENGINE_MODE_NFM) behind rdsp_engine_enable_fm */
   rdsp_fm::FmSet fm; /* rdsp_engine_set_fm: in force while the group is in NFM */
   rdsp_tone::ToneSet tone; /* rdsp_engine_set_tone_squelch: in force while the group is in NFM behind rdsp_engine_enable_tone */
+  rdsp_tone_search::SearchSet search; /* rdsp_engine_set_tone_search: in force while the group is in NFM behind rdsp_engine_enable_tone_search */
   EngineAgcSet agc;
   rdsp_meter::MeterSet meter; /* rdsp_engine_set_meter / set_squelch: in force once rdsp_engine_enable_meter was called */
   uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
@@ -101,6 +104,25 @@ struct EngTone {
   /* behind the meter kernel of the NFM group p describes (channels c0 on), behind its tail kernel without a meter */
   hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_tone::ToneSet &set, const EngMeter *meter, const int16_t *d_lr, hipStream_t s);
 };
+/* the tone search (rdsp_engine_tone_search_host.hip): every channel's detector words, the bank's steps, the last call's records,
+ * the table */
+struct EngToneSearch {
+  DevBuf<uint32_t> state, dphi; /* [ch][SEARCH_WORDS]; [MAX_TONES] */
+  DevBuf<uint8_t> best;         /* [ch][max_blocks] */
+  DevBuf<float> a2, next;       /* [ch][max_blocks] */
+  DevBuf<float4> tab;           /* rdsp_tune.h's table, the detector's own copy: the engine may have no sources */
+  rdsp_dev::Event bank_ev;      /* the last upload has left `bank` */
+  rdsp_tone_search::SearchBank bank; /* as uploaded last: what the kernel runs with */
+  bool stale = true;            /* rdsp_engine_set_tone_bank since the last upload (or none yet) */
+  size_t n_channels = 0, max_blocks = 0;
+  std::vector<std::pair<size_t, size_t>> rows; /* of the last call: first channel and count of every group that ran the detector */
+  hipError_t init(size_t n_channels, size_t max_blocks); /* every buffer; state, steps and records zeroed */
+  hipError_t reset(hipStream_t s);                       /* the state zero */
+  hipError_t upload(const rdsp_tone_search::SearchBank &b, hipStream_t s); /* the bank's steps, when it changed */
+  /* behind the tone-squelch kernel of the NFM group p describes (channels c0 on); set.K > 0 */
+  hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_tone_search::SearchSet &set, hipStream_t s);
+  hipError_t clear_group(size_t c0, size_t count, hipStream_t s); /* a group with K == 0: its channels' words are zeros */
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -120,10 +142,15 @@ struct rdsp_engine {
   std::unique_ptr<EngVoice> voice; /* the voice-rate audio, from rdsp_engine_enable_voice on */
   std::unique_ptr<EngFm> fm;       /* the narrow-band FM detector, from rdsp_engine_enable_fm on */
   std::unique_ptr<EngTone> tone;   /* the tone squelch, from rdsp_engine_enable_tone on */
+  std::unique_ptr<EngToneSearch> search; /* the tone search, from rdsp_engine_enable_tone_search on */
   int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
   std::vector<float> tone_hz;      /* per channel (empty: all 0), rdsp_engine_set_tones: a setting that may precede the detector */
+  std::vector<float> bank_hz;      /* rdsp_engine_set_tone_bank (empty: the 50 standard tones): a setting that may precede the search */
   std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
 };
+
+/* the engine's bank as the tone search runs it: the caller's (rdsp_engine_set_tone_bank), or the standard tones */
+rdsp_tone_search::SearchBank rdsp_engine_search_bank(const rdsp_engine_t *e);
 
 /* the setters address the selected group, or all of them */
 template <typename F>

@@ -325,6 +325,58 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_tone(self.h, n, a2.data_ptr(), n, tone.data_ptr(), n, stream_ptr(stream)))
         return a2, tone
 
+    def enable_tone_search(self):
+        """the CTCSS tone search from the next update on (include/rdsp.h, "tone search"): every NFM group with a search window
+        (set_tone_search) runs a bank of correlators per receiver, one per tone of the bank, and records which tone the channel
+        carries.  It only measures.  After enable_fm(); independent of enable_tone(); again: a no-op.  Takes no stream and waits
+        for the device."""
+        check(self.lib.rdsp_engine_enable_tone_search(self.h))
+
+    @property
+    def tone_search_enabled(self):
+        return bool(self.lib.rdsp_engine_tone_search_enabled(self.h))
+
+    def set_tone_bank(self, hz):
+        """the engine's bank: 1 ... 64 tones of 60 ... 300 Hz, strictly ascending (default: standard_tones()); may precede
+        enable_tone_search()"""
+        t = np.ascontiguousarray(np.atleast_1d(hz), np.float32)
+        check(self.lib.rdsp_engine_set_tone_bank(self.h, t.ctypes.data_as(_F32P), t.size))
+
+    def tone_bank(self):
+        """the bank in force: float32 [n_tones]"""
+        o = np.zeros(64, np.float32)
+        n = self.lib.rdsp_engine_tone_bank(self.h, o.ctypes.data_as(_F32P))
+        check(min(n, 0))
+        return o[:n].copy()
+
+    def set_tone_search(self, K=128, min_amp=0.04, ratio=4.0):
+        """the selected group's search: windows of K blocks (0: off, or 4 ... 512); a tone is found when its amplitude behind the
+        decimator is at least min_amp (1.0: the peak deviation) and its power at least ratio times that of the strongest tone
+        that is not its neighbour in the bank"""
+        check(self.lib.rdsp_engine_set_tone_search(self.h, int(K), float(min_amp), float(ratio)))
+
+    def read_tone_search(self, n_blocks, stream=None):
+        """the last call's records -> (best uint8: the index in the bank of the tone the last completed window found, 255: none;
+        a2 float32: the strongest tone's squared amplitude; next float32: the largest power outside its neighbourhood), each
+        [n_channels, n_blocks] on the device; 255 / 0 / 0 for receivers the search did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        best = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        a2 = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        nxt = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_tone_search(self.h, n, best.data_ptr(), n, a2.data_ptr(), n, nxt.data_ptr(), n, stream_ptr(stream)))
+        return best, a2, nxt
+
+    def read_tone_spectrum(self, stream=None):
+        """the last completed window's powers, one per tone of the bank -> float32 [n_channels, n_tones] on the device"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = len(self.tone_bank())
+        out = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_tone_spectrum(self.h, 0, self.n_channels, out.data_ptr(), n, stream_ptr(stream)))
+        return out
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -394,6 +446,22 @@ def tone_gain(tone_hz, tau_us=750.0):
     """the magnitude of the NFM de-emphasis at tone_hz (1.0 for tau_us == 0): a tone at d Hz of deviation reads
     d / deviation_hz x tone_gain on the demodulated tap (host only, no GPU)"""
     g = float(load().rdsp_engine_tone_gain(float(tone_hz), float(tau_us)))
+    if g == 0.0:
+        check(-1)
+    return g
+
+
+def standard_tones():
+    """the 50 standard CTCSS tones, 67.0 ... 254.1 Hz, ascending: the tone search's default bank (host only, no GPU)"""
+    o = np.zeros(50, np.float32)
+    assert load().rdsp_engine_tone_standard(o.ctypes.data_as(_F32P)) == 50
+    return o
+
+
+def tone_search_gain(tone_hz, tau_us=750.0):
+    """what the tone search's decimator (a boxcar of 32 samples) and the NFM de-emphasis leave of a tone at tone_hz: sqrt(a2) of
+    a tone at d Hz of deviation reads d / deviation_hz x tone_search_gain (host only, no GPU)"""
+    g = float(load().rdsp_engine_tone_search_gain(float(tone_hz), float(tau_us)))
     if g == 0.0:
         check(-1)
     return g
