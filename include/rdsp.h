@@ -1338,6 +1338,94 @@ int rdsp_engine_read_tone_search(rdsp_engine_t *e, int n_blocks, uint8_t *d_best
 int rdsp_engine_read_tone_spectrum(rdsp_engine_t *e, int first_channel, int n_channels, float *d_power, size_t stride, void *stream);
 int rdsp_engine_tone_standard(float *out50 /* host */);
 double rdsp_engine_tone_search_gain(float tone_hz, float tau_us);
+/* Code squelch (DCS).  The other half of VHF / UHF channels separates its user groups not by a tone but by Digital Coded Squelch:
+ * a 23-bit Golay word, repeated without a gap at 134.4 bit/s as sub-audible NRZ on the same "demod" tap.  After
+ * rdsp_engine_enable_dcs(e) every NFM group runs one more kernel behind its tone-squelch kernel (behind its meter kernel without
+ * one, behind its tail kernel without either), in front of the list kernel and the voice stage: per receiver bit timing, slicing
+ * and code matching.  The code is per CHANNEL (rdsp_engine_set_dcs_codes), the window and the counts per GROUP
+ * (rdsp_engine_set_dcs_squelch).  RDSP_DCS_ANY opens on any valid code and reads it out: that tells a caller WHICH code a channel
+ * carries.  Opt-in: an engine that never calls rdsp_engine_enable_dcs allocates, launches, returns and saves what it did before.
+ * It is independent of rdsp_engine_enable_tone and rdsp_engine_enable_tone_search.  The arithmetic is csrc/rdsp_dcs.h's.
+ *   Code words (host only).  rdsp_dcs_codeword(code), code = 0 ... 511 (the octal digits read as a number: 023 is 19):
+ *     data = 0x800 | code; parity = the remainder of data x^11 by g = x^11 + x^10 + x^6 + x^5 + x^4 + x^2 + 1 (0xC75);
+ *     word = parity << 12 | data; code 023 gives 0x763813.  The word is sent LSB first, bit 1 is positive deviation (the tap above
+ *     its mean); the inverted code is word ^ 0x7FFFFF.  A receiver does not know where a word begins, so a code is its word's
+ *     class under the 23 rotations.  The 104 standard codes 023 ... 754 (rdsp_dcs_standard) lie in 104 distinct classes, any two
+ *     at least 7 bits apart over all rotations; the 512 codes fall into 177 classes with at most one standard code each; and the
+ *     inverted word of every standard code is a rotation of ANOTHER standard code's word (inverted 023 is normal 047).  So a
+ *     read-out cannot tell "047" from "023 inverted": rdsp_dcs_code_of_word reports the NORMAL-polarity reading.
+ *   a[n] is the receiver's "demod" tap; blocks of 128 samples are counted from the detector's last reset.
+ *   1. Decimation by 32.  Exactly the tone search's step 2: d[b][q], q = 0 ... 3.  1378.125 Hz, 10.254 values a bit.
+ *   2. Eight timing hypotheses p = 0 ... 7 with the bit phase bp_p = p 2^29 + M step (uint32, wrapping), M the count of decimated
+ *      values since the detector's last reset, step = (uint32) llround(134.4 32 2^32 / 44100.0) = 418861572.  For every decimated
+ *      value v in order: acc_p = acc_p + v for every p, a plain float add; then, if adding step wraps bp_p, hypothesis p TICKS.
+ *      step < 2^29, so at most one hypothesis ticks per value.
+ *   3. Tick.  ring_p[pos_p] = acc_p; pos_p = (pos_p + 1) mod 23; acc_p = 0; nb_p = min(nb_p + 1, 23);
+ *      thr = (ring_p[0] + ring_p[1] + ... + ring_p[22]) (float)(1.0 / 23.0), the sum left to right, no contraction -- this removes
+ *      the discriminator's DC, a tuning error: a whole word has a fixed weight, 11 or 12 ones for every standard code;
+ *      w has bit j set iff ring_p[(pos_p + j) mod 23] > thr: j = 0 is the oldest bit.
+ *   4. Match, counted only when nb_p == 23.  For a code: min over r of popcount(w ^ rot(want, r)) <= max_err, want the code's
+ *      word, inverted if asked; the matched word is canon(want).  For RDSP_DCS_ANY: parity(w & 0xFFF) == w >> 12 and some rotation
+ *      of w has bits 9 ... 11 equal to 100 (max_err is ignored); the matched word is canon(w).  canon is the smallest of the 23
+ *      rotations, rot(w, r) = (w >> r | w << (23 - r)) & 0x7FFFFF.  On a match hits_p += 1 and last_p = the matched word.
+ *   5. Window of K blocks, non-overlapping, counted from the detector's last reset.  After a block cnt += 1; when cnt == K:
+ *      best = the lowest p with the largest hits_p; H = hits_best; dcs = H >= (dcs ? off_hits : on_hits);
+ *      word = H ? last_best : 0; every hits_p and last_p go to 0 and cnt = 0.  Rings, phases and acc run on.
+ *   6. Records.  After block b of a call dcs_rec (uint8), hits_rec (uint8) and word_rec (uint32) hold dcs, H and word of the last
+ *      completed window, 0 before the first.
+ *   7. Gate.  The tone squelch's rule 5 with dcs_rec in place of tone_rec and "code != 0" in place of "dphi != 0": only with the
+ *      meter on, open[ch][b] <- open[ch][b] & dcs_rec[ch][b] in the meter's per-call record; a newly closed block is written as
+ *      128 zero words; the channel's entry in the active list (MT_ANY) follows the combined records; the meter's signal state is
+ *      NOT touched.  A channel with a tone and a code is gated by both.  Without the meter nothing is gated.
+ *   8. Everything is a function of whole blocks counted from a reset: a stream gives the same bits however it is cut into calls.
+ *   Latency: 23 bits take 59 blocks before anything can match; at the defaults the gate opens at the end of the second window.
+ *   State: per channel 232 words -- a header key, K, cnt, dcs, H, word, M step (uint32), 0, then per hypothesis acc, pos, nb,
+ *     hits, last, ring[23] (acc and ring floats).  key = 2^31 | ANY 2^30 | inverted 2^29 | max_err 2^24 | want, want the word
+ *     looked for (inverted if asked; 0 for ANY).  At the start of a call the stored key and K are compared with the channel's
+ *     and its group's; if either differs, or the group's FM reset is pending, the detector starts from zeros.  That one rule
+ *     covers a changed code, polarity, max_err or K, a regrouping into a group with another K and a loaded blob that does not
+ *     match.  A channel with code 0 has its words and its records written as zeros and is not gated.  The words are zeroed by
+ *     rdsp_engine_reset, maintained only while the group is in NFM, stay with the channel through rdsp_engine_set_groups and
+ *     travel in rdsp_engine_save_state / load_state as a seventh optional part: header flag 64, 232 words per channel, behind
+ *     the tone-search words; rdsp_engine_state_bytes says so.  The blob of an engine without the detector is unchanged; a blob
+ *     with the part is refused by an engine without it (RDSP_ERR_NOT_READY, nothing changed); a blob without it zeroes the
+ *     words of the channels it lands on.
+ *   Not built: the 134.4 Hz turn-off code a transmitter sends at the end of an over (the gate closes a window after the code
+ *     stops instead); acting on a read-out on the device (setting the code found is the caller's); fusing the detectors into
+ *     the FM kernel.
+ * - rdsp_engine_enable_dcs works as rdsp_engine_enable_tone does: no stream, it waits for the engine's device, then allocates 928
+ *   bytes of state and 4 bytes of setting per channel and 6 bytes per channel and block of max_blocks; if that fails the object
+ *   is as it was (RDSP_ERR_NOMEM).  Again: RDSP_OK, nothing changed.  It needs rdsp_engine_enable_fm first (RDSP_ERR_NOT_READY).
+ * - rdsp_engine_set_dcs_codes(e, first_channel, n_channels, codes): the codes of a channel range from a HOST array, kept in a
+ *   host mirror and uploaded stream-ordered at the next update.  0: none (the default); 1 ... 511: a code; + 0x8000: that code
+ *   with inverted polarity; RDSP_DCS_ANY.  Settings: kept by reset, in no blob, and they may precede the enable.  Any other value
+ *   anywhere in the array, a NULL array or a range outside the object: RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_set_dcs_squelch(e, K, max_err, on_hits, off_hits): settings of the selected group(s), copied by a new group, kept
+ *   by reset, in no blob.  K in 8 ... 512; max_err in 0 ... 3; 1 <= off_hits <= on_hits <= K 128 134.4 / 44100 rounded down
+ *   (= K 1024 / 2625: the bits of a window); the defaults are 64, 1, 16, 12 -- a window the code fills counts 25, and the window behind a code that
+ *   stopped still counts up to 9 from the bits left in the rings (at max_err 1), which off_hits has to exceed for the gate to close
+ *   one window after the code.  Anything else: RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_read_dcs copies the last call's records, [ch][n_blocks] with the given strides (elements), into the caller's
+ *   DEVICE buffers, stream-ordered; any pointer may be NULL; rows of receivers the kernel did not run on read as zeros.
+ *   RDSP_ERR_NOT_READY before rdsp_engine_enable_dcs; RDSP_ERR_INVALID for n_blocks negative or above the last call's, a stride
+ *   below n_blocks.
+ * - rdsp_dcs_codeword(code), host only: the word above; 0 (and rdsp_last_error) for a code outside 0 ... 511.
+ * - rdsp_dcs_standard(out104), host only: the 104 standard codes, ascending; returns 104.
+ * - rdsp_dcs_code_of_word(word, code, inverted), host only: the lowest standard code whose word has `word` among its 23
+ *   rotations, *inverted = 0; failing that the lowest standard code whose INVERTED word has, *inverted = 1 (by the class facts
+ *   above this never happens for a standard word); failing that RDSP_ERR_INVALID, as for a NULL pointer or a word outside
+ *   1 ... 0x7FFFFF. */
+#define RDSP_DCS_ANY 0xFFFFu
+#define RDSP_DCS_INVERTED 0x8000u
+int rdsp_engine_enable_dcs(rdsp_engine_t *e);
+int rdsp_engine_dcs_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_dcs_codes(rdsp_engine_t *e, int first_channel, int n_channels, const uint16_t *codes /* host */);
+int rdsp_engine_set_dcs_squelch(rdsp_engine_t *e, int K, int max_err, int on_hits, int off_hits);
+int rdsp_engine_read_dcs(rdsp_engine_t *e, int n_blocks, uint8_t *d_dcs, size_t dcs_stride, uint8_t *d_hits, size_t hits_stride, uint32_t *d_word,
+                         size_t word_stride, void *stream);
+uint32_t rdsp_dcs_codeword(int code);
+int rdsp_dcs_standard(uint16_t *out104 /* host */);
+int rdsp_dcs_code_of_word(uint32_t word, int *code, int *inverted);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -5,10 +5,10 @@
  * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
  * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_fm_host.hip the narrow-band FM
  * detector's; rdsp_engine_tone_host.hip the tone squelch's; rdsp_engine_tone_search_host.hip the tone search's;
- * rdsp_engine_state.hip the state blob.  Host logic only: the kernels
+ * rdsp_engine_dcs_host.hip the code squelch's; rdsp_engine_state.hip the state blob.  Host logic only: the kernels
  * are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's, rdsp_engine_pack.hip's,
- * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's and rdsp_engine_tone_search.hip's, the front end is
- * rdsp_engine_sources.h's.  All nine are compiled with the kernels' flags (-ffp-contract=off).
+ * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's, rdsp_engine_tone_search.hip's and rdsp_engine_dcs.hip's, the front end is
+ * rdsp_engine_sources.h's.  All ten are compiled with the kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
 #define RDSP_ENGINE_HOST_H
@@ -20,6 +20,7 @@
 #include <memory>
 #include <vector>
 
+#include "rdsp_engine_dcs.h"
 #include "rdsp_engine_fm.h"
 #include "rdsp_engine_int.h"
 #include "rdsp_engine_laws.h"
@@ -40,6 +41,7 @@ struct EngSettings {
   rdsp_fm::FmSet fm; /* rdsp_engine_set_fm: in force while the group is in NFM */
   rdsp_tone::ToneSet tone; /* rdsp_engine_set_tone_squelch: in force while the group is in NFM behind rdsp_engine_enable_tone */
   rdsp_tone_search::SearchSet search; /* rdsp_engine_set_tone_search: in force while the group is in NFM behind rdsp_engine_enable_tone_search */
+  rdsp_dcs::DcsSet dcs; /* rdsp_engine_set_dcs_squelch: in force while the group is in NFM behind rdsp_engine_enable_dcs */
   EngineAgcSet agc;
   rdsp_meter::MeterSet meter; /* rdsp_engine_set_meter / set_squelch: in force once rdsp_engine_enable_meter was called */
   uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
@@ -123,6 +125,22 @@ struct EngToneSearch {
   hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_tone_search::SearchSet &set, hipStream_t s);
   hipError_t clear_group(size_t c0, size_t count, hipStream_t s); /* a group with K == 0: its channels' words are zeros */
 };
+/* the code squelch (rdsp_engine_dcs_host.hip): every channel's detector words and setting, the last call's records */
+struct EngDcs {
+  DevBuf<uint32_t> state, sel;  /* [ch][DCS_WORDS]; [ch]: dcs_sel of the channel's code */
+  DevBuf<uint8_t> dcs, hits;    /* [ch][max_blocks] */
+  DevBuf<uint32_t> word;        /* [ch][max_blocks] */
+  rdsp_dev::Event sel_ev;       /* the last upload has left sel_stage */
+  std::vector<uint32_t> sel_stage;
+  bool stale = true;            /* rdsp_engine_set_dcs_codes since the last upload */
+  size_t n_channels = 0, max_blocks = 0;
+  std::vector<std::pair<size_t, size_t>> rows; /* of the last call: first channel and count of every group that ran the detector */
+  hipError_t init(size_t n_channels, size_t max_blocks); /* every buffer; state, settings and records zeroed */
+  hipError_t reset(hipStream_t s);                       /* the state zero */
+  hipError_t upload(const std::vector<uint16_t> &codes, hipStream_t s); /* the channels' settings, when they changed */
+  /* behind the tone-squelch kernel of the NFM group p describes (channels c0 on), behind its meter or tail kernel without one */
+  hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_dcs::DcsSet &set, const EngMeter *meter, const int16_t *d_lr, hipStream_t s);
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -143,8 +161,10 @@ struct rdsp_engine {
   std::unique_ptr<EngFm> fm;       /* the narrow-band FM detector, from rdsp_engine_enable_fm on */
   std::unique_ptr<EngTone> tone;   /* the tone squelch, from rdsp_engine_enable_tone on */
   std::unique_ptr<EngToneSearch> search; /* the tone search, from rdsp_engine_enable_tone_search on */
+  std::unique_ptr<EngDcs> dcs;     /* the code squelch, from rdsp_engine_enable_dcs on */
   int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
   std::vector<float> tone_hz;      /* per channel (empty: all 0), rdsp_engine_set_tones: a setting that may precede the detector */
+  std::vector<uint16_t> dcs_codes; /* per channel (empty: all 0), rdsp_engine_set_dcs_codes: a setting that may precede the detector */
   std::vector<float> bank_hz;      /* rdsp_engine_set_tone_bank (empty: the 50 standard tones): a setting that may precede the search */
   std::vector<double> station; /* per channel, Hz from its stream's centre (0 until tuned): a setting that may precede the sources */
 };

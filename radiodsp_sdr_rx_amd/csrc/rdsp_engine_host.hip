@@ -52,6 +52,7 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.fm = {rdsp_fm::FM_DEFAULT_W, rdsp_fm::FM_DEFAULT_DEVIATION, rdsp_fm::FM_DEFAULT_TAU};
   s.tone = {rdsp_tone::TONE_DEFAULT_K, rdsp_tone::TONE_DEFAULT_ON, rdsp_tone::TONE_DEFAULT_OFF};
   s.search = {0, rdsp_tone_search::SEARCH_DEFAULT_MIN, rdsp_tone_search::SEARCH_DEFAULT_RATIO}; /* off */
+  s.dcs = {rdsp_dcs::DCS_DEFAULT_K, rdsp_dcs::DCS_DEFAULT_ERR, rdsp_dcs::DCS_DEFAULT_ON, rdsp_dcs::DCS_DEFAULT_OFF};
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -145,6 +146,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess && e->fm) err = e->fm->reset(s);
   if (err == hipSuccess && e->tone) err = e->tone->reset(s);
   if (err == hipSuccess && e->search) err = e->search->reset(s);
+  if (err == hipSuccess && e->dcs) err = e->dcs->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -244,6 +246,10 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     e->search->rows.clear();
     if (e->search->stale && (err = e->search->upload(rdsp_engine_search_bank(e), s)) != hipSuccess) return engine_fail("rdsp_engine_update", err);
   }
+  if (e->dcs) {
+    e->dcs->rows.clear();
+    if ((err = e->dcs->upload(e->dcs_codes, s)) != hipSuccess) return engine_fail("rdsp_engine_update", err);
+  }
   for (size_t g = 0; g < e->grp.size(); g++) {
     EngSettings &q = e->grp[g];
     const EngParams p = group_params(e, g, call);
@@ -259,6 +265,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     if (err == hipSuccess && e->tone && nfm) err = e->tone->launch_group(p, c0, q.tone, e->meter.get(), d_lr, s); /* and a tone squelch behind it */
     if (err == hipSuccess && e->search) /* the tone search reads the same rows; a group without a window keeps zero words */
       err = q.search.K == 0 ? e->search->clear_group(c0, (size_t)p.n_channels, s) : nfm ? e->search->launch_group(p, c0, q.search, s) : hipSuccess;
+    if (err == hipSuccess && e->dcs && nfm) err = e->dcs->launch_group(p, c0, q.dcs, e->meter.get(), d_lr, s); /* and a code squelch behind both */
     if (err != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
     if (!nfm && (q.mode <= 3 || q.mode == 6)) q.pos = (q.pos + (uint32_t)n_blocks * BS) & (e->ring_size - 1); /* the lines only move when the SSB / CW path runs */
     q.resets = 0;

@@ -12,6 +12,7 @@ NFMmode = 7                                                              # RDSP_
 audioAM, audioCW, audio2100, audio2700, audio3100, audioNone = 0, 1, 3, 6, 8, 10
 AGCoff, AGCfast, AGCmedium, AGCslow = range(4)
 SRC_S16, SRC_U8, SRC_S8, SRC_F32 = range(4)                              # RDSP_SRC_*: what the source rows hold
+DCS_ANY, DCS_INVERTED = 0xFFFF, 0x8000                                   # RDSP_DCS_*: set_dcs_codes
 _F32P = C.POINTER(C.c_float)
 
 
@@ -377,6 +378,41 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_tone_spectrum(self.h, 0, self.n_channels, out.data_ptr(), n, stream_ptr(stream)))
         return out
 
+    def enable_dcs(self):
+        """the DCS code squelch from the next update on (include/rdsp.h, "code squelch"): every NFM group runs one more kernel
+        that recovers the 134.4 bit/s code under the audio and, with the meter on, closes the blocks that do not carry the
+        receiver's code.  After enable_fm(); independent of enable_tone() and enable_tone_search(); again: a no-op.  Takes no
+        stream and waits for the device."""
+        check(self.lib.rdsp_engine_enable_dcs(self.h))
+
+    @property
+    def dcs_enabled(self):
+        return bool(self.lib.rdsp_engine_dcs_enabled(self.h))
+
+    def set_dcs_codes(self, first_channel, codes):
+        """receivers first_channel ... get the codes (0: none; 1 ... 511, the octal digits read as a number: 0o023; | DCS_INVERTED:
+        inverted polarity; DCS_ANY: any valid code, read out); may precede enable_dcs()"""
+        c = np.ascontiguousarray(np.atleast_1d(codes), np.uint16)
+        check(self.lib.rdsp_engine_set_dcs_codes(self.h, int(first_channel), c.size, c.ctypes.data_as(C.POINTER(C.c_uint16))))
+
+    def set_dcs_squelch(self, K=64, max_err=1, on_hits=16, off_hits=12):
+        """the selected group's detector: windows of K blocks (8 ... 512); a word matches within max_err bits (0 ... 3); the code
+        is there from on_hits matches in a window and until a window has fewer than off_hits"""
+        check(self.lib.rdsp_engine_set_dcs_squelch(self.h, int(K), int(max_err), int(on_hits), int(off_hits)))
+
+    def read_dcs(self, n_blocks, stream=None):
+        """the last call's records -> (dcs uint8: the decision, hits uint8: the last completed window's matches, word int32: its
+        matched word, the smallest rotation; dcs_code_of_word names it), each [n_channels, n_blocks] on the device; zeros for
+        receivers the detector did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        dcs = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        hits = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        word = torch.empty((self.n_channels, n), dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_read_dcs(self.h, n, dcs.data_ptr(), n, hits.data_ptr(), n, word.data_ptr(), n, stream_ptr(stream)))
+        return dcs, hits, word
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -465,6 +501,29 @@ def tone_search_gain(tone_hz, tau_us=750.0):
     if g == 0.0:
         check(-1)
     return g
+
+
+def dcs_codeword(code):
+    """the 23-bit word of DCS code 0 ... 511 (0o023 -> 0x763813), sent LSB first (host only, no GPU)"""
+    w = int(load().rdsp_dcs_codeword(int(code)))
+    if w == 0:
+        check(-1)
+    return w
+
+
+def standard_dcs_codes():
+    """the 104 standard DCS codes 0o023 ... 0o754, ascending: uint16 [104] (host only, no GPU)"""
+    o = np.zeros(104, np.uint16)
+    assert load().rdsp_dcs_standard(o.ctypes.data_as(C.POINTER(C.c_uint16))) == 104
+    return o
+
+
+def dcs_code_of_word(word):
+    """(code, inverted) of a word read_dcs reported: the lowest standard code whose word is a rotation of it -- the
+    normal-polarity reading, since every standard code's inverted word is another standard code's (host only, no GPU)"""
+    code, inv = C.c_int(0), C.c_int(0)
+    check(load().rdsp_dcs_code_of_word(int(word) & 0xFFFFFFFF, C.byref(code), C.byref(inv)))
+    return code.value, bool(inv.value)
 
 
 def rate_taps(P, Q, gain=1.0):
