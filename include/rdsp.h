@@ -1426,6 +1426,73 @@ int rdsp_engine_read_dcs(rdsp_engine_t *e, int n_blocks, uint8_t *d_dcs, size_t 
 uint32_t rdsp_dcs_codeword(int code);
 int rdsp_dcs_standard(uint16_t *out104 /* host */);
 int rdsp_dcs_code_of_word(uint32_t word, int *code, int *inverted);
+/* Noise squelch.  The carrier squelch above compares the mean square of the IQ input with absolute thresholds, which depend on the
+ * source's sample format, the gain folded into its filter, the channelizer and the dongle's AGC: receivers on sources of different
+ * gains cannot share a pair of thresholds.  An FM receiver reads the discriminator's noise above the voice band instead: an empty
+ * channel delivers full-scale noise there and a captured carrier quiets it, whatever the input level -- the "demod" tap reads
+ * +-1.0 at the peak deviation at any gain.  After rdsp_engine_enable_noise(e) every NFM group whose mode is above 0 runs one more
+ * kernel behind its meter kernel (behind its tail kernel without a meter), in front of its tone-squelch kernel.  Opt-in: an engine
+ * that never calls rdsp_engine_enable_noise allocates, launches, returns and saves what it did before.  It is independent of the
+ * tone squelch, the tone search and the code squelch.  The arithmetic is csrc/rdsp_noise.h's (compiled with -ffp-contract=off).
+ *   a[n] is the receiver's "demod" tap, y[n] of the FM detector; n counts from the detector's last start.  Per channel:
+ *   1. Taps.  rdsp_engine_noise_taps(tau_us, out[65]), host only.  The prototype is a band-pass of T = 64 taps, the difference of
+ *      two windowed sincs with cutoffs f2 = 8000 Hz and f1 = 4500 Hz: hb[k] = (2 f2 / fs sinc(2 f2 / fs m) - 2 f1 / fs sinc(2 f1 / fs m))
+ *      w[k], m = k - 31.5, fs = 44100, w the Kaiser window of beta 6; evaluated in double as ((s2 - s1) / u) (I0(6 sqrt(1 - rho^2)) /
+ *      I0(6)) with q = |2 k - 63|, u = pi q / 2, rho = q / 63, s2 = sin(pi 160 q / 882), s1 = sin(pi 90 q / 882), the sine and I0 by
+ *      the libm-free series of rdsp_engine_ddc_taps: every host and the numpy restatement give the same bits.  The tap sits behind
+ *      the de-emphasis, which takes 29 dB off this band at 750 us; the taps undo it: with a the float of the FM detector's
+ *      de-emphasis coefficient and r = 1 - (double) a, g[k] = (float)((hb[k] - r hb[k - 1]) / a), k = 0 ... 64, hb[-1] = hb[64] = 0;
+ *      tau_us == 0: g[k] = (float) hb[k], g[64] = 0.  No normalisation: the prototype reads 0.0 dB at 6 kHz, -6 dB at 8 kHz,
+ *      at most -63 dB up to 3 kHz and -37.6 dB at 3.4 kHz; the compensated taps at 750 us read -40 dB at 3 kHz.  The taps belong to
+ *      the group through the tau_us of its rdsp_engine_set_fm.
+ *   2. Block reading.  Only every fourth output of the filter is computed (the mean square of a subsampled stationary signal is
+ *      the same mean square).  For j = 0 ... 31 of a block that begins at sample n0: v_j = ONE chain over k = 0 ... 64 ascending
+ *      from 0, v = fmaf(g[k], a[n0 + 4 j + 3 - k], v); samples in front of the call come from the detector's history, zeros
+ *      after a start.  q_j = v_j v_j; nz = tree(q_0 ... q_31) 0.03125f, adjacent pairs in index order over five levels (the
+ *      strides 1, 2, 4, 8, 16 of the meter's exchange over 32 lanes).
+ *   3. Level.  N <- the meter's level step, fmaf(nz - N > 0 ? rise : fall, nz - N, N): rise applies while the noise grows (the
+ *      channel empties), fall while it drops (a carrier arrives).
+ *   4. Gate, the meter's with the sense reversed.  N <= open_n: open = 1, hang = hang_blocks; else open && N <= close_n:
+ *      hang = hang_blocks; else open && hang > 0: hang--; else open = 0.
+ *   5. Settings, per group: mode 0 (off, the default), 1 (measure only) or 2 (gate); 0 < open_n <= close_n, both finite;
+ *      hang_blocks 0 ... 65535; fall and rise in (0, 1].  The defaults are 0.01, 0.025, 8, 0.75, 0.125: rms 0.10 and 0.16 on the
+ *      tap against an empty channel's 0.33.  (fall 0.5 was proposed first; from N = 1 it needs seven blocks to reach 0.01, and a
+ *      strong station is to be open from its fourth block on: docs/engine.md.)
+ *   6. Start.  Zero state must not read as "quiet", so the detector has a key word: 2^31 | mode 2^24 | W 2^16 | (tau_us != 0).  A
+ *      stored key that differs from the one the channel is run with, or the group's pending FM reset, starts the detector:
+ *      N = 1.0f, open = 0, hang = 0, history zeros.  That one rule covers a changed mode or W, a regrouping, a zeroing blob and
+ *      rdsp_engine_reset (which zeroes the words).  A group with mode 0 has its channels' words and records written as zeros
+ *      and is not gated.
+ *   7. Records.  After block b of a call: noise_rec[ch][b] = N and nopen_rec[ch][b] = open.
+ *   8. Gate into the engine, mode 2 only: the tone squelch's rule 5 with nopen_rec in place of tone_rec, for every channel of the
+ *      group.  With the meter's squelch off the noise gate works alone -- the intended use.  Without the meter nothing is gated.
+ *      The gates are ANDs: their order changes no result.
+ *   9. Everything is a function of whole blocks counted from a start: a stream gives the same bits however it is cut into calls.
+ *   An all-zero row (a dead source) lets N decay from 1.0: the gate OPENS on silence.  A dead source is not an empty channel.
+ *   State: per channel 68 words -- key, N, open, hang, the newest 64 samples of the tap, oldest first.  Signal state: it stays with
+ *     the channel through rdsp_engine_set_groups, is zeroed by rdsp_engine_reset, is maintained only while the group is in NFM, and
+ *     travels in rdsp_engine_save_state / load_state as an eighth optional part: header flag 128, 68 words per channel, behind the
+ *     code-squelch words.  The blob of an engine without the detector is unchanged; a blob with the part is refused by an engine
+ *     without it (RDSP_ERR_NOT_READY, nothing changed); a blob without it zeroes the words, which by rule 6 restarts the
+ *     detector closed.
+ * - rdsp_engine_enable_noise works as rdsp_engine_enable_tone does: no stream, it waits for the engine's device, then allocates 272
+ *   bytes of state per channel and 5 bytes per channel and block of max_blocks; if that fails the object is as it was
+ *   (RDSP_ERR_NOMEM).  Again: RDSP_OK, nothing changed.  It needs rdsp_engine_enable_fm first (RDSP_ERR_NOT_READY), not the meter.
+ * - rdsp_engine_set_noise_squelch: settings of the selected group(s), copied by a new group, kept by reset, in no blob.  Anything
+ *   outside rule 5 (a NaN among them): RDSP_ERR_INVALID, nothing changed.
+ * - rdsp_engine_read_noise copies the last call's records, [ch][n_blocks] with the given strides (elements), into the caller's
+ *   DEVICE buffers, stream-ordered; either pointer may be NULL; rows of receivers the kernel did not run on read as zeros.
+ *   RDSP_ERR_NOT_READY before rdsp_engine_enable_noise; RDSP_ERR_INVALID for n_blocks negative or above the last call's, a stride
+ *   below n_blocks.
+ * - rdsp_engine_noise_taps: RDSP_ERR_INVALID for a NULL out or a tau_us rdsp_engine_set_fm refuses. */
+#define RDSP_NOISE_OFF 0
+#define RDSP_NOISE_MEASURE 1
+#define RDSP_NOISE_GATE 2
+int rdsp_engine_enable_noise(rdsp_engine_t *e);
+int rdsp_engine_noise_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_noise_squelch(rdsp_engine_t *e, int mode, float open_n, float close_n, int hang_blocks, float fall, float rise);
+int rdsp_engine_read_noise(rdsp_engine_t *e, int n_blocks, float *d_noise, size_t noise_stride, uint8_t *d_open, size_t open_stride, void *stream);
+int rdsp_engine_noise_taps(float tau_us, float *out /* [65], host */);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -53,6 +53,8 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.tone = {rdsp_tone::TONE_DEFAULT_K, rdsp_tone::TONE_DEFAULT_ON, rdsp_tone::TONE_DEFAULT_OFF};
   s.search = {0, rdsp_tone_search::SEARCH_DEFAULT_MIN, rdsp_tone_search::SEARCH_DEFAULT_RATIO}; /* off */
   s.dcs = {rdsp_dcs::DCS_DEFAULT_K, rdsp_dcs::DCS_DEFAULT_ERR, rdsp_dcs::DCS_DEFAULT_ON, rdsp_dcs::DCS_DEFAULT_OFF};
+  s.noise = {rdsp_noise::NOISE_OFF, rdsp_noise::NOISE_DEFAULT_OPEN, rdsp_noise::NOISE_DEFAULT_CLOSE, rdsp_noise::NOISE_DEFAULT_HANG,
+             rdsp_noise::NOISE_DEFAULT_FALL, rdsp_noise::NOISE_DEFAULT_RISE}; /* off */
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -147,6 +149,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess && e->tone) err = e->tone->reset(s);
   if (err == hipSuccess && e->search) err = e->search->reset(s);
   if (err == hipSuccess && e->dcs) err = e->dcs->reset(s);
+  if (err == hipSuccess && e->noise) err = e->noise->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -250,6 +253,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     e->dcs->rows.clear();
     if ((err = e->dcs->upload(e->dcs_codes, s)) != hipSuccess) return engine_fail("rdsp_engine_update", err);
   }
+  if (e->noise) e->noise->rows.clear();
   for (size_t g = 0; g < e->grp.size(); g++) {
     EngSettings &q = e->grp[g];
     const EngParams p = group_params(e, g, call);
@@ -262,6 +266,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
       err = rdsp_engine_launch(p, q.nb_on != 0, q.als_on != 0, s);
     }
     if (err == hipSuccess && e->meter) err = e->meter->launch_group(nfm ? e->fm->metered(p, c0) : p, c0, q.meter, d_lr, s); /* NFM: a carrier squelch */
+    if (err == hipSuccess && e->noise && nfm) err = e->noise->launch_group(p, c0, q.noise, q.fm, e->meter.get(), d_lr, s); /* a noise squelch behind it */
     if (err == hipSuccess && e->tone && nfm) err = e->tone->launch_group(p, c0, q.tone, e->meter.get(), d_lr, s); /* and a tone squelch behind it */
     if (err == hipSuccess && e->search) /* the tone search reads the same rows; a group without a window keeps zero words */
       err = q.search.K == 0 ? e->search->clear_group(c0, (size_t)p.n_channels, s) : nfm ? e->search->launch_group(p, c0, q.search, s) : hipSuccess;

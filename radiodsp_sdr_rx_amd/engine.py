@@ -13,6 +13,7 @@ audioAM, audioCW, audio2100, audio2700, audio3100, audioNone = 0, 1, 3, 6, 8, 10
 AGCoff, AGCfast, AGCmedium, AGCslow = range(4)
 SRC_S16, SRC_U8, SRC_S8, SRC_F32 = range(4)                              # RDSP_SRC_*: what the source rows hold
 DCS_ANY, DCS_INVERTED = 0xFFFF, 0x8000                                   # RDSP_DCS_*: set_dcs_codes
+NOISE_OFF, NOISE_MEASURE, NOISE_GATE = range(3)                          # RDSP_NOISE_*: set_noise_squelch
 _F32P = C.POINTER(C.c_float)
 
 
@@ -413,6 +414,34 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_dcs(self.h, n, dcs.data_ptr(), n, hits.data_ptr(), n, word.data_ptr(), n, stream_ptr(stream)))
         return dcs, hits, word
 
+    def enable_noise(self):
+        """the noise squelch from the next update on (include/rdsp.h, "noise squelch"): every NFM group whose mode
+        (set_noise_squelch) is above 0 runs one more kernel that reads the discriminator's noise above the voice band and, at
+        mode 2 with the meter on, closes the blocks of an empty channel.  After enable_fm(); again: a no-op.  Takes no stream
+        and waits for the device; does not need the meter."""
+        check(self.lib.rdsp_engine_enable_noise(self.h))
+
+    @property
+    def noise_enabled(self):
+        return bool(self.lib.rdsp_engine_noise_enabled(self.h))
+
+    def set_noise_squelch(self, mode=NOISE_GATE, open_n=0.01, close_n=0.025, hang_blocks=8, fall=0.75, rise=0.125):
+        """the selected group's detector: mode NOISE_OFF, NOISE_MEASURE or NOISE_GATE; the gate opens when the level N of the
+        noise reading (a mean square on the demodulated tap, 1.0: the peak deviation) is at most open_n and stays open until it
+        is above close_n for more than hang_blocks blocks; N follows a falling reading with `fall`, a rising one with `rise`"""
+        check(self.lib.rdsp_engine_set_noise_squelch(self.h, int(mode), float(open_n), float(close_n), int(hang_blocks), float(fall), float(rise)))
+
+    def read_noise(self, n_blocks, stream=None):
+        """the last call's records -> (noise float32: the level N, nopen uint8: the noise gate), each [n_channels, n_blocks] on the
+        device; zeros for receivers the detector did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        noise = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        nopen = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        check(self.lib.rdsp_engine_read_noise(self.h, n, noise.data_ptr(), n, nopen.data_ptr(), n, stream_ptr(stream)))
+        return noise, nopen
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -524,6 +553,14 @@ def dcs_code_of_word(word):
     code, inv = C.c_int(0), C.c_int(0)
     check(load().rdsp_dcs_code_of_word(int(word) & 0xFFFFFFFF, C.byref(code), C.byref(inv)))
     return code.value, bool(inv.value)
+
+
+def noise_taps(tau_us=750.0):
+    """the 65 float32 taps of the noise squelch for a group whose set_fm has tau_us: a 4500 ... 8000 Hz band-pass with the
+    inverse of the de-emphasis folded in (host only, no GPU)"""
+    o = np.zeros(65, np.float32)
+    check(load().rdsp_engine_noise_taps(float(tau_us), o.ctypes.data_as(_F32P)))
+    return o
 
 
 def rate_taps(P, Q, gain=1.0):
