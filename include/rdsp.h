@@ -1493,6 +1493,72 @@ int rdsp_engine_noise_enabled(const rdsp_engine_t *e);
 int rdsp_engine_set_noise_squelch(rdsp_engine_t *e, int mode, float open_n, float close_n, int hang_blocks, float fall, float rise);
 int rdsp_engine_read_noise(rdsp_engine_t *e, int n_blocks, float *d_noise, size_t noise_stride, uint8_t *d_open, size_t open_stride, void *stream);
 int rdsp_engine_noise_taps(float tau_us, float *out /* [65], host */);
+/* DTMF decoder.  The detectors above read what lies below and above the voice band; DTMF is the signalling INSIDE it (repeater
+ * control, autopatch, selective calling and ANI, node control).  After rdsp_engine_enable_dtmf(e) every NFM group whose DTMF
+ * frame length K is above 0 runs one more kernel behind its other detector kernels.  It only measures: it reads the "demod" tap
+ * (1.0: the peak deviation, so a tone's amplitude is absolute and needs no AGC) and writes its own records and state words; the
+ * audio, the meter's records, the gates and the active list are untouched.  An engine that never calls the enable allocates,
+ * launches, returns and saves what it did before.  It is independent of the tone squelch, the tone search, the code squelch and
+ * the noise squelch.  The arithmetic is csrc/rdsp_dtmf.h's (compiled with -ffp-contract=off, the fused operations written as
+ * fmaf).  a[n] is the receiver's "demod" tap, in blocks of 128 samples counted from the detector's start.
+ *   1. Tones.  t = 0 ... 3, the low group: 697, 770, 852, 941 Hz; t = 4 ... 7, the high group: 1209, 1336, 1477, 1633 Hz.  Fixed:
+ *      there is no bank setter.  The step per DECIMATED sample is dphi_t = (uint32) llround(f_t 2^32 4 / 44100.0).
+ *   2. Decimation by 4.  d[b][r] = (a0 + a1) + (a2 + a3) over samples 128 b + 4 r ... + 3, r = 0 ... 31: 11 025 Hz, no products.
+ *   3. Correlation in eight sub-chains per tone.  A frame is K blocks.  Sub-chain j = 0 ... 7 of tone t takes the decimated
+ *      samples r = 4 j ... 4 j + 3 of every block of the frame, blocks ascending, r ascending within a block: with m = 32 cnt + r
+ *      (cnt the block's index in the frame), (c, s) = tune_phasor(tab, m dphi_t) (a wrapping uint32 product),
+ *      re_tj = fmaf(d, c, re_tj), im_tj = fmaf(d, s, im_tj).  Beside them eight energy chains e_j = fmaf(d, d, e_j).
+ *   4. Frame end (cnt == K).  RE_t, IM_t and E' are the sums over j by the tree ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).
+ *      P_t = fmaf(RE_t, RE_t, IM_t IM_t) scale, scale = (float)(1 / (64 K)^2): a sine of amplitude A reads about A^2 (times
+ *      rdsp_engine_dtmf_gain squared).  E = E' (float)(1 / (256 K)): a clean pair reads about A_L^2 + A_H^2.  In each group i is
+ *      the lowest index of the largest P and `second` the largest of the other three; P_L, P_H the two maxima.  The frame's
+ *      symbol is sym = 4 i_L + (i_H - 4) if all of
+ *        P_L >= min2 and P_H >= min2 (min2 = min_amp min_amp);  P_L >= ratio second_L and P_H >= ratio second_H;
+ *        P_L <= twist P_H and P_H <= twist P_L;  P_L + P_H >= share E
+ *      hold (every product and the sum rounded floats), else 255.  The key is "123A456B789C*0#D"[sym] (rdsp_engine_dtmf_key).
+ *      All chains and cnt go to 0.
+ *   5. Digit logic, once per frame with the frame's symbol s; state last, run, cur, miss (255: none):
+ *        run = (s != 255 && s == last) ? run + 1 : (s != 255);  last = s;
+ *        if cur != 255: s == cur ? miss = 0 : (miss += 1, and miss >= off_frames: cur = 255);
+ *        then if cur == 255 && run >= on_frames: cur = s, miss = 0, and a digit is emitted:
+ *        ring[n_digits mod 16] = sym | (t_blocks & 0xFFFFFF) << 8, n_digits += 1; t_blocks counts the blocks since the detector's
+ *        start, this one included.
+ *   6. Records after block b of a call, each [ch][max_blocks]: key_rec = cur; new_rec = the symbol emitted by a frame that ended
+ *      with this block, else 255; lo_rec, hi_rec = P_L, P_H of the last completed frame (0 before the first).  Receivers the
+ *      kernel did not run on read 255 / 255 / 0 / 0.
+ *   7. Everything is a function of whole blocks counted from the detector's start: a stream gives the same bits however it is
+ *      cut into calls.
+ * State: 168 words a channel (rdsp_dtmf.h: K, cnt, last + 1, run, cur + 1, miss, n_digits, t_blocks, P_L, P_H, six zeros,
+ * ring[16], re[64], im[64], e[8]; last and cur are stored plus one modulo 256, so zeros are a detector that holds no key).  A
+ * stored K that differs from the one the channel is run with, or the group's pending FM reset, starts the detector from zeros;
+ * a change of thresholds does not.  The words are zeroed by rdsp_engine_reset, maintained only for NFM groups with K > 0 (a
+ * group with K == 0 has its channels' words zeroed in the stream, a group outside NFM leaves them alone), stay with the channel
+ * through rdsp_engine_set_groups, and travel as a ninth optional part of the state blob (header flag 256): an engine without the
+ * decoder writes the blob it always wrote and refuses one that carries the part (RDSP_ERR_NOT_READY); a blob without the part
+ * zeroes the words.
+ * - rdsp_engine_enable_dtmf works as rdsp_engine_enable_tone_search does: no stream, waits for the device, RDSP_ERR_NOT_READY
+ *   before rdsp_engine_enable_fm, RDSP_ERR_NOMEM with the object unchanged, again a no-op.
+ * - rdsp_engine_set_dtmf(e, K, min_amp, ratio, twist, share, on_frames, off_frames): settings of the selected group(s), copied
+ *   by a new group, kept by reset, in no blob.  K 0 (off, the default) or 4 ... 32; 0 < min_amp <= 1 (0.015); 1 <= ratio <= 1e6
+ *   (4); 1 <= twist <= 1e6 (16); 0 < share <= 1 (0.5); on_frames, off_frames 1 ... 16 (2, 2).  RDSP_ERR_INVALID otherwise (a NaN
+ *   fails), nothing changed.  With K = 4 a frame is 11.6 ms: 40 ms of tone and 40 ms of pause always hold two whole frames each.
+ * - rdsp_engine_read_dtmf copies the last call's four records, [ch][n_blocks] with the given strides (elements), into DEVICE
+ *   buffers, stream-ordered; any pointer may be NULL.  RDSP_ERR_NOT_READY before rdsp_engine_enable_dtmf; RDSP_ERR_INVALID for
+ *   n_blocks negative or above the last call's, a stride below n_blocks.
+ * - rdsp_engine_read_dtmf_digits copies n_digits (d_count, [n_channels]) and the 16 ring words (d_ring, [n_channels][16]) of
+ *   channels first_channel ... into DEVICE buffers, stream-ordered; either pointer may be NULL: a caller who polls rarely still
+ *   gets the last 16 keys with their block stamps.  RDSP_ERR_INVALID for a range outside the object.
+ * - rdsp_engine_dtmf_key(sym), host only: the key's character, 0 for anything above 15.
+ * - rdsp_engine_dtmf_gain(hz, tau_us), host only, in double: what the boxcar of 4 samples and the de-emphasis leave of a sine,
+ *   |sin(4 pi hz / 44100) / (4 sin(pi hz / 44100))| x rdsp_engine_tone_gain(hz, tau_us); 0.0 for what that refuses. */
+int rdsp_engine_enable_dtmf(rdsp_engine_t *e);
+int rdsp_engine_dtmf_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_dtmf(rdsp_engine_t *e, int K, float min_amp, float ratio, float twist, float share, int on_frames, int off_frames);
+int rdsp_engine_read_dtmf(rdsp_engine_t *e, int n_blocks, uint8_t *d_key, size_t key_stride, uint8_t *d_new, size_t new_stride, float *d_lo,
+                          size_t lo_stride, float *d_hi, size_t hi_stride, void *stream);
+int rdsp_engine_read_dtmf_digits(rdsp_engine_t *e, int first_channel, int n_channels, uint32_t *d_count, uint32_t *d_ring, void *stream);
+char rdsp_engine_dtmf_key(int sym);
+double rdsp_engine_dtmf_gain(float hz, float tau_us);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -55,6 +55,8 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.dcs = {rdsp_dcs::DCS_DEFAULT_K, rdsp_dcs::DCS_DEFAULT_ERR, rdsp_dcs::DCS_DEFAULT_ON, rdsp_dcs::DCS_DEFAULT_OFF};
   s.noise = {rdsp_noise::NOISE_OFF, rdsp_noise::NOISE_DEFAULT_OPEN, rdsp_noise::NOISE_DEFAULT_CLOSE, rdsp_noise::NOISE_DEFAULT_HANG,
              rdsp_noise::NOISE_DEFAULT_FALL, rdsp_noise::NOISE_DEFAULT_RISE}; /* off */
+  s.dtmf = {0, rdsp_dtmf::DTMF_DEFAULT_MIN, rdsp_dtmf::DTMF_DEFAULT_RATIO, rdsp_dtmf::DTMF_DEFAULT_TWIST, rdsp_dtmf::DTMF_DEFAULT_SHARE,
+            rdsp_dtmf::DTMF_DEFAULT_ON, rdsp_dtmf::DTMF_DEFAULT_OFF}; /* off */
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -150,6 +152,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess && e->search) err = e->search->reset(s);
   if (err == hipSuccess && e->dcs) err = e->dcs->reset(s);
   if (err == hipSuccess && e->noise) err = e->noise->reset(s);
+  if (err == hipSuccess && e->dtmf) err = e->dtmf->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -254,6 +257,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     if ((err = e->dcs->upload(e->dcs_codes, s)) != hipSuccess) return engine_fail("rdsp_engine_update", err);
   }
   if (e->noise) e->noise->rows.clear();
+  if (e->dtmf) e->dtmf->rows.clear();
   for (size_t g = 0; g < e->grp.size(); g++) {
     EngSettings &q = e->grp[g];
     const EngParams p = group_params(e, g, call);
@@ -271,6 +275,8 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     if (err == hipSuccess && e->search) /* the tone search reads the same rows; a group without a window keeps zero words */
       err = q.search.K == 0 ? e->search->clear_group(c0, (size_t)p.n_channels, s) : nfm ? e->search->launch_group(p, c0, q.search, s) : hipSuccess;
     if (err == hipSuccess && e->dcs && nfm) err = e->dcs->launch_group(p, c0, q.dcs, e->meter.get(), d_lr, s); /* and a code squelch behind both */
+    if (err == hipSuccess && e->dtmf) /* the DTMF decoder reads the same rows; a group without a frame length keeps zero words */
+      err = q.dtmf.K == 0 ? e->dtmf->clear_group(c0, (size_t)p.n_channels, s) : nfm ? e->dtmf->launch_group(p, c0, q.dtmf, s) : hipSuccess;
     if (err != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
     if (!nfm && (q.mode <= 3 || q.mode == 6)) q.pos = (q.pos + (uint32_t)n_blocks * BS) & (e->ring_size - 1); /* the lines only move when the SSB / CW path runs */
     q.resets = 0;

@@ -442,6 +442,48 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_noise(self.h, n, noise.data_ptr(), n, nopen.data_ptr(), n, stream_ptr(stream)))
         return noise, nopen
 
+    def enable_dtmf(self):
+        """the DTMF decoder from the next update on (include/rdsp.h, "DTMF decoder"): every NFM group with a frame length
+        (set_dtmf) runs one more kernel that correlates the demodulated tap against the eight DTMF tones and reads the keys sent.
+        It only measures.  After enable_fm(); independent of the other detectors; again: a no-op.  Takes no stream and waits for
+        the device."""
+        check(self.lib.rdsp_engine_enable_dtmf(self.h))
+
+    @property
+    def dtmf_enabled(self):
+        return bool(self.lib.rdsp_engine_dtmf_enabled(self.h))
+
+    def set_dtmf(self, K=4, min_amp=0.015, ratio=4.0, twist=16.0, share=0.5, on_frames=2, off_frames=2):
+        """the selected group's decoder: frames of K blocks (0: off, or 4 ... 32); a frame carries a key when both groups'
+        strongest tones have an amplitude of at least min_amp (1.0: the peak deviation), `ratio` times the power of their
+        group's second, at most `twist` times each other's power, and together at least `share` of the frame's energy; a digit
+        is emitted after on_frames equal frames and released after off_frames others"""
+        check(self.lib.rdsp_engine_set_dtmf(self.h, int(K), float(min_amp), float(ratio), float(twist), float(share), int(on_frames), int(off_frames)))
+
+    def read_dtmf(self, n_blocks, stream=None):
+        """the last call's records -> (key uint8: the key held after each block, 255: none; new uint8: the key emitted by a frame
+        that ended with the block, else 255; lo, hi float32: the two groups' largest powers of the last completed frame), each
+        [n_channels, n_blocks] on the device; 255 / 255 / 0 / 0 for receivers the decoder did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        key = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        new = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        lo = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        hi = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_dtmf(self.h, n, key.data_ptr(), n, new.data_ptr(), n, lo.data_ptr(), n, hi.data_ptr(), n, stream_ptr(stream)))
+        return key, new, lo, hi
+
+    def read_dtmf_digits(self, stream=None):
+        """every receiver's digit count and ring -> (n_digits int32 [n_channels], ring int32 [n_channels, 16]) on the device
+        (the words are uint32: view them so); ring[k mod 16] of digit k is sym | (t_blocks & 0xFFFFFF) << 8"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        count = torch.empty((self.n_channels,), dtype=torch.int32, device=dev)
+        ring = torch.empty((self.n_channels, 16), dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_read_dtmf_digits(self.h, 0, self.n_channels, count.data_ptr(), ring.data_ptr(), stream_ptr(stream)))
+        return count, ring
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -561,6 +603,20 @@ def noise_taps(tau_us=750.0):
     o = np.zeros(65, np.float32)
     check(load().rdsp_engine_noise_taps(float(tau_us), o.ctypes.data_as(_F32P)))
     return o
+
+
+def dtmf_key(sym):
+    """the key of a DTMF symbol 0 ... 15, "123A456B789C*0#D"[sym]; "" for anything else (host only, no GPU)"""
+    return load().rdsp_engine_dtmf_key(int(sym)).decode("ascii").rstrip("\0")
+
+
+def dtmf_gain(hz, tau_us=750.0):
+    """what the DTMF decoder's decimator (a boxcar of 4 samples) and the NFM de-emphasis leave of a tone at hz: the square root
+    of its power reads d / deviation_hz x dtmf_gain for a tone at d Hz of deviation (host only, no GPU)"""
+    g = float(load().rdsp_engine_dtmf_gain(float(hz), float(tau_us)))
+    if g == 0.0:
+        check(-1)
+    return g
 
 
 def rate_taps(P, Q, gain=1.0):
