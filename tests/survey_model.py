@@ -1,6 +1,8 @@
 """rdsp_survey_t restated (include/rdsp.h has the definition): a float64 numpy evaluation that starts from the float32 values of
 the source rows (engine_sources_model.values) and the library's float32 window, with the row schedule, the error bound of the
-float32 kernel and the test band of the station finder.  Plain numpy; the library is loaded where a function needs it."""
+float32 kernel and the test band of the station finder; and, for the noise floor, the same definition in float32
+(survey_rows_f32), a two-tone input and the rule that holds a row's floor to the float32 one's.  Plain numpy, and scipy's
+complex64 transform where scipy is installed; the library is loaded where a function needs it."""
 import numpy as np
 
 from engine_sources_model import values
@@ -58,6 +60,91 @@ def survey_rows(fmt, raw, N, navg, w):
         P[r] /= navg
         B[r] /= navg
     return P, B
+
+
+# ---- the noise floor: a float32 reference and a two-tone input ------------------------------------------------------------------
+K_STRONG = 37               # the carrier's bin; the weak tone sits on bin N / 4 + 3
+FLOOR_MARGIN_DB = 12.0      # over the float32 reference's floor: the factor 4 in amplitude that twiddles good to about 4 ulp
+                            # (the plan's product chains) can cost over exact ones
+
+
+def two_tone(N, weak_db, frames):
+    """float32 [(frames + 1) N / 2, 2] rows of format F32 (`frames` overlapping frames), no noise:
+    0.5 e^{j 2 pi 37 n / N} + 0.5 10^(weak_db / 20) e^{j (2 pi (N / 4 + 3) n / N + 1)}, rounded to float32"""
+    n = np.arange((frames + 1) * (N // 2), dtype=np.float64)
+    z = 0.5 * np.exp(2j * np.pi * K_STRONG * n / N) + 0.5 * 10.0 ** (weak_db / 20.0) * np.exp(1j * (2.0 * np.pi * (N // 4 + 3) * n / N + 1.0))
+    return np.stack([z.real, z.imag], 1).astype(np.float32)
+
+
+def _fft_c64(x):
+    """the forward transform of a complex64 vector in complex64: scipy's, or without scipy a radix-2 one with twiddles
+    computed in float64"""
+    try:
+        import scipy.fft
+    except ImportError:
+        x = np.asarray(x, np.complex64)
+        n = len(x)
+        if n == 1:
+            return x
+        even, odd = _fft_c64(x[0::2]), _fft_c64(x[1::2])
+        t = np.exp(-2j * np.pi * np.arange(n // 2) / n).astype(np.complex64) * odd
+        return np.concatenate([even + t, even - t]).astype(np.complex64)
+    X = scipy.fft.fft(np.asarray(x, np.complex64))
+    assert X.dtype == np.complex64
+    return X
+
+
+def survey_rows_f32(fmt, raw, N, navg, w):
+    """the definition evaluated in float32 -> float32 [rows, N]: one rounded window product per component, a complex64
+    transform, |X|^2 as fmaf(re, re, im im), the frames added in ascending order from 0, times 1 / navg"""
+    F = np.float32
+    v = values(fmt, raw)
+    w = np.asarray(w, F)
+    assert v.dtype == F
+    H = N // 2
+    nrows = rows(N, navg, len(v))
+    P = np.zeros((nrows, N), F)
+    for r in range(nrows):
+        acc = np.zeros(N, F)
+        for f in range(r * navg, (r + 1) * navg):
+            xf = np.empty(N, np.complex64)
+            xf.real = w * v[f * H:f * H + N, 0]
+            xf.imag = w * v[f * H:f * H + N, 1]
+            X = np.fft.fftshift(_fft_c64(xf))
+            re, im = X.real.astype(F), X.imag.astype(F)
+            p = (re.astype(np.float64) * re + (im * im).astype(np.float64)).astype(F)     # fmaf(re, re, im * im)
+            acc = (acc + p).astype(F)
+        P[r] = acc * F(1.0 / navg)
+    return P
+
+
+def tone_indices(N, mirror=False):
+    """the row indices of the carrier and the weak tone of two_tone; mirror: of the same rows run backwards"""
+    s = -1 if mirror else 1
+    return N // 2 + s * K_STRONG, N // 2 + s * (N // 4 + 3)
+
+
+def far(N, mirror=False):
+    """the mask of row indices more than 8 bins from both tones of two_tone"""
+    j = np.arange(N)
+    m = np.ones(N, bool)
+    for c in tone_indices(N, mirror):
+        d = np.abs(j - c)
+        m &= np.minimum(d, N - d) > 8
+    return m
+
+
+def floor_db(row, N, mirror=False):
+    """the largest far bin of a row of two_tone, in dB relative to the row's peak"""
+    row = np.asarray(row, np.float64)
+    return 10.0 * np.log10(max(row[far(N, mirror)].max(), 1e-300) / row.max())
+
+
+def floor_within_margin(row, ref_row, N, mirror=False):
+    """-> (ok, the row's floor, the reference row's floor): the floor of `row` is at most FLOOR_MARGIN_DB over that of the
+    float32 reference's row of the same input"""
+    got, ref = floor_db(row, N, mirror), floor_db(ref_row, N, mirror)
+    return got <= ref + FLOOR_MARGIN_DB, got, ref
 
 
 # ---- the station finder's band: U8 at 160 / 147 (48 000 Hz), three AM carriers in noise -------------------------------------

@@ -3,9 +3,14 @@ of shared IQ source rows in the engine's four sample formats, and the station fi
 rdsp_engine_tune.  tests/survey_model.py restates the definition in float64.
 
 `-m "not gpu"`: the window (formula, sum, sidelobes of the float taps), the schedule and the axis, the finder on the model's row
-of a band of three AM stations, and tests/host/host_survey_check.c under the address and undefined-behaviour sanitizers.
+of a band of three AM stations, tests/host/host_survey_check.c under the address and undefined-behaviour sanitizers, and the
+noise floor of the float64 model and of the float32 reference (survey_model.survey_rows_f32) on survey_model.two_tone, with
+the check the GPU floor test applies (survey_model.floor_within_margin) shown to refuse a floor of -130 dB.
 `-m gpu` (3 sources, a few N pairs each): parity with the float64 model inside the float32 FFT bound, the call split and the
 formats bit for bit, sign and scale, reset and refusals, and the way from a survey row to tuned receivers.
+tests/test_survey_gpu.py goes on from here on the GPU: the kernel's floor against the float32 reference, and the schedule and
+the launch shape at the settings these cases leave out (navg 1, 8 and 256, lead > 0 with a trailing row in one launch, 300
+units, 67 and 4096 sources, drawn sessions with a reset in mid-row).
 
 The bound (survey_model.survey_rows): per bin, summed over the row's frames, 2 |X_k| E + E^2 with
 E = (12 log2 N + 2) 2^-24 sqrt(N) ||x_f||_2, plus navg 2^-24 sum P.  Worst observed fraction of it on an MI355X: 0.0037
@@ -111,6 +116,78 @@ def test_find_stations_on_the_models_row(rdsp):
     assert len(hz) == 1 and hz[0] == survey.bin_hz(B["N"], B["P"], B["Q"], 300)
     with pytest.raises(rdsp.RdspError):
         survey.find_stations(np.ones(512, np.float32), 1, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _two_tone_rows(N, weak_db):
+    """one row (navg = 2) of survey_model.two_tone in format F32: the float64 model's, its bound, the float32 reference's"""
+    from radiodsp_sdr_rx_amd import survey
+    raw = M.two_tone(N, weak_db, 2)
+    assert raw.dtype == np.float32 and raw.shape == (N + N // 2, 2)
+    P, B = M.survey_rows(FL, raw, N, 2, survey.window(N))
+    R = M.survey_rows_f32(FL, raw, N, 2, survey.window(N))
+    assert P.shape == B.shape == R.shape == (1, N) and R.dtype == np.float32
+    for a in (P, B, R):
+        a.setflags(write=False)
+    return P[0], B[0], R[0]
+
+
+@pytest.mark.parametrize("weak_db", [-100, -120])
+@pytest.mark.parametrize("N", [1024, 4096])
+def test_floor_of_the_model_and_of_the_float32_reference(rdsp, N, weak_db):
+    """a float32 carrier of 0.5 on bin 37 and a tone weak_db below it on bin N / 4 + 3, F32, navg 2.  More than 8 bins from both,
+    relative to the peak: the float64 model reads at most -160 dB; the float32 reference (survey_model.survey_rows_f32) at most
+    -148 dB (N = 1024) and -153 dB (N = 4096); the bound of survey_rows admits at least -101 dB at every such bin, which is why
+    the bound cannot hold a kernel to its floor.  The reference's weak bin is within 1 % of the model's in power."""
+    P, B, R = _two_tone_rows(N, weak_db)
+    strong, weak = M.tone_indices(N)
+    far = M.far(N)
+    assert far.sum() == N - 34 and not far[strong - 8] and far[strong - 9] and not far[weak + 8] and far[weak + 9]
+    assert P.argmax() == strong and R.argmax() == strong and abs(P[strong] / 16384.0 ** 2 - 1.0) < 1e-3
+    model, ref = M.floor_db(P, N), M.floor_db(R, N)
+    bound = 10.0 * np.log10(B[far].min() / P.max())
+    weak_off = abs(float(R[weak]) / P[weak] - 1.0)
+    print(f"N = {N}, weak tone {weak_db} dB: far-bin maximum of the float64 model {model:.1f} dB, of the float32 reference {ref:.1f} dB; "
+          f"the bound at the far bins {bound:.1f} dB; the reference's weak bin off the model's by {weak_off:.1e}")
+    assert model <= -160.0
+    assert ref <= (-148.0 if N == 1024 else -153.0)
+    assert weak_off <= 0.01 and abs(10.0 * np.log10(P[weak] / P[strong]) - weak_db) < 0.01
+    assert bound >= -101.0
+
+
+@pytest.mark.parametrize("N", [1024, 4096])
+def test_floor_check_has_teeth(N):
+    """survey_model.floor_within_margin, the check the GPU floor test applies: the float32 reference's own row passes it; the
+    same row with 10^-13 of its peak (-130 dB) added to every far bin fails it, while that row stays within a hundredth of
+    the bound of survey_rows (-130 dB against a bound of about -99 dB is a factor 1e-3) -- the bound would not have noticed.
+    The mirrored mask on the mirrored row likewise."""
+    P, B, R = _two_tone_rows(N, -100)
+    ok, got, ref = M.floor_within_margin(R, R, N)
+    assert ok and got == ref
+    bad = R.astype(np.float64)
+    bad[M.far(N)] += 1e-13 * bad.max()
+    ok, got, ref = M.floor_within_margin(bad, R, N)
+    frac = (np.abs(bad - P) / B).max()
+    print(f"N = {N}: a floor of {got:.1f} dB against the reference's {ref:.1f} dB fails; it sits at {frac:.4f} of the bound")
+    assert not ok and got > ref + M.FLOOR_MARGIN_DB and -130.5 < got < -129.5
+    assert frac <= 0.01
+    assert M.floor_within_margin(R[::-1], R[::-1], N, mirror=True)[0] and not M.floor_within_margin(bad[::-1], R[::-1], N, mirror=True)[0]
+    assert np.array_equal(M.far(N, mirror=True)[1:], M.far(N)[1:][::-1])
+
+
+def test_float32_transform_without_scipy(monkeypatch):
+    """survey_model._fft_c64 without scipy (the radix-2 numpy transform) stays complex64 and agrees with the float64 transform
+    to float32 accuracy"""
+    import sys
+    r = np.random.default_rng(3)
+    x = (r.standard_normal(1024) + 1j * r.standard_normal(1024)).astype(np.complex64)
+    want = np.fft.fft(x.astype(np.complex128))
+    with_scipy = M._fft_c64(x)
+    monkeypatch.setitem(sys.modules, "scipy.fft", None)
+    monkeypatch.setitem(sys.modules, "scipy", None)
+    plain = M._fft_c64(x)
+    for X in (with_scipy, plain):
+        assert X.dtype == np.complex64 and np.abs(X - want).max() <= 1e-5 * np.abs(want).max()
 
 
 def test_host_half_under_address_and_ub_sanitizers(tmp_path):
