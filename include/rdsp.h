@@ -1559,6 +1559,67 @@ int rdsp_engine_read_dtmf(rdsp_engine_t *e, int n_blocks, uint8_t *d_key, size_t
 int rdsp_engine_read_dtmf_digits(rdsp_engine_t *e, int first_channel, int n_channels, uint32_t *d_count, uint32_t *d_ring, void *stream);
 char rdsp_engine_dtmf_key(int sym);
 double rdsp_engine_dtmf_gain(float hz, float tau_us);
+/* AFSK 1200 packet decoder.  Of the signalling inside the voice band, Bell 202 AFSK at 1200 baud is the one that carries data:
+ * AX.25 (APRS, packet BBS traffic, telemetry).  After rdsp_engine_enable_afsk(e) every NFM group with the decoder on runs one
+ * more kernel behind its other detector kernels.  It only measures: it reads the "demod" tap and writes its own records and
+ * state words, among them a ring of the last four frames whose frame check sequence held.  An engine that never calls the enable
+ * allocates, launches, returns and saves what it did before.  The arithmetic is csrc/rdsp_afsk.h's (compiled with
+ * -ffp-contract=off, the fused operations written as fmaf); its plain loop afsk_reference IS this definition.  a[n] is the
+ * receiver's "demod" tap, in blocks of 128 samples counted from the detector's start.
+ *   1. Decimation by 4.  d[m] = (a0 + a1) + (a2 + a3) over samples 4 m ... 4 m + 3: 32 samples a block at 11 025 Hz, 9.1875 a
+ *      bit.  m = 32 t_blocks + r as uint32 (t_blocks: the blocks before this one); d is 0 before the start.
+ *   2. Two correlators.  dphi_f = llround(f 2^32 4 / 44100) for f = 1200 (mark) and 2200 (space); (c, s) = tune_phasor(tab,
+ *      m dphi_f); p_f[m] = (d c, d s), two rounded products.  Over a window of 12 samples S_f[m] = sum of p_f[m - 11 ... m], each
+ *      component as (q0 + q1) + q2, q_i = (t0 + t1) + (t2 + t3) of terms 4 i ... 4 i + 3, oldest first; recomputed for every m.
+ *      P_f = fmaf(S.x, S.x, S.y S.y); gp = g P_space (space_gain, rounded on its own); raw[m] = P_mark - gp > 0.
+ *   3. Bit clock, integers only.  step = llround(2^32 1200 4 / 44100).  For each m: (a) raw != prev_raw: pll = (int32) pll -
+ *      ((int32) pll >> pull), an arithmetic shift, and prev_raw = raw; (b) old = pll, pll += step (uint32); (int32) old >= 0 and
+ *      (int32) pll < 0: a bit is sampled, bit = (raw == prev_sampled) (NRZI), prev_sampled = raw.
+ *   4. HDLC, per sampled bit.  A one: ones = min(ones + 1, 7); ones >= 7 leaves the frame (inframe = 0), else inside a frame the
+ *      bit is set in `byte` at nb, nb += 1.  A zero: behind six ones it is a flag's end -- inside a frame with nb == 7 and nbytes
+ *      >= min_bytes the frame is emitted if its FCS holds (the running CRC-16/X-25, reflected 0x8408 from 0xFFFF, equals the
+ *      residue 0xF0B8), else n_bad and the block's `bad` count it; either way a frame begins: inframe = 1, nbytes = byte = nb = 0,
+ *      crc = 0xFFFF -- behind five ones it is a stuffed bit and dropped, else inside a frame nb += 1; then ones = 0.  Then
+ *      inframe and nb == 8: buf[nbytes++] = byte, the crc takes the byte, byte = nb = 0, and nbytes > 330 leaves the frame.
+ *   5. Emit.  ring[n_frames mod 4] = { len = nbytes - 2, t_blocks (the blocks since the detector's start, the one the flag ended
+ *      in included), the len bytes packed little-endian into 82 words, the rest 0 }; n_frames += 1.
+ *   6. Records after block b of a call, each [ch][max_blocks]: sync_rec = inframe, new_rec and bad_rec = the frames emitted and
+ *      refused in the block (uint8), lvl_rec = the sum over the block's 32 m of P_mark + gp, by the pairwise tree over r, times
+ *      (float)(1 / (32 24^2)): about A^2 of a present tone of amplitude A (before the boxcar's and the de-emphasis's gain).
+ *      Receivers the kernel did not run on read zeros.
+ *   7. Everything is a function of whole blocks counted from the detector's start: a stream gives the same bits however it is
+ *      cut into calls.
+ * State: 448 words a channel (rdsp_afsk.h: on, pll, prev_raw, prev_sampled, ones, inframe, byte, nb, nbytes, crc, n_frames,
+ * n_bad, t_blocks, three zeros; the last 11 d and a zero; buf, 84 words; the ring, 4 x 84 words).  A stored `on` that differs
+ * from the one the channel is run with, or the group's pending FM reset, starts the detector from zeros; a change of space_gain,
+ * pull or min_bytes does not.  The words are zeroed by rdsp_engine_reset, maintained only for NFM groups with the decoder on
+ * (an NFM group with it off has its channels' words zeroed in the stream, a group outside NFM leaves them alone), stay with the
+ * channel through rdsp_engine_set_groups, and travel as a tenth optional part of the state blob (header flag 512): an engine
+ * without the decoder writes the blob it always wrote and refuses one that carries the part (RDSP_ERR_NOT_READY); a blob
+ * without the part zeroes the words.
+ * - rdsp_engine_enable_afsk works as rdsp_engine_enable_dtmf does: no stream, waits for the device, RDSP_ERR_NOT_READY before
+ *   rdsp_engine_enable_fm, RDSP_ERR_NOMEM with the object unchanged, again a no-op.
+ * - rdsp_engine_set_afsk(e, on, space_gain, pull, min_bytes): settings of the selected group(s), copied by a new group, kept by
+ *   reset, in no blob.  on 0 (the default) or 1; 1/16 <= space_gain <= 16 (1.0: a transmitter that pre-emphasises, the usual
+ *   case, arrives level behind the de-emphasis); pull 1 ... 4 (2); min_bytes 9 ... 330 (17: two addresses, control, FCS).
+ *   RDSP_ERR_INVALID otherwise (a NaN fails), nothing changed.
+ * - rdsp_engine_read_afsk copies the last call's four records, [ch][n_blocks] with the given strides (elements), into DEVICE
+ *   buffers, stream-ordered; any pointer may be NULL.  RDSP_ERR_NOT_READY before rdsp_engine_enable_afsk; RDSP_ERR_INVALID for
+ *   n_blocks negative or above the last call's, a stride below n_blocks.
+ * - rdsp_engine_read_afsk_frames copies n_frames (d_count, [n_channels]) and the ring (d_ring, [n_channels][4][84]) of channels
+ *   first_channel ... into DEVICE buffers, stream-ordered; either pointer may be NULL.  RDSP_ERR_INVALID for a range outside the
+ *   object.
+ * - rdsp_engine_afsk_space_gain(tau_us), host only, in double: (rdsp_engine_dtmf_gain(1200, tau_us) / rdsp_engine_dtmf_gain(2200,
+ *   tau_us))^2, the space_gain for a flat (not pre-emphasised) sender; 0.0 for a tau_us that refuses.
+ * - rdsp_engine_afsk_fcs(bytes, n), host only: the X-25 frame check sequence AX.25 appends, low byte first. */
+int rdsp_engine_enable_afsk(rdsp_engine_t *e);
+int rdsp_engine_afsk_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_afsk(rdsp_engine_t *e, int on, float space_gain, int pull, int min_bytes);
+int rdsp_engine_read_afsk(rdsp_engine_t *e, int n_blocks, uint8_t *d_sync, size_t sync_stride, uint8_t *d_new, size_t new_stride, uint8_t *d_bad,
+                          size_t bad_stride, float *d_lvl, size_t lvl_stride, void *stream);
+int rdsp_engine_read_afsk_frames(rdsp_engine_t *e, int first_channel, int n_channels, uint32_t *d_count, uint32_t *d_ring, void *stream);
+double rdsp_engine_afsk_space_gain(float tau_us);
+uint32_t rdsp_engine_afsk_fcs(const uint8_t *bytes, size_t n);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -484,6 +484,59 @@ class Engine(Handle):
         check(self.lib.rdsp_engine_read_dtmf_digits(self.h, 0, self.n_channels, count.data_ptr(), ring.data_ptr(), stream_ptr(stream)))
         return count, ring
 
+    def enable_afsk(self):
+        """the AFSK 1200 packet decoder from the next update on (include/rdsp.h, "AFSK 1200 packet decoder"): every NFM group
+        with the decoder on (set_afsk) runs one more kernel that demodulates Bell 202 on the demodulated tap, recovers the bit
+        clock, unstuffs HDLC and keeps the frames whose check sequence holds.  It only measures.  After enable_fm(); independent
+        of the other detectors; again: a no-op.  Takes no stream and waits for the device."""
+        check(self.lib.rdsp_engine_enable_afsk(self.h))
+
+    @property
+    def afsk_enabled(self):
+        return bool(self.lib.rdsp_engine_afsk_enabled(self.h))
+
+    def set_afsk(self, on=1, space_gain=1.0, pull=2, min_bytes=17):
+        """the selected group's decoder: on 0 or 1; the space correlator's power counts space_gain times (1.0 for a sender
+        that pre-emphasises, afsk_space_gain(tau_us) for a flat one); a transition pulls the bit clock by 2^-pull of its error;
+        frames below min_bytes bytes (FCS included) are not looked at"""
+        check(self.lib.rdsp_engine_set_afsk(self.h, int(on), float(space_gain), int(pull), int(min_bytes)))
+
+    def read_afsk(self, n_blocks, stream=None):
+        """the last call's records -> (sync uint8: inside a frame at the block's end; new uint8, bad uint8: the frames emitted
+        and refused by their check sequence in the block; lvl float32: the two correlators' power), each [n_channels, n_blocks]
+        on the device; zeros for receivers the decoder did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        sync = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        new = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        bad = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        lvl = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_afsk(self.h, n, sync.data_ptr(), n, new.data_ptr(), n, bad.data_ptr(), n, lvl.data_ptr(), n, stream_ptr(stream)))
+        return sync, new, bad, lvl
+
+    def read_afsk_ring(self, stream=None):
+        """every receiver's frame count and ring -> (n_frames int32 [n_channels], ring int32 [n_channels, 4, 84]) on the device
+        (the words are uint32: view them so); slot k mod 4 of frame k is len, t_blocks and the bytes in 82 little-endian words"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        count = torch.empty((self.n_channels,), dtype=torch.int32, device=dev)
+        ring = torch.empty((self.n_channels, 4, 84), dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_read_afsk_frames(self.h, 0, self.n_channels, count.data_ptr(), ring.data_ptr(), stream_ptr(stream)))
+        return count, ring
+
+    def read_afsk_frames(self, stream=None):
+        """the frames the rings hold -> a list of (channel, t_blocks, bytes), oldest first per channel: the last four at most
+        (FCS checked and removed; ax25.parse reads the addresses).  Waits for the stream."""
+        count, ring = (v.cpu().numpy().view("uint32") for v in self.read_afsk_ring(stream))
+        out = []
+        for c in count.nonzero()[0]:
+            n = int(count[c])
+            for k in range(max(0, n - 4), n):
+                slot = ring[c, k % 4]
+                out.append((int(c), int(slot[1]), slot[2:].astype("<u4").tobytes()[:int(slot[0])]))
+        return out
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -617,6 +670,21 @@ def dtmf_gain(hz, tau_us=750.0):
     if g == 0.0:
         check(-1)
     return g
+
+
+def afsk_space_gain(tau_us=750.0):
+    """the AFSK decoder's space_gain for a sender that does not pre-emphasise: (dtmf_gain(1200) / dtmf_gain(2200))^2 behind a
+    de-emphasis of tau_us (host only, no GPU)"""
+    g = float(load().rdsp_engine_afsk_space_gain(float(tau_us)))
+    if g == 0.0:
+        check(-1)
+    return g
+
+
+def afsk_fcs(data):
+    """the X-25 frame check sequence of AX.25 over `data`; a frame carries it low byte first (host only, no GPU)"""
+    data = bytes(data)
+    return int(load().rdsp_engine_afsk_fcs(data, len(data)))
 
 
 def rate_taps(P, Q, gain=1.0):
