@@ -1620,6 +1620,79 @@ int rdsp_engine_read_afsk(rdsp_engine_t *e, int n_blocks, uint8_t *d_sync, size_
 int rdsp_engine_read_afsk_frames(rdsp_engine_t *e, int first_channel, int n_channels, uint32_t *d_count, uint32_t *d_ring, void *stream);
 double rdsp_engine_afsk_space_gain(float tau_us);
 uint32_t rdsp_engine_afsk_fcs(const uint8_t *bytes, size_t n);
+/* POCSAG pager decoder.  The other large class of traffic on the VHF/UHF bands is not audio: POCSAG paging is direct NRZ FSK
+ * at 512, 1200 or 2400 baud on the discriminator's output.  After rdsp_engine_enable_pocsag(e) every NFM group whose baud is not
+ * 0 runs one more kernel behind its other detector kernels.  It only measures: it reads the "demod" tap and writes its own
+ * records and state words, among them a ring of the last four messages.  An engine that never calls the enable allocates,
+ * launches, returns and saves what it did before.  The arithmetic is csrc/rdsp_pocsag.h's (compiled with -ffp-contract=off); its
+ * plain loop pocsag_reference IS this definition.  a[n] is the receiver's "demod" tap, in blocks of 128 samples counted from the
+ * detector's start.  Set a paging channel with rdsp_engine_set_fm(e, 2, 7500, 0): the usual +-4.5 kHz shift then reads +-0.6,
+ * away from the clip at +-1, and no de-emphasis smears the NRZ (the decoder does not refuse one).
+ *   1. Decimation by 4.  d[m] = (a0 + a1) + (a2 + a3) over samples 4 m ... 4 m + 3: 32 samples a block at 11 025 Hz, 21.53,
+ *      9.19 and 4.59 a bit at 512, 1200 and 2400 baud; d is 0 before the start.
+ *   2. Matched filter.  S[m] = the sum of d[m - W + 1 ... m], W = 20, 8 or 4, as q_i = (t0 + t1) + (t2 + t3) of terms 4 i ...
+ *      4 i + 3, oldest first, folded from the left, ((q0 + q1) + q2) + ...; recomputed for every m, no running sum.
+ *      raw[m] = S[m] < 0: POCSAG's 1 is the lower frequency.
+ *   3. Bit clock, integers only, the AFSK decoder's.  step = llround(baud 2^32 4 / 44100).  For each m: (a) raw != prev_raw:
+ *      pll = (int32) pll - ((int32) pll >> pull) and prev_raw = raw; (b) old = pll, pll += step (uint32); (int32) old >= 0 and
+ *      (int32) pll < 0: the bit raw is sampled.
+ *   4. Framing, per sampled bit.  sr = sr << 1 | bit (32 bits).  Hunting: popcount(sr ^ 0x7CD215D8) <= sync_errs goes in sync
+ *      with polarity 0 (allowed by invert 0 and 2, tested first), the same test on ~sr with polarity 1 (invert 1 and 2); nbits =
+ *      ncw = 0.  In sync: every 32nd bit closes a word, sr read through the polarity.  Words 0 ... 15 are codewords (5, 6); the
+ *      17th must match the sync word within sync_errs at the latched polarity and starts the next batch; if it does not, the
+ *      open message is closed with the flag `cut` and the machine hunts again from the next bit.
+ *   5. Codeword.  pocsag_syndrome = the remainder of bits 31 ... 1 by x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1 (0x769); the error
+ *      pattern is the one of weight <= 2 on those 31 bits with that syndrome (496 patterns; none: uncorrectable); an odd parity
+ *      of the corrected 32 bits counts one more error, in bit 0.  With ne errors the corrected word is accepted iff ne <= (its
+ *      bit 31 ? fix_data : fix_addr); a word not accepted is uncorrectable.
+ *   6. Messages.  An accepted idle word (0x7A89C197) closes the open message; another accepted address word (bit 31 clear)
+ *      closes it and opens a new one, address = bits 30 ... 13 << 3 | codeword index >> 1, function = bits 12 ... 11; an accepted
+ *      message word (bit 31 set) is appended to the open message as 20 data bits (30 ... 11) | ne << 24, ignored if none is
+ *      open; an uncorrectable word counts in n_bad and the block's `bad`, and is appended to an open message as received, bits
+ *      30 ... 11 | 1 << 31.  A message holds 80 words; more are dropped and the message is flagged truncated.
+ *   7. Ring.  A closed message goes to ring[n_msgs mod 4], n_msgs += 1.  A slot is 84 words: n_cw | flags << 8 | polarity << 16;
+ *      t_blocks (the blocks since the detector's start, the one it closed in included); address | function << 21; corrected
+ *      bits (the address word's among them) | uncorrectable words << 16; the n_cw words, the rest 0.  flags: 1 cut, 2
+ *      truncated, 4 holds an uncorrectable word.
+ *   8. Records after block b of a call, each [ch][max_blocks]: sync_rec = in sync, new_rec = messages closed in the block,
+ *      bad_rec = uncorrectable codewords in the block, saturating at 255 (uint8), lvl_rec = the pairwise tree over the block's
+ *      32 |S[m]| times (float)(1 / (32 4 W)), about the amplitude of a present signal, dc_rec = the tree over the block's d[m]
+ *      times 1/128: the block's mean, the receiver's frequency offset in units of the deviation.  Receivers the kernel did not
+ *      run on read zeros.
+ *   9. Everything is a function of whole blocks counted from the detector's start: a stream gives the same bits however it is
+ *      cut into calls.
+ * State: 456 words a channel (rdsp_pocsag.h: baud, pll, prev_raw, sr, insync, pol, nbits, ncw, open, the open message's n_cw,
+ * flags, address word and counts, n_msgs, n_bad, t_blocks; the last 19 d and a zero; the open message, four zeros and 80 words
+ * (those of messages closed before are left in place); the ring, 4 x 84 words).  A stored baud that differs from the one the
+ * channel is run with, or the group's pending FM reset, starts the detector from zeros; a change of the other settings does
+ * not.  The words are zeroed by rdsp_engine_reset, maintained only for NFM groups with a baud (an NFM group with baud 0 has its
+ * channels' words zeroed in the stream, a group outside NFM leaves them alone), stay with the channel through
+ * rdsp_engine_set_groups, and travel as an eleventh optional part of the state blob (header flag 1024): an engine without the
+ * decoder writes the blob it always wrote and refuses one that carries the part (RDSP_ERR_NOT_READY); a blob without the part
+ * zeroes the words.
+ * - rdsp_engine_enable_pocsag works as rdsp_engine_enable_afsk does: no stream, waits for the device, RDSP_ERR_NOT_READY before
+ *   rdsp_engine_enable_fm, RDSP_ERR_NOMEM with the object unchanged, again a no-op.
+ * - rdsp_engine_set_pocsag(e, baud, invert, pull, sync_errs, fix_addr, fix_data): settings of the selected group(s), copied by a
+ *   new group, kept by reset, in no blob.  baud 0 (the default: off), 512, 1200 or 2400; invert 0, 1 or 2 (2); pull 1 ... 4 (3);
+ *   sync_errs 0 ... 3 (2); fix_addr 0 ... 2 (1: in noise two-bit correction accepts a quarter of all random words as
+ *   addresses); fix_data 0 ... 2 (2).  RDSP_ERR_INVALID otherwise, nothing changed.
+ * - rdsp_engine_read_pocsag copies the last call's five records, [ch][n_blocks] with the given strides (elements), into DEVICE
+ *   buffers, stream-ordered; any pointer may be NULL.  RDSP_ERR_NOT_READY before rdsp_engine_enable_pocsag; RDSP_ERR_INVALID for
+ *   n_blocks negative or above the last call's, a stride below n_blocks.
+ * - rdsp_engine_read_pocsag_messages copies n_msgs (d_count, [n_channels]) and the ring (d_ring, [n_channels][4][84]) of
+ *   channels first_channel ... into DEVICE buffers, stream-ordered; either pointer may be NULL.  RDSP_ERR_INVALID for a range
+ *   outside the object.
+ * - rdsp_engine_pocsag_bch_table(), host only: 1024 entries by syndrome, b1 | b2 << 5 | ne << 10 (b: the word's bit 1 ... 31 to
+ *   flip, 0 for none), 0xFFFF where no pattern of weight <= 2 has the syndrome.
+ * - rdsp_engine_pocsag_codeword(data21), host only: the 21 data bits, their BCH(31,21) remainder and the even parity bit. */
+int rdsp_engine_enable_pocsag(rdsp_engine_t *e);
+int rdsp_engine_pocsag_enabled(const rdsp_engine_t *e);
+int rdsp_engine_set_pocsag(rdsp_engine_t *e, int baud, int invert, int pull, int sync_errs, int fix_addr, int fix_data);
+int rdsp_engine_read_pocsag(rdsp_engine_t *e, int n_blocks, uint8_t *d_sync, size_t sync_stride, uint8_t *d_new, size_t new_stride, uint8_t *d_bad,
+                            size_t bad_stride, float *d_lvl, size_t lvl_stride, float *d_dc, size_t dc_stride, void *stream);
+int rdsp_engine_read_pocsag_messages(rdsp_engine_t *e, int first_channel, int n_channels, uint32_t *d_count, uint32_t *d_ring, void *stream);
+const uint16_t *rdsp_engine_pocsag_bch_table(void);
+uint32_t rdsp_engine_pocsag_codeword(uint32_t data21);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

@@ -361,6 +361,13 @@ SYMBOLS = [
     ("rdsp_engine_read_afsk_frames", _i, [_vp, _i, _i, _vp, _vp, _vp]),
     ("rdsp_engine_afsk_space_gain", C.c_double, [C.c_float]),
     ("rdsp_engine_afsk_fcs", C.c_uint32, [C.c_char_p, _sz]),
+    ("rdsp_engine_enable_pocsag", _i, [_vp]),
+    ("rdsp_engine_pocsag_enabled", _i, [_vp]),
+    ("rdsp_engine_set_pocsag", _i, [_vp, _i, _i, _i, _i, _i, _i]),
+    ("rdsp_engine_read_pocsag", _i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    ("rdsp_engine_read_pocsag_messages", _i, [_vp, _i, _i, _vp, _vp, _vp]),
+    ("rdsp_engine_pocsag_bch_table", C.POINTER(C.c_uint16), []),
+    ("rdsp_engine_pocsag_codeword", C.c_uint32, [C.c_uint32]),
     ("rdsp_dcs_codeword", C.c_uint32, [_i]),
     ("rdsp_dcs_standard", _i, [C.POINTER(C.c_uint16)]),
     ("rdsp_dcs_code_of_word", _i, [C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

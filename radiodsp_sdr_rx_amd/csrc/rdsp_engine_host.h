@@ -5,10 +5,10 @@
  * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
  * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_fm_host.hip the narrow-band FM
  * detector's; rdsp_engine_tone_host.hip the tone squelch's; rdsp_engine_tone_search_host.hip the tone search's;
- * rdsp_engine_dcs_host.hip the code squelch's; rdsp_engine_noise_host.hip the noise squelch's; rdsp_engine_dtmf_host.hip the DTMF decoder's; rdsp_engine_afsk_host.hip the AFSK 1200 decoder's; rdsp_engine_state.hip the state blob.  Host logic only: the kernels
+ * rdsp_engine_dcs_host.hip the code squelch's; rdsp_engine_noise_host.hip the noise squelch's; rdsp_engine_dtmf_host.hip the DTMF decoder's; rdsp_engine_afsk_host.hip the AFSK 1200 decoder's; rdsp_engine_pocsag_host.hip the POCSAG decoder's; rdsp_engine_state.hip the state blob.  Host logic only: the kernels
  * are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's, rdsp_engine_pack.hip's,
- * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's, rdsp_engine_tone_search.hip's, rdsp_engine_dcs.hip's, rdsp_engine_noise.hip's, rdsp_engine_dtmf.hip's and rdsp_engine_afsk.hip's, the front end is
- * rdsp_engine_sources.h's.  All thirteen are compiled with the kernels' flags (-ffp-contract=off).
+ * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's, rdsp_engine_tone_search.hip's, rdsp_engine_dcs.hip's, rdsp_engine_noise.hip's, rdsp_engine_dtmf.hip's, rdsp_engine_afsk.hip's and rdsp_engine_pocsag.hip's, the front end is
+ * rdsp_engine_sources.h's.  All fourteen are compiled with the kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
 #define RDSP_ENGINE_HOST_H
@@ -28,6 +28,7 @@
 #include "rdsp_engine_laws.h"
 #include "rdsp_engine_meter.h"
 #include "rdsp_engine_noise.h"
+#include "rdsp_engine_pocsag.h"
 #include "rdsp_engine_pack.h"
 #include "rdsp_engine_sources.h"
 #include "rdsp_engine_tone.h"
@@ -48,6 +49,7 @@ struct EngSettings {
   rdsp_noise::NoiseSet noise; /* rdsp_engine_set_noise_squelch: in force while the group is in NFM behind rdsp_engine_enable_noise */
   rdsp_dtmf::DtmfSet dtmf; /* rdsp_engine_set_dtmf: in force while the group is in NFM behind rdsp_engine_enable_dtmf */
   rdsp_afsk::AfskSet afsk; /* rdsp_engine_set_afsk: in force while the group is in NFM behind rdsp_engine_enable_afsk */
+  rdsp_pocsag::PocsagSet pocsag; /* rdsp_engine_set_pocsag: in force while the group is in NFM behind rdsp_engine_enable_pocsag */
   EngineAgcSet agc;
   rdsp_meter::MeterSet meter; /* rdsp_engine_set_meter / set_squelch: in force once rdsp_engine_enable_meter was called */
   uint32_t pos; /* where the group's next sample goes in its channels' rings (they only move in the SSB / CW modes) */
@@ -192,6 +194,19 @@ struct EngAfsk {
   hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_afsk::AfskSet &set, hipStream_t s);
   hipError_t clear_group(size_t c0, size_t count, hipStream_t s); /* a group with the decoder off: its channels' words are zeros */
 };
+/* the POCSAG pager decoder (rdsp_engine_pocsag_host.hip): every channel's detector words and the last call's records */
+struct EngPocsag {
+  DevBuf<uint32_t> state;          /* [ch][POCSAG_WORDS] */
+  DevBuf<uint8_t> sync, fresh, bad; /* [ch][max_blocks]: sync_rec, new_rec, bad_rec */
+  DevBuf<float> lvl, dc;           /* [ch][max_blocks] */
+  size_t n_channels = 0, max_blocks = 0;
+  std::vector<std::pair<size_t, size_t>> rows; /* of the last call: first channel and count of every group that ran the detector */
+  hipError_t init(size_t n_channels, size_t max_blocks); /* every buffer; state and records zeroed */
+  hipError_t reset(hipStream_t s);                       /* the state zero */
+  /* behind the other detector kernels of the NFM group p describes (channels c0 on); set.baud != 0 */
+  hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_pocsag::PocsagSet &set, hipStream_t s);
+  hipError_t clear_group(size_t c0, size_t count, hipStream_t s); /* a group with baud 0: its channels' words are zeros */
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -216,6 +231,7 @@ struct rdsp_engine {
   std::unique_ptr<EngNoise> noise; /* the noise squelch, from rdsp_engine_enable_noise on */
   std::unique_ptr<EngDtmf> dtmf;   /* the DTMF decoder, from rdsp_engine_enable_dtmf on */
   std::unique_ptr<EngAfsk> afsk;   /* the AFSK 1200 decoder, from rdsp_engine_enable_afsk on */
+  std::unique_ptr<EngPocsag> pocsag; /* the POCSAG decoder, from rdsp_engine_enable_pocsag on */
   int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
   std::vector<float> tone_hz;      /* per channel (empty: all 0), rdsp_engine_set_tones: a setting that may precede the detector */
   std::vector<uint16_t> dcs_codes; /* per channel (empty: all 0), rdsp_engine_set_dcs_codes: a setting that may precede the detector */

@@ -58,6 +58,8 @@ EngSettings settings_as_constructed(const rdsp_engine_t *e) { /* AudioSDR::Audio
   s.dtmf = {0, rdsp_dtmf::DTMF_DEFAULT_MIN, rdsp_dtmf::DTMF_DEFAULT_RATIO, rdsp_dtmf::DTMF_DEFAULT_TWIST, rdsp_dtmf::DTMF_DEFAULT_SHARE,
             rdsp_dtmf::DTMF_DEFAULT_ON, rdsp_dtmf::DTMF_DEFAULT_OFF}; /* off */
   s.afsk = {0, rdsp_afsk::AFSK_DEFAULT_GAIN, rdsp_afsk::AFSK_DEFAULT_PULL, rdsp_afsk::AFSK_DEFAULT_MIN_BYTES}; /* off */
+  s.pocsag = {0, rdsp_pocsag::POCSAG_DEFAULT_INVERT, rdsp_pocsag::POCSAG_DEFAULT_PULL, rdsp_pocsag::POCSAG_DEFAULT_SYNC_ERRS,
+               rdsp_pocsag::POCSAG_DEFAULT_FIX_ADDR, rdsp_pocsag::POCSAG_DEFAULT_FIX_DATA}; /* off */
   settings_demod(e, s, 0);
   s.resets = 0;
   return s;
@@ -155,6 +157,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess && e->noise) err = e->noise->reset(s);
   if (err == hipSuccess && e->dtmf) err = e->dtmf->reset(s);
   if (err == hipSuccess && e->afsk) err = e->afsk->reset(s);
+  if (err == hipSuccess && e->pocsag) err = e->pocsag->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
@@ -261,6 +264,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
   if (e->noise) e->noise->rows.clear();
   if (e->dtmf) e->dtmf->rows.clear();
   if (e->afsk) e->afsk->rows.clear();
+  if (e->pocsag) e->pocsag->rows.clear();
   for (size_t g = 0; g < e->grp.size(); g++) {
     EngSettings &q = e->grp[g];
     const EngParams p = group_params(e, g, call);
@@ -282,6 +286,8 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
       err = q.dtmf.K == 0 ? e->dtmf->clear_group(c0, (size_t)p.n_channels, s) : nfm ? e->dtmf->launch_group(p, c0, q.dtmf, s) : hipSuccess;
     if (err == hipSuccess && e->afsk && nfm) /* and the AFSK decoder behind it; an NFM group with it off keeps zero words */
       err = q.afsk.on == 0 ? e->afsk->clear_group(c0, (size_t)p.n_channels, s) : e->afsk->launch_group(p, c0, q.afsk, s);
+    if (err == hipSuccess && e->pocsag && nfm) /* and the POCSAG decoder; an NFM group with baud 0 keeps zero words */
+      err = q.pocsag.baud == 0 ? e->pocsag->clear_group(c0, (size_t)p.n_channels, s) : e->pocsag->launch_group(p, c0, q.pocsag, s);
     if (err != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
     if (!nfm && (q.mode <= 3 || q.mode == 6)) q.pos = (q.pos + (uint32_t)n_blocks * BS) & (e->ring_size - 1); /* the lines only move when the SSB / CW path runs */
     q.resets = 0;

@@ -10,7 +10,8 @@
  * the 232 code-squelch words per channel of one with the code squelch (rdsp_engine_enable_dcs),
  * the 68 noise-squelch words per channel of one with the noise squelch (rdsp_engine_enable_noise),
  * the 168 DTMF words per channel of one with the DTMF decoder (rdsp_engine_enable_dtmf),
- * the 448 AFSK words per channel of one with the AFSK 1200 decoder (rdsp_engine_enable_afsk).  Settings are not part of it (they belong to the group the channels land in).  The blob of an engine without a part
+ * the 448 AFSK words per channel of one with the AFSK 1200 decoder (rdsp_engine_enable_afsk),
+ * the 456 POCSAG words per channel of one with the POCSAG decoder (rdsp_engine_enable_pocsag).  Settings are not part of it (they belong to the group the channels land in).  The blob of an engine without a part
  * is as it was before the part existed (no flag, nothing appended).
  */
 #include <array>
@@ -19,7 +20,7 @@
 
 namespace {
 constexpr uint32_t STATE_MAGIC = 0x45534452u; /* "RDSE" */
-constexpr uint32_t STATE_PHASES = 1u, STATE_METER = 2u, STATE_VOICE = 4u, STATE_FM = 8u, STATE_TONE = 16u, STATE_SEARCH = 32u, STATE_DCS = 64u, STATE_NOISE = 128u, STATE_DTMF = 256u, STATE_AFSK = 512u;
+constexpr uint32_t STATE_PHASES = 1u, STATE_METER = 2u, STATE_VOICE = 4u, STATE_FM = 8u, STATE_TONE = 16u, STATE_SEARCH = 32u, STATE_DCS = 64u, STATE_NOISE = 128u, STATE_DTMF = 256u, STATE_AFSK = 512u, STATE_POCSAG = 1024u;
 /* where a channel's planes lie in its blob words: whole, but of a ring its last RING_KEPT samples in time order */
 constexpr size_t RING_KEPT = 512;
 constexpr size_t BLOB_OFF[N_PLANES] = {0, NF, NF + RING_KEPT, NF + 2 * RING_KEPT, NF + 2 * RING_KEPT + NB_WORDS};
@@ -27,7 +28,7 @@ constexpr size_t STATE_CH_WORDS = BLOB_OFF[PL_ALS] + ALS_WORDS;
 /* an optional part: the first blob_words of every channel's dev_words on the device (dev: the owner's words; null: the engine
  * has no such part), in the blob under a header flag; needs: what load_state asks for when only the blob has the part */
 struct StatePart { uint32_t flag; size_t dev_words, blob_words; float *dev; const char *needs; };
-constexpr int N_PARTS = 10; /* in flag order, which is their order in the blob */
+constexpr int N_PARTS = 11; /* in flag order, which is their order in the blob */
 using StateParts = std::array<StatePart, N_PARTS>;
 StateParts state_parts(const rdsp_engine_t *e) {
   return {{{STATE_PHASES, 1, 1, e && e->src ? (float *)e->src->phase.p : nullptr, "tuning phases; call rdsp_engine_set_sources"},
@@ -47,7 +48,9 @@ StateParts state_parts(const rdsp_engine_t *e) {
            {STATE_DTMF, rdsp_dtmf::DTMF_WORDS, rdsp_dtmf::DTMF_WORDS, e && e->dtmf ? (float *)e->dtmf->state.p : nullptr,
             "DTMF decoder state; call rdsp_engine_enable_dtmf"},
            {STATE_AFSK, rdsp_afsk::AFSK_WORDS, rdsp_afsk::AFSK_WORDS, e && e->afsk ? (float *)e->afsk->state.p : nullptr,
-            "AFSK decoder state; call rdsp_engine_enable_afsk"}}};
+            "AFSK decoder state; call rdsp_engine_enable_afsk"},
+           {STATE_POCSAG, rdsp_pocsag::POCSAG_WORDS, rdsp_pocsag::POCSAG_WORDS, e && e->pocsag ? (float *)e->pocsag->state.p : nullptr,
+            "POCSAG decoder state; call rdsp_engine_enable_pocsag"}}};
 }
 /* the flags of a blob the engine writes (its own parts), or with all = true every flag a blob may carry */
 uint32_t state_flags(const StateParts &parts, bool all = false) {
@@ -146,7 +149,7 @@ int rdsp_engine_load_state(rdsp_engine_t *e, int first_channel, const void *host
    * that never metered (and always those of the last call: they are no state), the voice history of one without the stage, the
    * detector words of one without FM, the tone words of one without the tone squelch, the search words of one without the
    * tone search, the code-squelch words of one without the code squelch, the noise-squelch words of one without the noise squelch (which
-   * restarts the detector closed: a zero key is no key), the DTMF words of one without the DTMF decoder, the AFSK words of one without the AFSK decoder */
+   * restarts the detector closed: a zero key is no key), the DTMF words of one without the DTMF decoder, the AFSK words of one without the AFSK decoder, the POCSAG words of one without the POCSAG decoder */
   StateImage im(e, parts, n);
   blob_move(e, parts, im, false, hdr[3], first_channel, n, (float *)(hdr + 4)); /* read only: save is false */
   const hipError_t err = image_copy(e, parts, im, false, c0, n, (hipStream_t)stream);

@@ -537,6 +537,63 @@ class Engine(Handle):
                 out.append((int(c), int(slot[1]), slot[2:].astype("<u4").tobytes()[:int(slot[0])]))
         return out
 
+    def enable_pocsag(self):
+        """the POCSAG pager decoder from the next update on (include/rdsp.h, "POCSAG pager decoder"): every NFM group with a
+        paging baud rate (set_pocsag) runs one more kernel that slices the demodulated tap behind a matched filter, recovers the
+        bit clock, frames batches on the sync word, corrects every codeword by BCH(31,21) and keeps the messages.  It only
+        measures.  After enable_fm(); set a paging channel with set_fm(W=2, deviation_hz=7500, tau_us=0).  Independent of the
+        other detectors; again: a no-op.  Takes no stream and waits for the device."""
+        check(self.lib.rdsp_engine_enable_pocsag(self.h))
+
+    @property
+    def pocsag_enabled(self):
+        return bool(self.lib.rdsp_engine_pocsag_enabled(self.h))
+
+    def set_pocsag(self, baud=1200, invert=2, pull=3, sync_errs=2, fix_addr=1, fix_data=2):
+        """the selected group's decoder: baud 0 (off), 512, 1200 or 2400; invert 0, 1 or 2: the polarity as sent, inverted, or
+        either; a transition pulls the bit clock by 2^-pull of its error; a sync word matches within sync_errs bits; address and
+        idle words are accepted with up to fix_addr corrected bits, message words with up to fix_data"""
+        check(self.lib.rdsp_engine_set_pocsag(self.h, int(baud), int(invert), int(pull), int(sync_errs), int(fix_addr), int(fix_data)))
+
+    def read_pocsag(self, n_blocks, stream=None):
+        """the last call's records -> (sync uint8: in sync at the block's end; new uint8: the messages closed in the block; bad
+        uint8: its uncorrectable codewords; lvl float32: the matched filter's mean magnitude; dc float32: the tap's mean), each
+        [n_channels, n_blocks] on the device; zeros for receivers the decoder did not run on"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        n = int(n_blocks)
+        sync = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        new = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        bad = torch.empty((self.n_channels, n), dtype=torch.uint8, device=dev)
+        lvl = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        dc = torch.empty((self.n_channels, n), dtype=torch.float32, device=dev)
+        check(self.lib.rdsp_engine_read_pocsag(self.h, n, sync.data_ptr(), n, new.data_ptr(), n, bad.data_ptr(), n, lvl.data_ptr(), n, dc.data_ptr(), n,
+                                               stream_ptr(stream)))
+        return sync, new, bad, lvl, dc
+
+    def read_pocsag_ring(self, stream=None):
+        """every receiver's message count and ring -> (n_msgs int32 [n_channels], ring int32 [n_channels, 4, 84]) on the device
+        (the words are uint32: view them so); slot k mod 4 of message k is n_cw | flags << 8 | polarity << 16, t_blocks, address
+        | function << 21, corrected bits | uncorrectable words << 16 and the words"""
+        import torch
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        count = torch.empty((self.n_channels,), dtype=torch.int32, device=dev)
+        ring = torch.empty((self.n_channels, 4, 84), dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_read_pocsag_messages(self.h, 0, self.n_channels, count.data_ptr(), ring.data_ptr(), stream_ptr(stream)))
+        return count, ring
+
+    def read_pocsag_messages(self, stream=None):
+        """the messages the rings hold -> a list of (channel, pocsag.Message), oldest first per channel: the last four at most
+        (pocsag.numeric and pocsag.alpha read the words).  Waits for the stream."""
+        from . import pocsag
+        count, ring = (v.cpu().numpy().view("uint32") for v in self.read_pocsag_ring(stream))
+        out = []
+        for c in count.nonzero()[0]:
+            n = int(count[c])
+            for k in range(max(0, n - 4), n):
+                out.append((int(c), pocsag.from_slot(ring[c, k % 4])))
+        return out
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
@@ -685,6 +742,19 @@ def afsk_fcs(data):
     """the X-25 frame check sequence of AX.25 over `data`; a frame carries it low byte first (host only, no GPU)"""
     data = bytes(data)
     return int(load().rdsp_engine_afsk_fcs(data, len(data)))
+
+
+def pocsag_bch_table():
+    """the POCSAG decoder's correction table: 1024 uint16 by syndrome, b1 | b2 << 5 | ne << 10, 0xFFFF for no pattern of weight
+    <= 2 (host only, no GPU)"""
+    import numpy as np
+    p = load().rdsp_engine_pocsag_bch_table()
+    return np.array([p[k] for k in range(1024)], np.uint16)
+
+
+def pocsag_codeword(data21):
+    """the POCSAG codeword of 21 data bits: BCH(31,21) and even parity (host only, no GPU)"""
+    return int(load().rdsp_engine_pocsag_codeword(int(data21) & 0x1FFFFF))
 
 
 def rate_taps(P, Q, gain=1.0):
