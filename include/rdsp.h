@@ -1693,6 +1693,63 @@ int rdsp_engine_read_pocsag(rdsp_engine_t *e, int n_blocks, uint8_t *d_sync, siz
 int rdsp_engine_read_pocsag_messages(rdsp_engine_t *e, int first_channel, int n_channels, uint32_t *d_count, uint32_t *d_ring, void *stream);
 const uint16_t *rdsp_engine_pocsag_bch_table(void);
 uint32_t rdsp_engine_pocsag_codeword(uint32_t data21);
+/* Decoder events.  The three decoders above each keep a ring of results per receiver: 16 digits, 4 frames, 4 messages.  Their
+ * read-outs are dense -- every channel's count and whole ring -- and say nothing of which items are new.
+ * rdsp_engine_gather_events gathers, after an update, the items that update emitted into dense payload words with one record
+ * each: on the device, without atomics, the same bytes every time.  It is opt-in by being called: an engine that never calls it
+ * allocates, launches, returns and saves exactly what it does without.  It only reads the decoders' words and records.  The
+ * plain loop events_reference of csrc/rdsp_events.h IS the definition; it is exported as rdsp_events_reference.
+ *
+ * 1. Kinds.  RDSP_EVENT_DTMF 0, RDSP_EVENT_AFSK 1, RDSP_EVENT_POCSAG 2.  A kind whose decoder is not enabled contributes
+ *    nothing.
+ * 2. Which items are new, per channel ch and kind.  Take the kind's record `new` of the last update exactly as the kind's read
+ *    call (rdsp_engine_read_dtmf / _afsk / _pocsag) returns it for all of that update's blocks: receivers the decoder did not
+ *    run on read 255 (DTMF) or 0 (AFSK, POCSAG), whatever the engine's buffers still hold of an earlier call.
+ *      c = the count of blocks with new != 255 (DTMF), the sum of new (AFSK, POCSAG)
+ *      n = the detector's count word: n_digits, n_frames, n_msgs;  R = the ring's size: 16, 4, 4
+ *      take = min(c, R), lost = c - take
+ *    The items are those with seq = n - take ... n - 1 (uint32), oldest first, item seq in ring slot seq mod R.  By the decoders'
+ *    definitions c <= n holds behind every update (a detector that starts from zeros does so at the start of its launch).  Where
+ *    it does not hold take is n, so a violated premise can misreport but never names an item the ring cannot have; lost stays
+ *    c - min(c, R).
+ * 3. Payload.  The used part of the item's slot, copied verbatim:
+ *      DTMF    the ring word (sym | t_blocks << 8)                                        n_words = 1
+ *      AFSK    slot words 0 ... 1 + ceil(len / 4) (len, t_blocks, the bytes)              n_words = 2 + (min(len, 328) + 3) / 4 <= 84
+ *      POCSAG  slot words 0 ... 3 + n_cw (the four header words, then the words)          n_words = 4 + min(n_cw, 80) <= 84
+ * 4. Sequence.  The events run by channel ascending, then kind ascending, then seq ascending.  needed_events is the sequence's
+ *    length, needed_words the sum of its n_words, lost the sum of lost over channels and kinds.
+ * 5. Output.  rdsp_event_record_t = {int32 channel; uint32 kind | n_words << 8; uint32 seq; uint32 offset}, offset the index of
+ *    the payload's first word in d_words: the sum of n_words of all earlier events.  written_events is the length of the longest
+ *    prefix of the sequence whose events k have k < capacity_events and offset_k + n_words_k <= capacity_words; written_words is
+ *    the offset of the first event behind that prefix (needed_words when there is none).  The records and payloads of the
+ *    prefix are written; nothing at or behind written_events in d_records, or at or behind written_words in d_words, is.
+ *    d_counts[5] = {needed_events, written_events, needed_words, written_words, lost}, on the device.
+ * 6. The call.  Stream-ordered behind the last update.  A sizing call is allowed: both capacities 0, both buffers NULL.  The call
+ *    is repeatable, with another capacity too, and modifies nothing of the engine but its own scratch (16 + 3 bytes a channel),
+ *    which its first call allocates: if that fails it returns RDSP_ERR_NOMEM and the engine is as it was.
+ * 7. When the counts are all 0.  No update made yet; the last update had 0 blocks (or failed); and behind rdsp_engine_reset or
+ *    rdsp_engine_load_state until the next update -- the words then no longer belong to the last call's records.  A host flag
+ *    set by the update and cleared by those calls does this.  No other host call touches the detector words between updates:
+ *    rdsp_engine_set_groups and the setters take effect in the next update, whose kernels zero or restart a detector at their
+ *    start, and a decoder enabled between updates has no rows in the last call, so it contributes nothing.
+ * 8. Refusals.  RDSP_ERR_NOT_READY with none of the three decoders enabled.  RDSP_ERR_INVALID, nothing written: d_counts NULL; a
+ *    capacity above 0 with a NULL buffer; d_records or d_words not 16-byte aligned; a capacity above INT32_MAX; n_channels x 688
+ *    above INT32_MAX (688 = 16 + 4 x 84 + 4 x 84 words, the most a channel contributes: every sum fits an int32).
+ * 9. rdsp_events_reference, host only, is events_reference on host arrays: the three `new` records [n_channels][new_stride] and
+ *    the three detector-word arrays [n_channels][168 / 448 / 456], a kind off where either of its two is NULL; the same refusals
+ *    but for the alignment, and new_stride >= n_blocks >= 0.  It returns the number of (channel, kind) pairs with c > n -- 0
+ *    behind every update -- or RDSP_ERR_INVALID. */
+enum { RDSP_EVENT_DTMF = 0, RDSP_EVENT_AFSK = 1, RDSP_EVENT_POCSAG = 2 };
+typedef struct {
+  int32_t channel;
+  uint32_t kind_words; /* kind | n_words << 8 */
+  uint32_t seq, offset;
+} rdsp_event_record_t;
+int rdsp_engine_gather_events(rdsp_engine_t *e, rdsp_event_record_t *d_records, size_t capacity_events, uint32_t *d_words, size_t capacity_words,
+                              int32_t *d_counts, void *stream);
+int rdsp_events_reference(const uint8_t *new_dtmf, const uint8_t *new_afsk, const uint8_t *new_pocsag, size_t new_stride, const uint32_t *dtmf_words,
+                          const uint32_t *afsk_words, const uint32_t *pocsag_words, int n_channels, int n_blocks, rdsp_event_record_t *records,
+                          size_t capacity_events, uint32_t *words, size_t capacity_words, int32_t *counts);
 /* Receiver groups.  The sketch has one receiver -- one mode, one audio filter, one AGC setting; an object of many
  * channels can be cut into groups of CONSECUTIVE channels that each carry their own settings.  first_channel[g] is group
  * g's first channel (ascending, first_channel[0] = 0; a new group starts as a copy of the group its first channel was in).

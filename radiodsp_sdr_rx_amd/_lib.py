@@ -368,6 +368,8 @@ SYMBOLS = [
     ("rdsp_engine_read_pocsag_messages", _i, [_vp, _i, _i, _vp, _vp, _vp]),
     ("rdsp_engine_pocsag_bch_table", C.POINTER(C.c_uint16), []),
     ("rdsp_engine_pocsag_codeword", C.c_uint32, [C.c_uint32]),
+    ("rdsp_engine_gather_events", _i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("rdsp_events_reference", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     ("rdsp_dcs_codeword", C.c_uint32, [_i]),
     ("rdsp_dcs_standard", _i, [C.POINTER(C.c_uint16)]),
     ("rdsp_dcs_code_of_word", _i, [C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

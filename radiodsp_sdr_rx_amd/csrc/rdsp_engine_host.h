@@ -5,10 +5,10 @@
  * entry points, rdsp_engine_pack_active among them; rdsp_engine_sources_host.hip the entry points of the shared IQ sources;
  * rdsp_engine_voice_host.hip the voice-rate audio's owner and entry points; rdsp_engine_fm_host.hip the narrow-band FM
  * detector's; rdsp_engine_tone_host.hip the tone squelch's; rdsp_engine_tone_search_host.hip the tone search's;
- * rdsp_engine_dcs_host.hip the code squelch's; rdsp_engine_noise_host.hip the noise squelch's; rdsp_engine_dtmf_host.hip the DTMF decoder's; rdsp_engine_afsk_host.hip the AFSK 1200 decoder's; rdsp_engine_pocsag_host.hip the POCSAG decoder's; rdsp_engine_state.hip the state blob.  Host logic only: the kernels
+ * rdsp_engine_dcs_host.hip the code squelch's; rdsp_engine_noise_host.hip the noise squelch's; rdsp_engine_dtmf_host.hip the DTMF decoder's; rdsp_engine_afsk_host.hip the AFSK 1200 decoder's; rdsp_engine_pocsag_host.hip the POCSAG decoder's; rdsp_engine_events_host.hip the owner and entry points of rdsp_engine_gather_events; rdsp_engine_state.hip the state blob.  Host logic only: the kernels
  * are rdsp_engine.hip's stage files' (rdsp_engine_front / _hilbert / _tail.hip), rdsp_engine_meter.hip's, rdsp_engine_pack.hip's,
- * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's, rdsp_engine_tone_search.hip's, rdsp_engine_dcs.hip's, rdsp_engine_noise.hip's, rdsp_engine_dtmf.hip's, rdsp_engine_afsk.hip's and rdsp_engine_pocsag.hip's, the front end is
- * rdsp_engine_sources.h's.  All fourteen are compiled with the kernels' flags (-ffp-contract=off).
+ * rdsp_engine_voice.hip's, rdsp_engine_fm.hip's, rdsp_engine_tone.hip's, rdsp_engine_tone_search.hip's, rdsp_engine_dcs.hip's, rdsp_engine_noise.hip's, rdsp_engine_dtmf.hip's, rdsp_engine_afsk.hip's, rdsp_engine_pocsag.hip's and rdsp_engine_events.hip's, the front end is
+ * rdsp_engine_sources.h's.  All fifteen are compiled with the kernels' flags (-ffp-contract=off).
  */
 #ifndef RDSP_ENGINE_HOST_H
 #define RDSP_ENGINE_HOST_H
@@ -23,6 +23,7 @@
 #include "rdsp_engine_afsk.h"
 #include "rdsp_engine_dcs.h"
 #include "rdsp_engine_dtmf.h"
+#include "rdsp_engine_events.h"
 #include "rdsp_engine_fm.h"
 #include "rdsp_engine_int.h"
 #include "rdsp_engine_laws.h"
@@ -207,6 +208,16 @@ struct EngPocsag {
   hipError_t launch_group(const EngParams &p, size_t c0, const rdsp_pocsag::PocsagSet &set, hipStream_t s);
   hipError_t clear_group(size_t c0, size_t count, hipStream_t s); /* a group with baud 0: its channels' words are zeros */
 };
+/* the decoders' events (rdsp_engine_events_host.hip): rdsp_engine_gather_events' scratch, allocated by its first call; it owns no
+ * state and reads the decoders' */
+struct EngEvents {
+  DevBuf<int4> chan;   /* [ch]: a channel's counts, then where its first event and word go */
+  DevBuf<uint8_t> ran; /* [kind][ch]: 1 where the kind's decoder ran on the channel in the last call (its owner's `rows`) */
+  size_t n_channels = 0;
+  hipError_t init(size_t n_channels); /* both buffers */
+  /* p carries the caller's arguments; the decoders' words, records and rows are filled in here */
+  hipError_t launch(const rdsp_engine *e, rdsp_eng::EventsParams p, hipStream_t s);
+};
 struct rdsp_engine {
   int n_channels, device, max_blocks;
   uint32_t ring_size;
@@ -232,7 +243,10 @@ struct rdsp_engine {
   std::unique_ptr<EngDtmf> dtmf;   /* the DTMF decoder, from rdsp_engine_enable_dtmf on */
   std::unique_ptr<EngAfsk> afsk;   /* the AFSK 1200 decoder, from rdsp_engine_enable_afsk on */
   std::unique_ptr<EngPocsag> pocsag; /* the POCSAG decoder, from rdsp_engine_enable_pocsag on */
+  std::unique_ptr<EngEvents> events; /* rdsp_engine_gather_events' scratch, from its first call on */
   int last_blocks = 0;             /* of the last call that ran: what rdsp_engine_read_demod may ask for */
+  int event_blocks = 0;            /* the blocks of the last update while the decoders' words are still as it left them: 0 behind an update
+                                      of no blocks, rdsp_engine_reset and rdsp_engine_load_state (rdsp_engine_gather_events then counts nothing) */
   std::vector<float> tone_hz;      /* per channel (empty: all 0), rdsp_engine_set_tones: a setting that may precede the detector */
   std::vector<uint16_t> dcs_codes; /* per channel (empty: all 0), rdsp_engine_set_dcs_codes: a setting that may precede the detector */
   std::vector<float> bank_hz;      /* rdsp_engine_set_tone_bank (empty: the 50 standard tones): a setting that may precede the search */

@@ -160,6 +160,7 @@ int rdsp_engine_reset(rdsp_engine_t *e, void *stream) {
   if (err == hipSuccess && e->pocsag) err = e->pocsag->reset(s);
   if (err == hipSuccess) err = hipStreamSynchronize(s); /* the host vectors go away */
   for (auto &g : e->grp) { g.pos = 0; g.resets = 0; }
+  e->event_blocks = 0; /* the decoders' words are zeros: the last call's records tell of nothing in them */
   return err == hipSuccess ? RDSP_OK : engine_fail("rdsp_engine_reset", err);
 }
 
@@ -242,6 +243,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     rdsp_set_error("rdsp_engine_update: the engine's coefficient tables are not loaded (rdsp_engine_load_tables)");
     return RDSP_ERR_NOT_READY;
   }
+  e->event_blocks = 0; /* until this call has run: rdsp_engine_gather_events counts nothing behind a call of no blocks or a failed one */
   if (n_blocks == 0) return RDSP_OK;
   hipStream_t s = (hipStream_t)stream;
   hipError_t err = hipSetDevice(e->device);
@@ -293,6 +295,7 @@ int rdsp_engine_update(rdsp_engine_t *e, const int16_t *d_iq, size_t in_stride, 
     q.resets = 0;
   }
   e->last_blocks = n_blocks;
+  e->event_blocks = n_blocks;
   if (e->meter && (err = e->meter->launch_list(n_blocks, s)) != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
   if (e->voice && (err = e->voice->launch(d_lr, out_stride, n_blocks, s)) != hipSuccess) return engine_fail("rdsp_engine_update launch", err);
   return RDSP_OK;

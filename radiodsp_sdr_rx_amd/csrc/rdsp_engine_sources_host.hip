@@ -187,7 +187,7 @@ int update_source_rows(const char *who, rdsp_engine_t *e, const void *d_src, siz
     rdsp_set_error("%s: the engine's coefficient tables are not loaded (rdsp_engine_load_tables)", who);
     return RDSP_ERR_NOT_READY;
   }
-  if (n_blocks == 0) return RDSP_OK;
+  if (n_blocks == 0) { e->event_blocks = 0; return RDSP_OK; } /* as rdsp_engine_update's call of no blocks */
   hipError_t err = hipSetDevice(e->device);
   const SourceTuning tuning{e->first, [e](size_t g) { return e->grp[g].tuning_offset; }, e->station};
   if (err == hipSuccess) err = e->src->run(d_src, src_stride, n_blocks, tuning, (hipStream_t)stream);

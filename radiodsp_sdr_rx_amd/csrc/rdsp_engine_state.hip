@@ -150,6 +150,7 @@ int rdsp_engine_load_state(rdsp_engine_t *e, int first_channel, const void *host
    * detector words of one without FM, the tone words of one without the tone squelch, the search words of one without the
    * tone search, the code-squelch words of one without the code squelch, the noise-squelch words of one without the noise squelch (which
    * restarts the detector closed: a zero key is no key), the DTMF words of one without the DTMF decoder, the AFSK words of one without the AFSK decoder, the POCSAG words of one without the POCSAG decoder */
+  e->event_blocks = 0; /* the decoders' words are no longer what the last call's records tell of */
   StateImage im(e, parts, n);
   blob_move(e, parts, im, false, hdr[3], first_channel, n, (float *)(hdr + 4)); /* read only: save is false */
   const hipError_t err = image_copy(e, parts, im, false, c0, n, (hipStream_t)stream);

@@ -594,6 +594,41 @@ class Engine(Handle):
                 out.append((int(c), pocsag.from_slot(ring[c, k % 4])))
         return out
 
+    def gather_events(self, capacity_events=None, capacity_words=None, stream=None):
+        """the digits, frames and messages the decoders emitted in the last update, dense (include/rdsp.h "Decoder events") ->
+        (records int32 [written_events, 4] = channel, kind | n_words << 8, seq, offset; words int32 [written_words], both on the
+        device (view them as uint32); counts, an events.Counts of needed_events, written_events, needed_words, written_words and
+        lost).  capacity_events, capacity_words: room for so many (default: a sizing call first, then exactly `needed`).  Waits
+        for the stream."""
+        import torch
+        from . import events
+        dev = torch.device("cuda", self.lib.rdsp_engine_device(self.h))
+        cnt = torch.empty(5, dtype=torch.int32, device=dev)
+        s = stream_ptr(stream)
+
+        def counts():   # read on the host: wait for the caller's stream, whichever form it came in, as active() does
+            if stream is not None:
+                (stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(stream)).synchronize()
+            return events.Counts(*[int(v) for v in cnt.tolist()])
+        if capacity_events is None or capacity_words is None:
+            check(self.lib.rdsp_engine_gather_events(self.h, None, 0, None, 0, cnt.data_ptr(), s))
+            need = counts()
+            capacity_events = need.needed_events if capacity_events is None else capacity_events
+            capacity_words = need.needed_words if capacity_words is None else capacity_words
+        ce, cw = int(capacity_events), int(capacity_words)
+        records = torch.empty((ce, 4), dtype=torch.int32, device=dev)
+        words = torch.empty((cw,), dtype=torch.int32, device=dev)
+        check(self.lib.rdsp_engine_gather_events(self.h, records.data_ptr() if ce else None, ce, words.data_ptr() if cw else None, cw, cnt.data_ptr(), s))
+        got = counts()
+        return records[:got.written_events], words[:got.written_words], got
+
+    def events(self, stream=None):
+        """the last update's events -> a list of events.Event(channel, kind, seq, t_blocks, value), by channel, then kind (DTMF,
+        AFSK, POCSAG), then seq: value is the key's character, the frame's bytes or a pocsag.Message.  Waits for the stream."""
+        from . import events
+        records, words, _ = self.gather_events(stream=stream)
+        return events.parse(records.cpu().numpy(), words.cpu().numpy())
+
     def set_groups(self, first_channels):
         """groups of consecutive channels with settings of their own: first_channels[g] = group g's first channel"""
         a = (C.c_int * len(first_channels))(*[int(x) for x in first_channels])
