@@ -1299,8 +1299,10 @@ double rdsp_engine_tone_gain(float tone_hz, float tau_us);
  *     either differs, or the group's FM reset is pending, the detector starts from zeros.  That one rule covers a changed K, a
  *     changed bank, a regrouping into a group with another K and a loaded blob that does not match.  The words are zeroed by
  *     rdsp_engine_reset, are maintained only for NFM groups with K > 0 (a channel of a group with K == 0 has zero words from the
- *     next update on and the records 255 / 0 / 0), stay with the channel through rdsp_engine_set_groups, and travel in
- *     rdsp_engine_save_state / load_state as a sixth optional part: header flag 32, 200 words per channel, behind the tone words;
+ *     next update on and the records 255 / 0 / 0 -- whatever the group's mode: K == 0 is looked at before the mode, so "off"
+ *     never leaves words behind, while a group outside NFM with K > 0 leaves them alone), stay with the channel through
+ *     rdsp_engine_set_groups, and travel in rdsp_engine_save_state / load_state as a sixth optional part: header flag 32, 200
+ *     words per channel, behind the tone words;
  *     rdsp_engine_state_bytes says so.  The blob of an engine without the search is unchanged; a blob with the part is refused by
  *     an engine without it (RDSP_ERR_NOT_READY, nothing changed); a blob without it zeroes the words of the channels it lands on.
  * - rdsp_engine_enable_tone_search works as rdsp_engine_enable_tone does: it takes no stream, waits for everything queued on the
@@ -1532,7 +1534,8 @@ int rdsp_engine_noise_taps(float tau_us, float *out /* [65], host */);
  * ring[16], re[64], im[64], e[8]; last and cur are stored plus one modulo 256, so zeros are a detector that holds no key).  A
  * stored K that differs from the one the channel is run with, or the group's pending FM reset, starts the detector from zeros;
  * a change of thresholds does not.  The words are zeroed by rdsp_engine_reset, maintained only for NFM groups with K > 0 (a
- * group with K == 0 has its channels' words zeroed in the stream, a group outside NFM leaves them alone), stay with the channel
+ * group with K == 0 has its channels' words zeroed in the stream at every update, whatever its mode -- K == 0 is looked at
+ * before the mode, as in the tone search; a group outside NFM with K > 0 leaves them alone), stay with the channel
  * through rdsp_engine_set_groups, and travel as a ninth optional part of the state blob (header flag 256): an engine without the
  * decoder writes the blob it always wrote and refuses one that carries the part (RDSP_ERR_NOT_READY); a blob without the part
  * zeroes the words.
